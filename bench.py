@@ -9,6 +9,10 @@ A "step" is one full G+D update (trainer.py:245-299 of the reference: G forward,
 discriminator updates, generator update incl. DAMSM loss and image encoder, Adam, EMA) on
 one synthetic CUB-shaped batch of B=20 per GPU (cfg/bird_style.yml), 3 stages 64/128/256 px,
 inputs resident in HBM.  Rank 0 prints ONE JSON line (see README / DESIGN.md section 6).
+
+A plain run sets up, warms up (choosing the launch mode), times --steps steps and prints the line.  --full adds the
+rest of what the benchmark measures: the roofline figures (each kernel timed alone), the CPU baseline and the extra
+f32 / 128 px / 64 px lines.  --dump-outputs DIR writes what the last timed step computed as float32 .npy files.
 """
 import argparse
 import json
@@ -54,13 +58,23 @@ def parse():
     ap.add_argument('--phases', action='store_true', help='also print per-phase times of an eager step (stderr)')
     ap.add_argument('--attn-fp8', action='store_true',
                     help='BASELINE config 5: FP8 (e4m3) operands for the attention key projection GEMM')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-also', action='store_true', help='skip the extra 64 px / 128 px / f32 lines')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--dump-shapes', default=None, help='write the shapes of the time-dominant kernel (for '
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the roofline figures, the CPU baseline and the extra 64 px / 128 px / f32 lines '
+                         '(off: only the headline figure)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one computed (every loss the step returns, a '
+                         'fixed seeded sample of each network\'s updated parameters) as DIR/<name>.npy, float32; that '
+                         'step starts from a state set up deterministically, the same in every run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-also', action='store_true', help='--full without the extra 64 px / 128 px / f32 lines')
+    ap.add_argument('--no-roofline', action='store_true', help='--full without the roofline figures')
+    ap.add_argument('--dump-shapes', default=None, help='with --full: write the shapes of the time-dominant kernel (for '
                                                         'tools/pmc_dominant.py) to this JSON file')
     ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def build(args, dev):
@@ -76,6 +90,9 @@ def build(args, dev):
     from sbagan.trainer import GANStep
     ops.set_compute_dtype(torch.bfloat16 if args.dtype == 'bf16' else torch.float32)
     ops.set_attention_fp8(args.attn_fp8)
+    # seeded before the networks are built: weights_init re-draws the conv / linear weights and BatchNorm
+    # parameters, but a conv bias (D_GET_LOGITS.outlogits) keeps its construction-time draw
+    torch.manual_seed(100)
     netG = {'model': model.G_NET, 'bert': model_bert.G_NET, 'mix': model_bert.G_NET_MIX}[args.variant]()
     netsD = [model.D_NET64(), model.D_NET128(), model.D_NET256()][:args.branch]
     torch.manual_seed(100)
@@ -332,6 +349,66 @@ def cpu_baseline(args):
                       'threads=%d' % (args.branch, cores), 'also': also}
 
 
+DUMP_SAMPLE = 1 << 20      # parameters sampled per flat buffer by --dump-outputs (4 MB each in float32)
+SETTLE_STEPS = 8           # --dump-outputs: deterministic eager steps that set up the state of the last timed step
+
+
+def settle(step, one_step):
+    """--dump-outputs: the state the last timed step starts from.  SETTLE_STEPS eager steps from the seeded initial
+    state in the library's deterministic-reduction mode (bit-identical from run to run; the Adam moments past their
+    sign-like first updates, which turn rounding-level gradients into whole learning-rate steps), then a snapshot of
+    everything a step mutates and of the random-number state.  The timed steps themselves run the default mode, whose
+    f32 atomics make the training trajectory differ from run to run by more than rounding after a few steps."""
+    from sbagan import ops
+    ops.set_deterministic(True)
+    try:
+        for _ in range(SETTLE_STEPS):
+            one_step()
+        step.finish()
+        torch.cuda.synchronize()
+    finally:
+        ops.set_deterministic(False)
+    return step.snapshot(), torch.cuda.get_rng_state()
+
+
+def restore_settled(step, graph, settled):
+    """write settle()'s state back in place (captured graphs and recordings keep their pointers) and bring the packed
+    weight copies the launches read in line with it"""
+    from sbagan import ops
+    snap, rng = settled
+    step.restore(snap)
+    if graph is not None and hasattr(graph, 'resync'):
+        graph.resync()
+    else:
+        for flat in [step.flatG] + list(step.flatD):
+            if flat.packs is not None:
+                flat.packs.refresh(ops.compute_dtype())
+        ops.weights_changed()
+    torch.cuda.set_rng_state(rng)
+
+
+def dump_outputs(dirname, out, step):
+    """--dump-outputs: what the timed path computed in its last step -- every loss the step returns, and the state its
+    updates leave: each network's parameters (the generator's EMA shadow too), as a fixed, seeded sample of DUMP_SAMPLE
+    elements of its flat f32 buffer where it is larger -- written as DIR/<name>.npy in float32."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    flats = [('netG_params', step.flatG.data), ('netG_ema_params', step.flatG.avg)]
+    flats += [('netD%d_params' % i, f.data) for i, f in enumerate(step.flatD)]
+    for n, (name, t) in enumerate(flats):
+        if t is None:
+            continue
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(1000 + n))
+            t = t[idx.sort().values.to(t.device)]
+        arrays[name] = t
+    for k, v in arrays.items():
+        fname = ''.join(c if (c.isalnum() or c in '_-') else '_' for c in k)
+        np.save(os.path.join(dirname, fname + '.npy'), v.detach().float().cpu().numpy())
+
+
 class _LightEncoder(object):
     """--image-encoder standin: regions = conv1x1(avgpool -> 17x17), code = Linear(global mean).  Isolates the
     cost of the hand-written Inception trunk; never the reported configuration."""
@@ -355,8 +432,8 @@ def supervise(args):
     base = [sys.executable, os.path.abspath(__file__)] + [a for a in sys.argv[1:]] + ['--child']
     ladder = [[], ['--graph', '1'], ['--graph', '0']]     # all launch modes -> hipGraph only -> eager
 
-    def child(extra):
-        p = subprocess.run(base + extra, stdout=subprocess.PIPE, text=True)
+    def child(extra, cmd=base):
+        p = subprocess.run(cmd + extra, stdout=subprocess.PIPE, text=True)
         lines = [l for l in p.stdout.splitlines() if l.startswith('{') and '"metric"' in l]
         return (json.loads(lines[-1]) if p.returncode == 0 and lines else None), p.returncode
     res = None
@@ -368,14 +445,21 @@ def supervise(args):
                                                                if n + 1 < len(ladder) else ''))
     if res is None:
         return 1
-    if not args.no_also and args.branch == 3 and args.dtype == 'bf16':
+    if args.full and not args.no_also and args.branch == 3 and args.dtype == 'bf16':
         # the other points the metric names (64 / 128 px) and the fp32 step (the parity-compliant number: bf16
         # storage costs ~2e-3 on a discriminator loss at B=4, tests/test_step_gpu.py), shorter runs
         also = []
         short = ['--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-roofline', '--no-also']
+        own = []        # (the outputs dumped are those of the headline run alone)
+        argv = iter(base)
+        for a in argv:
+            if a == '--dump-outputs':
+                next(argv, None)
+            elif not a.startswith('--dump-outputs='):
+                own.append(a)
         for label, extra in (('256px f32', ['--dtype', 'f32']), ('128px bf16', ['--branch', '2']),
                              ('64px bf16', ['--branch', '1'])):
-            r, _ = child(short + extra)
+            r, _ = child(short + extra, own)
             if r is not None:
                 also.append({'what': label, 'metric': r['metric'], 'value': r['value'], 'ms_per_step': r['ms_per_step'],
                              'dtype': r['dtype'], 'launch': r['config']['launch']})
@@ -450,6 +534,8 @@ def main():
         encode()
         return step.step(b['imgs'], b['sent_emb'], b['words_embs'], b['mask'], b['cap_lens'], b['class_ids'],
                          noise)
+
+    settled = settle(step, one_step) if args.dump_outputs else None
 
     if args.phases:
         for _ in range(3):
@@ -598,7 +684,15 @@ def main():
 
     sync_all()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if settled is not None and i == args.steps - 1:
+            # --dump-outputs: the last timed step starts from the settled state, so that what it computes -- the outputs
+            # written below -- is the same from run to run; the clock stops while the state is written back
+            sync_all()
+            t1 = time.perf_counter()
+            restore_settled(step, graph, settled)
+            sync_all()
+            t0 += time.perf_counter() - t1
         if graph is not None:
             graph.replay()
         else:
@@ -633,8 +727,10 @@ def main():
         'step_tflops': round(GFLOP_PER_IMG[args.branch] * ips / 1e3, 2),
         'step_mfma_frac': round(GFLOP_PER_IMG[args.branch] * ips / 1e3 / world / PEAK_TFLOPS[args.dtype], 4),
     }
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, step)
     if rank == 0:
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             big = measure_dominant_kernel(args, dev)
             dominant, fam = measure_igemm_kernels(args, dev, step, one_step, dump=args.dump_shapes)
             # `roofline` = the TIME-dominant kernel; the largest-FLOP launch and the whole family ride along
@@ -642,7 +738,7 @@ def main():
             res['roofline_largest_flop_kernel'] = big
             if fam is not None:
                 res['roofline_igemm_family'] = fam
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(args)
         print(json.dumps(res), flush=True)
     if multi:

@@ -5,10 +5,10 @@ bench.py --dump-shapes writes the shapes this kernel handles in one step (geomet
 launches every one of them that many times (after one warm-up launch each) for rocprofv3 PMC passes, one counter per pass
 (MI355X_MICROARCH.md, HBM section):
 
-    python bench.py --child --steps 2 --warmup 2 --no-cpu-baseline --no-also --dump-shapes gpurun_out/dominant_shapes.json
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out_f -- python3 tools/pmc_dominant.py gpurun_out/dominant_shapes.json
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out_w -- python3 tools/pmc_dominant.py gpurun_out/dominant_shapes.json
-    python3 tools/pmc_dominant.py --collect gpurun_out/dominant_shapes.json out_f out_w > profiles/rNN_pmc_dominant_kernel.json
+    python bench.py --child --full --steps 2 --warmup 2 --no-cpu-baseline --no-also --dump-shapes dominant_shapes.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out_f -- python3 tools/pmc_dominant.py dominant_shapes.json
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out_w -- python3 tools/pmc_dominant.py dominant_shapes.json
+    python3 tools/pmc_dominant.py --collect dominant_shapes.json out_f out_w > profiles/rNN_pmc_dominant_kernel.json
 (tools/pmc_dominant.sh runs the four steps.)"""
 import csv
 import glob
