@@ -227,8 +227,8 @@ __device__ __forceinline__ void tile_epilogue(f32x16_t (&acc)[TM][TN], const boo
 // LDS: double-buffered A[BM] and B[BN] rows of 80 B (64 data + 16 pad: the
 // pad makes the 16-lane ds_read_b128 groups hit 16 distinct 4-bank slots).
 // ---------------------------------------------------------------------------
-template <typename T, int BM, int BN, int WM, int WN, int KS, int KG, int PF>
-__global__ __launch_bounds__((BM / WM) * (BN / WN) * 64 * KG, (sizeof(T) == 2 && BM * BN == 128 * 128 && KS == 1) ? 3 : 1) void igemm_kernel(const T* __restrict__ x, const T* __restrict__ w,
+template <typename T, int BM, int BN, int WM, int WN, int KS>
+__global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM * BN == 128 * 128 && KS == 1) ? 3 : 1) void igemm_kernel(const T* __restrict__ x, const T* __restrict__ w,
                                                     T* __restrict__ y, const T* __restrict__ addend,
                                                     float* __restrict__ stats, const sba_conv_geom g,
                                                     const int M, float* __restrict__ ws,
@@ -237,35 +237,25 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64 * KG, (sizeof(T) == 2 &&
     constexpr int KS_CH = 64 / (int)sizeof(T);   // channels per slab
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int WAVES_N = BN / WN;
-    constexpr int NT = (BM / WM) * (BN / WN) * 64;   // threads of one K-group: one wave per WM x WN sub-tile
-    constexpr int NTT = NT * KG;                     // KG groups walk disjoint K ranges of the same tile
+    constexpr int NT = (BM / WM) * (BN / WN) * 64;   // one wave per WM x WN sub-tile
     constexpr int RP = NT / 4;                       // tile rows staged per pass (4 threads x 16 B per row)
     constexpr int AI = (BM + RP - 1) / RP, BI = (BN + RP - 1) / RP;    // 16-byte loads per thread per slab
     static_assert(BM % WM == 0 && BN % WN == 0 && WM % 32 == 0 && WN % 32 == 0, "tile");
     constexpr int TILE_BYTES = (BM + BN) * ROWB;
-    // PF = stages of global loads kept in flight (register sets); PF == 1: double-buffered LDS, one
-    // stage ahead.  PF == 3 (small tiles, ~1 workgroup per CU, nothing else to hide the load latency
-    // behind): three register sets + three LDS buffers, loads issued three stages ahead.
-    static_assert(PF == 1 || PF == 3, "prefetch depth");
-    constexpr int NBUF = PF == 1 ? 2 : 3;
-    constexpr int GROUP_BYTES = NBUF * KS * TILE_BYTES;
-    static_assert(KG == 1 || (KG - 1) * BM * BN * 4 <= KG * GROUP_BYTES, "K-group partials fit in the staging buffers");
+    constexpr int STAGING_BYTES = 2 * KS * TILE_BYTES;      // double-buffered LDS, global loads one stage ahead
 
-    // KS slabs are staged per barrier (KS > 1 for the small tiles, whose MFMA work per slab is short);
-    // each K-group has its own double buffer
+    // KS slabs are staged per barrier (KS > 1 for the small tiles, whose MFMA work per slab is short)
     // The epilogue's row table and statistics accumulators live INSIDE the (by then free) staging buffers,
     // behind the staged bf16 output tile: the 64x64 tile then needs 36 KB instead of 40.75 KB of LDS and a CU
     // holds four workgroups instead of three.
     constexpr int EPI_OFF = sizeof(T) == 2 ? BM * (BN * 2 + 16) : 0;
     constexpr int EPI_END = EPI_OFF + BM * 4 + BN * 8;
-    constexpr int LDS_BYTES = KG * GROUP_BYTES > EPI_END ? KG * GROUP_BYTES : EPI_END;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_all[LDS_BYTES];
-    int* rowoff = reinterpret_cast<int*>(lds_all + EPI_OFF);
-    float* s_stat = reinterpret_cast<float*>(lds_all + EPI_OFF + BM * 4);
+    constexpr int LDS_BYTES = STAGING_BYTES > EPI_END ? STAGING_BYTES : EPI_END;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
+    int* rowoff = reinterpret_cast<int*>(lds + EPI_OFF);
+    float* s_stat = reinterpret_cast<float*>(lds + EPI_OFF + BM * 4);
 
-    const int kg = KG > 1 ? (int)threadIdx.x / NT : 0;
-    const int tid = KG > 1 ? (int)threadIdx.x - kg * NT : (int)threadIdx.x;
-    unsigned char* const lds = lds_all + kg * GROUP_BYTES;
+    const int tid = (int)threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
     const int wm0 = (wid / WAVES_N) * WM, wn0 = (wid % WAVES_N) * WN;
     const int m_base = blockIdx.x * BM, n_base = blockIdx.y * BN;
@@ -303,12 +293,9 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64 * KG, (sizeof(T) == 2 &&
     const int xcs = g.x_cstride ? g.x_cstride : g.Cin;       // input pixel stride (channels)
     const int ycs = g.y_cstride ? g.y_cstride : g.Cout;      // output pixel stride (channels)
 
-    // split-K: this block walks slabs [b_begin, b_end), its K-group kg the sub-range [s_begin, s_end)
-    const int b_begin = blockIdx.z * slabs_per_split;
-    const int b_end = min(b_begin + slabs_per_split, nsteps);
-    const int per_group = KG > 1 ? ((b_end - b_begin + KG * KS - 1) / (KG * KS)) * KS : b_end - b_begin;
-    const int s_begin = b_begin + kg * per_group;
-    const int s_end = min(s_begin + per_group, b_end);
+    // split-K: this block walks slabs [s_begin, s_end)
+    const int s_begin = blockIdx.z * slabs_per_split;
+    const int s_end = min(s_begin + slabs_per_split, nsteps);
 
     // Address generation is hoisted out of the per-slab path: slabs are consumed in order, so the
     // (tap, channel-slab) position is tracked incrementally (no division), the per-row gather
@@ -337,7 +324,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64 * KG, (sizeof(T) == 2 &&
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, w_bytes, 0x00020000);
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
-    uint4 rra[PF][KS][AI], rrb[PF][KS][BI];
+    uint4 rra[KS][AI], rrb[KS][BI];
     auto gload = [&](uint4 (&ra)[KS][AI], uint4 (&rb)[KS][BI]) {
 #pragma unroll
         for (int k = 0; k < KS; ++k) {
@@ -399,80 +386,23 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64 * KG, (sizeof(T) == 2 &&
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int nstages = (per_group + KS - 1) / KS;      // uniform over the groups (dead slabs load zeros)
-    if (PF == 1) {
-        gload(rra[0], rrb[0]);
-        lstore(0, rra[0], rrb[0]);
-        __syncthreads();
-        for (int s = 0; s < nstages; ++s) {
-            const int buf = s & 1;
-            if (s + 1 < nstages) gload(rra[0], rrb[0]);
+    const int nstages = (s_end - s_begin + KS - 1) / KS;
+    gload(rra, rrb);
+    lstore(0, rra, rrb);
+    __syncthreads();
+    for (int s = 0; s < nstages; ++s) {
+        const int buf = s & 1;
+        if (s + 1 < nstages) gload(rra, rrb);
 #pragma unroll
-            for (int k = 0; k < KS; ++k) {
-                const unsigned char* base = lds + (buf * KS + k) * TILE_BYTES;
-                Mma<T>::template slab<TM, TN, ROWB>(base + wm0 * ROWB, base + (BM + wn0) * ROWB, lane, acc);
-            }
-            if (s + 1 < nstages) lstore(buf ^ 1, rra[0], rrb[0]);
-            __syncthreads();
+        for (int k = 0; k < KS; ++k) {
+            const unsigned char* base = lds + (buf * KS + k) * TILE_BYTES;
+            Mma<T>::template slab<TM, TN, ROWB>(base + wm0 * ROWB, base + (BM + wn0) * ROWB, lane, acc);
         }
-    } else {
-        // stage s: LDS buffer s % 3 holds it; register set (s+1) % 3 and (s+2) % 3 hold the loads of
-        // stages s+1, s+2 (in flight); set s % 3 is free -> issue stage s+3 into it.  Stages past the
-        // end load zeros (OOB offsets), so the trip count is simply rounded up to a multiple of 3.
-        constexpr int P1 = PF > 1 ? 1 : 0, P2 = PF > 2 ? 2 : 0;
-        gload(rra[0], rrb[0]);
-        gload(rra[P1], rrb[P1]);
-        gload(rra[P2], rrb[P2]);
-        lstore(0, rra[0], rrb[0]);
-        __syncthreads();
-        auto stage = [&](int buf, uint4 (&fa)[KS][AI], uint4 (&fb)[KS][BI], const uint4 (&na)[KS][AI],
-                         const uint4 (&nb)[KS][BI]) {
-            gload(fa, fb);
-#pragma unroll
-            for (int k = 0; k < KS; ++k) {
-                const unsigned char* base = lds + (buf * KS + k) * TILE_BYTES;
-                Mma<T>::template slab<TM, TN, ROWB>(base + wm0 * ROWB, base + (BM + wn0) * ROWB, lane, acc);
-            }
-            lstore(buf == 2 ? 0 : buf + 1, na, nb);
-            __syncthreads();
-        };
-        for (int s = 0; s < nstages; s += 3) {
-            stage(0, rra[0], rrb[0], rra[P1], rrb[P1]);
-            stage(1, rra[P1], rrb[P1], rra[P2], rrb[P2]);
-            stage(2, rra[P2], rrb[P2], rra[0], rrb[0]);
-        }
-    }
-
-    if (KG > 1) {
-        // sum the K-groups' partial tiles into group 0 through the (now free) staging buffers
-        float* red = reinterpret_cast<float*>(lds_all);
-        if (kg > 0) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        red[(((kg - 1) * TM * TN + i * TN + j) * 16 + r) * NT + tid] = acc[i][j][r];
-        }
-        __syncthreads();
-        if (kg == 0) {
-#pragma unroll
-            for (int q = 0; q < KG - 1; ++q)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            acc[i][j][r] += red[((q * TM * TN + i * TN + j) * 16 + r) * NT + tid];
-        }
+        if (s + 1 < nstages) lstore(buf ^ 1, rra, rrb);
         __syncthreads();
     }
-    const bool lead = KG == 1 || kg == 0;       // the group that owns the summed tile
 
     if (ws) {
-        if (!lead) return;
         // split-K partial: f32 atomics into ws[m][co]; y / addend / stats are done by splitk_finish_kernel
         const int col_s = lane & 31, rsel_s = 4 * (lane >> 5);
 #pragma unroll
@@ -489,8 +419,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64 * KG, (sizeof(T) == 2 &&
         return;
     }
 
-    // (the main loop / K-group reduction ended with a barrier: the staging buffers are free)
-    for (int r = threadIdx.x; r < BM; r += NTT) {
+    // (the main loop ended with a barrier: the staging buffers are free)
+    for (int r = threadIdx.x; r < BM; r += NT) {
         const int m = m_base + r;
         int off = -1;
         if (m < M) {
@@ -500,10 +430,10 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64 * KG, (sizeof(T) == 2 &&
         }
         rowoff[r] = off;
     }
-    for (int c = threadIdx.x; c < 2 * BN; c += NTT) s_stat[c] = 0.f;
+    for (int c = threadIdx.x; c < 2 * BN; c += NT) s_stat[c] = 0.f;
     __syncthreads();
-    tile_epilogue<T, BM, BN, TM, TN, NTT, LDS_BYTES>(acc, lead, lds_all, rowoff, s_stat, wm0, wn0, lane, n_base, ycs, g,
-                                                     y, addend, stats, ex);
+    tile_epilogue<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, true, lds, rowoff, s_stat, wm0, wn0, lane, n_base, ycs, g,
+                                                    y, addend, stats, ex);
 }
 
 // ---------------------------------------------------------------------------
@@ -543,17 +473,14 @@ __device__ __forceinline__ void lds_dma16(const __amdgpu_buffer_rsrc_t rsrc, con
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 __device__ __forceinline__ void wg_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
-// Split-K without a finishing launch: every split adds its partial tile into the zero-filled f32 workspace with
-// device-scope atomics, then takes a ticket for its output tile; the LAST arrival reads the complete sums back
-// (device-scope loads: the partial sums were performed at the memory side, not in this XCD's L2), leaves the
-// workspace and the ticket zero for the next user, and runs the ordinary epilogue (bias / ReLU / addend / mask / BN
-// statistics / y) as if it had computed the whole K range itself.  Nobody waits for anybody: a workgroup that is
-// not last simply exits.  Returns true for the workgroup that has to run the epilogue.
-constexpr int SPLITK_TICKET_BYTES = 64 * 1024;      // tail of the workspace: one int32 ticket per output tile
+// Split-K partial sums: every split adds its partial tile into the zero-filled f32 workspace with device-scope
+// atomics; splitk_finish_kernel then runs the epilogue and leaves the workspace zero.  (The last arriving split finishing
+// its tile inside the GEMM kernel -- one ticket per tile in the workspace tail -- passed the GPU suite but measured no
+// gain on the step, 14.96 vs 14.78 ms with 75 finishing launches fewer: the last arrival's 16 KB device-scope reload +
+// epilogue sits at the tail of every tile, where the finishing launch spreads the same work over the whole chip; removed.)
 template <int TM, int TN>
-__device__ __forceinline__ bool splitk_arrive(float* __restrict__ ws, int* __restrict__ tickets, f32x16_t (&acc)[TM][TN],
-                                              const int m0, const int n0, const int lane, const int M, const int Cout,
-                                              const int tile_id, int* s_ticket) {
+__device__ __forceinline__ void splitk_accumulate(float* __restrict__ ws, const f32x16_t (&acc)[TM][TN], const int m0,
+                                                  const int n0, const int lane, const int M, const int Cout) {
     const int col_s = lane & 31, rsel_s = 4 * (lane >> 5);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -566,38 +493,6 @@ __device__ __forceinline__ bool splitk_arrive(float* __restrict__ ws, int* __res
                 if (m < M && co < Cout) atomicAdd(&ws[(int64_t)m * Cout + co], acc[i][j][r]);
             }
     }
-    if (!tickets) return false;                 // the caller launches splitk_finish_kernel
-    // Order "my partial sums, then my ticket" WITHOUT a release fence: at agent scope a fence writes back and
-    // invalidates the whole L2 of this XCD (measured: the step went from 14.4 to 18.6 ms).  The partial sums are
-    // device-scope atomics, performed at the memory side and acknowledged once performed; vmcnt counts them, so after
-    // s_waitcnt vmcnt(0) they are visible to every later device-scope access -- the ticket, and the last arrival's
-    // device-scope loads, which bypass the L2 themselves.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) *s_ticket = atomicAdd(&tickets[tile_id], 1);
-    __syncthreads();
-    const int ticket = *s_ticket;
-    __syncthreads();                            // s_ticket is a word of the staging ring: the epilogue reuses it
-    if (ticket != (int)gridDim.z - 1) return false;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int co = n0 + j * 32 + col_s;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel_s;
-                float v = 0.f;
-                if (m < M && co < Cout) {
-                    float* p = &ws[(int64_t)m * Cout + co];
-                    v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(p, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                acc[i][j][r] = v;
-            }
-    }
-    if (threadIdx.x == 0) __hip_atomic_store(&tickets[tile_id], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
 }
 
 #ifdef SBA_DMA_TRACE     // tools/trace_dma.py: per-stage s_memtime stamps of wave 0 of the first workgroups
@@ -619,7 +514,7 @@ template <int BM, int BN, int WM, int WN, int KS, int D>
 __device__ __forceinline__ void igemm_dma_body(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ w, bf16_t* __restrict__ y,
     const bf16_t* __restrict__ addend, float* __restrict__ stats, const sba_conv_geom& g, const int M,
-    float* __restrict__ ws, int* __restrict__ tickets, const int slabs_per_split, const EpiX ex, const int gx,
+    float* __restrict__ ws, const int slabs_per_split, const EpiX ex, const int gx,
     const int gy, const int L, const int bz, const int nmajor DMA_TRACE_PARAM) {
     typedef bf16_t T;
     constexpr int TM = WM / 32, TN = WN / 32, WAVES_N = BN / WN;
@@ -823,10 +718,9 @@ __device__ __forceinline__ void igemm_dma_body(
     wait_vmcnt<0>();        // the dead stages issued past the end still write (zeros) into the ring
     wg_barrier();
 
-    if (ws) {
-        if (!splitk_arrive<TM, TN>(ws, tickets, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout, L,
-                                   reinterpret_cast<int*>(lds_all)))
-            return;
+    if (ws) {           // split-K: splitk_finish_kernel runs the epilogue
+        splitk_accumulate<TM, TN>(ws, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout);
+        return;
     }
     for (int r = threadIdx.x; r < BM; r += NT) {
         const int m = m_base + r;
@@ -848,9 +742,9 @@ template <int BM, int BN, int WM, int WN, int KS, int D>
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_dma_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ w, bf16_t* __restrict__ y,
     const bf16_t* __restrict__ addend, float* __restrict__ stats, const sba_conv_geom g, const int M,
-    float* __restrict__ ws, int* __restrict__ tickets, const int slabs_per_split, const EpiX ex, const int gx,
+    float* __restrict__ ws, const int slabs_per_split, const EpiX ex, const int gx,
     const int gy, const int nmajor DMA_TRACE_PARAM) {
-    igemm_dma_body<BM, BN, WM, WN, KS, D>(x, w, y, addend, stats, g, M, ws, tickets, slabs_per_split, ex, gx, gy,
+    igemm_dma_body<BM, BN, WM, WN, KS, D>(x, w, y, addend, stats, g, M, ws, slabs_per_split, ex, gx, gy,
                                           (int)blockIdx.x, (int)blockIdx.z, nmajor DMA_TRACE_ARG_FWD);
 }
 
@@ -877,7 +771,7 @@ template <int BM, int BN, int WM, int WN, int D>
 __device__ __forceinline__ void igemm_dma2_body(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ w, bf16_t* __restrict__ y,
     const bf16_t* __restrict__ addend, float* __restrict__ stats, const sba_conv_geom& g, const int M,
-    float* __restrict__ ws, int* __restrict__ tickets, const int slabs_per_split, const EpiX ex, const int gx,
+    float* __restrict__ ws, const int slabs_per_split, const EpiX ex, const int gx,
     const int gy, const int L, const int bz, const int nmajor DMA_TRACE_PARAM) {
     typedef bf16_t T;
     constexpr int TM = WM / 32, TN = WN / 32, WAVES_N = BN / WN;
@@ -1108,10 +1002,9 @@ __device__ __forceinline__ void igemm_dma2_body(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     wg_barrier();
 
-    if (ws) {
-        if (!splitk_arrive<TM, TN>(ws, tickets, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout, L,
-                                   reinterpret_cast<int*>(lds_all)))
-            return;
+    if (ws) {           // split-K: splitk_finish_kernel runs the epilogue
+        splitk_accumulate<TM, TN>(ws, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout);
+        return;
     }
     for (int r = threadIdx.x; r < BM; r += NT) {
         const int m = m_base + r;
@@ -1133,9 +1026,9 @@ template <int BM, int BN, int WM, int WN, int D>
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_dma2_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ w, bf16_t* __restrict__ y,
     const bf16_t* __restrict__ addend, float* __restrict__ stats, const sba_conv_geom g, const int M,
-    float* __restrict__ ws, int* __restrict__ tickets, const int slabs_per_split, const EpiX ex, const int gx,
+    float* __restrict__ ws, const int slabs_per_split, const EpiX ex, const int gx,
     const int gy, const int nmajor DMA_TRACE_PARAM) {
-    igemm_dma2_body<BM, BN, WM, WN, D>(x, w, y, addend, stats, g, M, ws, tickets, slabs_per_split, ex, gx, gy,
+    igemm_dma2_body<BM, BN, WM, WN, D>(x, w, y, addend, stats, g, M, ws, slabs_per_split, ex, gx, gy,
                                        (int)blockIdx.x, (int)blockIdx.z, nmajor DMA_TRACE_ARG_FWD);
 }
 
@@ -1165,7 +1058,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_dma2_group_k
     const GroupItem& it = A.it[i];
     const sba_conv_geom g = it.g;
     // A.sps != 0: grid.z K splits, partial sums added into the item's f32 workspace, finished by splitk_finish_group_kernel
-    igemm_dma2_body<BM, BN, WM, WN, D>(it.x, it.w, it.y, it.addend, nullptr, g, it.M, A.sps ? it.ws : nullptr, nullptr,
+    igemm_dma2_body<BM, BN, WM, WN, D>(it.x, it.w, it.y, it.addend, nullptr, g, it.M, A.sps ? it.ws : nullptr,
                                        A.sps ? A.sps : g.ntaps * (g.Cin / 64), EpiX{it.bias, it.mask, 0}, it.gx, it.gy,
                                        (int)blockIdx.x - it.tile_begin, (int)blockIdx.z, it.nmajor DMA_TRACE_ARG_FWD);
 }
@@ -1179,7 +1072,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_dma_group_ke
         if (k < A.n && (int)blockIdx.x >= A.it[k].tile_begin) i = k;
     const GroupItem& it = A.it[i];
     const sba_conv_geom g = it.g;
-    igemm_dma_body<BM, BN, WM, WN, KS, D>(it.x, it.w, it.y, it.addend, nullptr, g, it.M, nullptr, nullptr,
+    igemm_dma_body<BM, BN, WM, WN, KS, D>(it.x, it.w, it.y, it.addend, nullptr, g, it.M, nullptr,
                                           g.ntaps * (g.Cin / 32), EpiX{it.bias, it.mask, 0}, it.gx, it.gy,
                                           (int)blockIdx.x - it.tile_begin, 0, it.nmajor DMA_TRACE_ARG_FWD);
 }
@@ -1668,173 +1561,6 @@ __global__ __launch_bounds__(256) void pack_frag_kernel(const sba_frag_desc* __r
 }
 
 // ---------------------------------------------------------------------------
-// Persistent halo-tile 3x3 convolution (Cin = 64): the kernel above pays, per 8 x 32 output tile, a serialised
-// prologue (halo staging through registers, first weight tap), nine barriers for the double-buffered weight
-// taps and an epilogue -- 17.8 us per workgroup-round for 5.8 us of MFMA issue.  Here
-//   * a workgroup is PERSISTENT (one per CU, 160 KB of LDS) and walks tiles t = id, id + G, ...;
-//   * the weights of all nine taps stay in LDS for the whole launch (9 x 64 x 128 B = 72 KB, loaded once);
-//   * the halo tile of tile t+1 is fetched by LDS-DMA into the second halo buffer while tile t's 144 MFMAs per
-//     wave run -- no barrier inside a tile's main loop, one counted vmcnt wait + barrier per tile;
-//   * rows are 128 B (64 channels) with the chunk swizzle c ^ ((row >> 1) & 7): conflict-free ds_read_b128 for
-//     the shifted tap views and for the weight rows alike; out-of-image halo pixels are out-of-range DMA lanes
-//     (zeros).
-// Epilogue (BatchNorm statistics, bias / ReLU / mask, addend, LDS-transposed NHWC store) is the shared one and
-// stages through the halo buffer the tile has just finished reading.
-// ---------------------------------------------------------------------------
-template <int UPS>
-__global__ __launch_bounds__(256) void conv3x3_halo2_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
-                                                            bf16_t* __restrict__ y, const bf16_t* __restrict__ addend,
-                                                            float* __restrict__ stats, const sba_conv_geom g,
-                                                            const EpiX ex, const int tiles, const int wgs_per_nblock) {
-    typedef bf16_t T;
-    constexpr int TH = 8, TW = 32, BM = TH * TW, BN = 64;
-    constexpr int HR = UPS ? TH / 2 + 2 : TH + 2, HC = UPS ? TW / 2 + 2 : TW + 2, HP = HR * HC;
-    constexpr int W_BYTES = 9 * BN * 128;                       // 73,728
-    constexpr int OUT_BYTES = BM * (BN * 2 + 16);               // 36,864: the epilogue's staging tile
-    constexpr int HI = (HP * 8 + 255) / 256;                    // DMA instructions per wave per halo tile
-    constexpr int WI = 9 * BN * 8 / 256;                        // ... for the weights (18)
-    // a halo buffer holds the DMA image (HI * 4 slots of 1 KB: the last slots are partly out-of-range lanes, which
-    // write zeros) and, during the epilogue, the staging tile + the row table + the statistics accumulators
-    constexpr int EPI_OFF = OUT_BYTES;
-    constexpr int HALO_NEED = HI * 4 * 1024 > EPI_OFF + BM * 4 + BN * 8 ? HI * 4 * 1024 : EPI_OFF + BM * 4 + BN * 8;
-    constexpr int HALO_BYTES = (HALO_NEED + 1023) / 1024 * 1024;
-    constexpr int TM = 2, TN = 2;
-    constexpr int LDS_BYTES = W_BYTES + 2 * HALO_BYTES;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    static_assert(HI <= 63, "vmcnt field");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];
-    unsigned char* const lW = lds;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nb = blockIdx.x / wgs_per_nblock, wg = blockIdx.x - nb * wgs_per_nblock;
-    const int n_base = nb * BN;
-    const int tiles_x = g.OW / TW, tiles_y = g.OH / TH;
-    const int xcs = g.x_cstride ? g.x_cstride : g.Cin;
-    const int ycs = g.y_cstride ? g.y_cstride : g.Cout;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    constexpr uint32_t OOB = 0xFFFFFFFFu;
-    const uint32_t x_bytes = (uint32_t)((int64_t)g.N * g.IH * g.IW * xcs * 2);
-    const uint32_t w_bytes = (uint32_t)((int64_t)g.Cout * 9 * 64 * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, w_bytes, 0x00020000);
-
-    // ---- weights: LDS row R = tap * 64 + co (128 B), DMA instruction q of wave `wid` covers rows 8 * (wid + 4 q) ..
-#pragma unroll
-    for (int q = 0; q < WI; ++q) {
-        const int R = 8 * (wid + 4 * q) + (lane >> 3);
-        const int tap = R >> 6, co = n_base + (R & 63);
-        const uint32_t c = (uint32_t)((lane & 7) ^ ((R >> 1) & 7));
-        const uint32_t o = co < g.Cout ? ((uint32_t)co * 9u + (uint32_t)tap) * 128u + c * 16u : OOB;
-        lds_dma16(wr, o, 0u, lds_base + (uint32_t)((wid + 4 * q) * 1024));
-    }
-    // ---- halo tile of output tile `t` into buffer `buf`: lane slot idx = 64 * (wid + 4 q) + lane -> pixel idx >> 3
-    auto issue_halo = [&](const int t, const int buf) {
-        const int tx_ = t % tiles_x, ty_ = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
-        const int oy0 = ty_ * TH, ox0 = tx_ * TW;
-        const int sy0 = UPS ? (oy0 >> 1) - 1 : oy0 - 1, sx0 = UPS ? (ox0 >> 1) - 1 : ox0 - 1;
-        const uint32_t dst = lds_base + (uint32_t)(W_BYTES + buf * HALO_BYTES + wid * 1024);
-        const bool live = t < tiles;
-#pragma unroll
-        for (int q = 0; q < HI; ++q) {
-            const int idx = 64 * (wid + 4 * q) + lane;
-            const int p = idx >> 3;
-            const int hr = p / HC, hc = p - hr * HC;
-            const int iy = sy0 + hr, ix = sx0 + hc;
-            const bool ok = live && p < HP && iy >= 0 && iy < g.IH && ix >= 0 && ix < g.IW;
-            const uint32_t c = (uint32_t)((idx & 7) ^ ((p >> 1) & 7));
-            const uint32_t o = ok ? (uint32_t)((n * g.IH + iy) * g.IW + ix) * (uint32_t)(xcs * 2) +
-                                        (uint32_t)(g.x_coff * 2) + c * 16u
-                                  : OOB;
-            lds_dma16(xr, o, 0u, dst + (uint32_t)(4 * q * 1024));
-        }
-    };
-    int t = wg;
-    issue_halo(t, 0);
-    const int rl = lane & 31, hf = lane >> 5;
-    int buf = 0;
-    for (; t < tiles; t += wgs_per_nblock, buf ^= 1) {
-        // next tile's halo into the other buffer (its last reader was tile t-1's epilogue, which ended with a barrier)
-        issue_halo(t + wgs_per_nblock, buf ^ 1);
-        wait_vmcnt<HI>();                   // everything but the HI loads just issued: this tile's halo (and the weights)
-        wg_barrier();
-        const unsigned char* lA = lds + W_BYTES + buf * HALO_BYTES;
-        f32x16_t acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        const int bsw = (rl >> 1) & 7;
-        // one wave per SIMD: nothing else hides the LDS latency, so the 16 fragments of tap t+1 are read into a
-        // second register set while the 16 MFMAs of tap t (512 cycles) run
-        struct TapFrags { bf16x8_t a[4][TM], b[4][TN]; };
-        auto load_tap = [&](TapFrags& F, const int tap) {
-            const int ky = tap / 3, kx = tap - ky * 3;
-            int hp[TM];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                int hr, hc;
-                if (UPS) {
-                    hr = ((2 * wid + i + ky - 1) >> 1) + 1;
-                    hc = ((rl + kx - 1) >> 1) + 1;
-                } else {
-                    hr = 2 * wid + i + ky;
-                    hc = rl + kx;
-                }
-                hp[i] = hr * HC + hc;
-            }
-            const unsigned char* bp = lW + (tap * 64 + rl) * 128;
-#pragma unroll
-            for (int k16 = 0; k16 < 4; ++k16) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-                    F.a[k16][i] = *reinterpret_cast<const bf16x8_t*>(lA + hp[i] * 128 + (((2 * k16 + hf) ^ ((hp[i] >> 1) & 7)) << 4));
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    F.b[k16][j] = *reinterpret_cast<const bf16x8_t*>(bp + j * 32 * 128 + (((2 * k16 + hf) ^ bsw) << 4));
-            }
-        };
-        auto mma_tap = [&](const TapFrags& F) {
-#pragma unroll
-            for (int k16 = 0; k16 < 4; ++k16)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F.a[k16][i], F.b[k16][j], acc[i][j], 0, 0, 0);
-        };
-        TapFrags F0, F1;
-        load_tap(F0, 0);
-#pragma unroll
-        for (int tap = 0; tap < 8; tap += 2) {
-            load_tap(F1, tap + 1);
-            mma_tap(F0);
-            __builtin_amdgcn_sched_barrier(0);
-            load_tap(F0, tap + 2);
-            mma_tap(F1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        mma_tap(F0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        wg_barrier();           // every wave has finished reading this tile's halo: the epilogue may stage through it
-        unsigned char* const stage = lds + W_BYTES + buf * HALO_BYTES;
-        int* rowoff = reinterpret_cast<int*>(stage + EPI_OFF);
-        float* s_stat = reinterpret_cast<float*>(stage + EPI_OFF + BM * 4);
-        {
-            const int tx_ = t % tiles_x, ty_ = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
-            rowoff[tid] = (n * g.OH + ty_ * TH + (tid >> 5)) * g.OW + tx_ * TW + (tid & 31);      // BM == 256 threads
-            if (tid < 2 * BN) s_stat[tid] = 0.f;
-        }
-        __syncthreads();
-        tile_epilogue<T, BM, BN, TM, TN, 256, HALO_BYTES>(acc, true, stage, rowoff, s_stat, wid * 64, 0, lane, n_base, ycs,
-                                                          g, y, addend, stats, ex, t);
-        __syncthreads();        // staging tile / row table / accumulators free again (next tile's halo DMA lands here)
-    }
-    wait_vmcnt<0>();            // the dead halo issued for the tile past the end
-}
-
-// ---------------------------------------------------------------------------
 // weight gradient: dw[co][tap][ci] += sum_pixels dy[pixel][co] * x[gather(pixel,tap)][ci]
 // Workgroup = one 64(co) x 64(ci) tile of one tap; its 4 waves each walk their
 // own 16-pixel slices of the workgroup's pixel range, then reduce through LDS.
@@ -2016,11 +1742,10 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ x, con
 // weight gradient, small-pixel-count regime (GEMM-like layers at 4x4 / 8x8 maps with
 // thousands of channels): every wave owns its own 64(co) x 64(ci) tile of one tap and walks
 // ALL pixels of the block's range, so there is no cross-wave reduction; the four waves of a
-// workgroup share the dy slice (same co tile) and differ in (tap, ci tile).  CT = 2: every wave owns
-// TWO co tiles (128 x 64 outputs) against the same x slice -- these launches are bound by the L2 traffic
-// of the operand slices (each wave streams its own), 0.375 instead of 0.625 KB per MFMA.
+// workgroup share the dy slice (same co tile) and differ in (tap, ci tile).  (Two co tiles per wave against the
+// same x slice, 0.375 instead of 0.625 KB of operands per MFMA: measured 20-35 % SLOWER at 4 waves per SIMD, removed.)
 // ---------------------------------------------------------------------------
-template <typename T, int CT>
+template <typename T>
 __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                           float* __restrict__ dw, const sba_conv_geom g,
                                                           const int M, const int chunks_per_split,
@@ -2030,12 +1755,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
     constexpr int CH = 16 / (int)sizeof(T);
     constexpr int CPR = 64 / CH;
     constexpr int LPT = 16 * CPR / 64;               // 16-byte loads per lane for a wave-private slice
-    constexpr int APT = (16 * CPR * CT + 255) / 256; // 16-byte loads per thread for the shared dy slice(s)
+    constexpr int APT = (16 * CPR + 255) / 256;      // 16-byte loads per thread for the shared dy slice
     constexpr int SLICE = 16 * ROWS;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[(CT + 4) * SLICE];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[5 * SLICE];
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int co0 = blockIdx.x * (64 * CT);
+    const int co0 = blockIdx.x * 64;
     const int ci_tiles = (g.Cin + 63) / 64;
     const int item = blockIdx.y * 4 + wid;
     const bool active = item < g.ntaps * ci_tiles;
@@ -2049,17 +1774,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
     const int sub = g.OHs * g.OWs;
 
     unsigned char* sa = lds;
-    unsigned char* sb = lds + (CT + wid) * SLICE;
+    unsigned char* sb = lds + (1 + wid) * SLICE;
 
-    f32x16_t acc[CT][2][2];
+    f32x16_t acc[2][2];
 #pragma unroll
-    for (int s = 0; s < CT; ++s)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[s][i][j][r] = 0.f;
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     const int total_chunks = (M + 15) / 16;
     const int chunk_lo = blockIdx.z * chunks_per_split;
@@ -2072,8 +1795,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
         for (int u = 0; u < APT; ++u) {
             const int idx = tid + 256 * u;
             va[u] = make_uint4(0, 0, 0, 0);
-            if (idx < 16 * CPR * CT) {
-                const int pix = idx / (CPR * CT), cc = idx - pix * (CPR * CT);
+            if (idx < 16 * CPR) {
+                const int pix = idx / CPR, cc = idx - pix * CPR;
                 const int m = m0 + pix, co = co0 + cc * CH;
                 if (m < M && co < g.Cout) {
                     const int n = (int)fdiv(m, dsub), rem = m - n * sub;
@@ -2109,9 +1832,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
 #pragma unroll
         for (int u = 0; u < APT; ++u) {
             const int idx = tid + 256 * u;
-            if (idx < 16 * CPR * CT) {
-                const int pix = idx / (CPR * CT), cc = idx - pix * (CPR * CT);
-                *reinterpret_cast<uint4*>(sa + (cc / CPR) * SLICE + pix * ROWS + (cc % CPR) * 16) = va[u];
+            if (idx < 16 * CPR) {
+                const int pix = idx / CPR, cc = idx - pix * CPR;
+                *reinterpret_cast<uint4*>(sa + pix * ROWS + cc * 16) = va[u];
             }
         }
 #pragma unroll
@@ -2122,29 +1845,26 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
         }
         __syncthreads();
         if (ck + 1 < chunk_hi) gload(ck + 1);
-#pragma unroll
-        for (int s = 0; s < CT; ++s) WgFrag<T>::mma(sa + s * SLICE, sb, lane, acc[s]);
+        WgFrag<T>::mma(sa, sb, lane, acc);
     }
 
     if (!active) return;
     const int col_l = lane & 31, rsel = 4 * (lane >> 5);
 #pragma unroll
-    for (int s = 0; s < CT; ++s)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + s * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                    const int ci = ci0 + j * 32 + col_l;
-                    if (co < g.Cout && ci < g.Cin) {
-                        float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-                        if (use_atomic == 1) atomicAdd(p, acc[s][i][j][r]);
-                        else if (use_atomic == 2) *p = acc[s][i][j][r];       // first write of a cleared gradient
-                        else *p += acc[s][i][j][r];
-                    }
+            for (int r = 0; r < 16; ++r) {
+                const int co = co0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
+                const int ci = ci0 + j * 32 + col_l;
+                if (co < g.Cout && ci < g.Cin) {
+                    float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
+                    if (use_atomic == 1) atomicAdd(p, acc[i][j][r]);
+                    else if (use_atomic == 2) *p = acc[i][j][r];       // first write of a cleared gradient
+                    else *p += acc[i][j][r];
                 }
+            }
 }
 
 // ---------------------------------------------------------------------------
@@ -2362,42 +2082,35 @@ struct WgFragRow {
     }
 };
 
-// KR = 1: one kernel row per workgroup (its KW waves); KR = KH: ALL kernel rows (KH x KW waves, the segment of every row
-// staged side by side): the dy slice is then shared by all taps -- for layers whose dW is small enough that the extra
-// pixel splits (fewer workgroups per split) cost nothing: the generator's 3x3 convs (dW <= 0.3 MB).
-template <int KW, int XB, int KR = 1> struct WgRowCfg {         // XB: 8-row DMA blocks of one x segment
-    static constexpr int NW = KW * KR;
-    static constexpr int LPS = (4 + KR * XB + NW - 1) / NW;      // DMA instructions per wave per stage
-    static constexpr int STAGE = LPS * NW * 1024;
+// One kernel row per workgroup, one wave per tap column.  (All kernel rows per workgroup -- nine waves for a 3x3 conv,
+// the dy slice shared by the nine taps -- measured SLOWER almost everywhere: ResBlock 128 x 128 58.9 -> 71.4 us, 64 x 64
+// 29.5 -> 42.3, upsample4 54.5 -> 68.9; only the 256 px upBlock gained, 183.6 -> 156.8; removed.)
+template <int KW, int XB> struct WgRowCfg {         // XB: 8-row DMA blocks of one x segment
+    static constexpr int LPS = (4 + XB + KW - 1) / KW;           // DMA instructions per wave per stage
+    static constexpr int STAGE = LPS * KW * 1024;
 };
 
-template <int KW, int SX, int XB, int D, int KR = 1>
-__global__ __launch_bounds__(64 * KW * KR, KR == 1 ? 2 : 1) void wgrad_row_dma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+template <int KW, int SX, int XB, int D>
+__global__ __launch_bounds__(64 * KW, 2) void wgrad_row_dma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
                                                                 float* __restrict__ dw, const sba_conv_geom g, const int M,
                                                                 const int chunks_per_split, const int use_atomic,
                                                                 const FastDiv dsub, const FastDiv dow, const int64_t zstride,
                                                                 const int wclog) {
-    typedef WgRowCfg<KW, XB, KR> Cfg;
-    constexpr int LPS = Cfg::LPS, STAGE = Cfg::STAGE, NW = Cfg::NW;
+    constexpr int LPS = WgRowCfg<KW, XB>::LPS, STAGE = WgRowCfg<KW, XB>::STAGE;
     extern __shared__ __attribute__((aligned(1024))) unsigned char wg_lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int khl = wv / KW, kw = wv - khl * KW;            // this wave's kernel row inside the workgroup, its tap column
+    const int kw = wv;                                      // this wave's tap column
     const int co0 = blockIdx.x * 64;
     const int ci_tiles = g.Cin / 64;
-    const int kh0 = KR == 1 ? blockIdx.y / ci_tiles : 0;    // first kernel row of the workgroup
-    const int ci0 = (KR == 1 ? blockIdx.y - kh0 * ci_tiles : blockIdx.y) * 64;
-    const int kh = kh0 + khl;
+    const int kh = blockIdx.y / ci_tiles;                   // the workgroup's kernel row
+    const int ci0 = (blockIdx.y - kh * ci_tiles) * 64;
     const int tap = kh * KW + kw;
-    // taps are row-structured (checked by the host): row k starts at (ty, tx0) = (g.ty[k KW], g.tx[k KW])
-    auto row_ty = [&](const int k) { int v = 0;
-#pragma unroll
-        for (int t = 0; t < SBA_MAX_TAPS; ++t) if (t == k * KW) v = g.ty[t];
-        return v; };
-    int tx0 = 0;
+    // taps are row-structured (checked by the host): row kh starts at (ty0, tx0) = (g.ty[kh KW], g.tx[kh KW])
+    int ty0 = 0, tx0 = 0;
 #pragma unroll
     for (int t = 0; t < SBA_MAX_TAPS; ++t) {
-        if (t == kh * KW) tx0 = g.tx[t];
+        if (t == kh * KW) { ty0 = g.ty[t]; tx0 = g.tx[t]; }
     }
     const int ups = g.ups;            // (KW = 3, SX = 1 only) x is the LOW-resolution input of a nearest x2 upsample
     const int Wc = 1 << wclog, R = 32 >> wclog, XW = ups ? (Wc >> 1) + 2 : SX * (Wc - 1) + KW, XR = R * XW;
@@ -2424,17 +2137,16 @@ __global__ __launch_bounds__(64 * KW * KR, KR == 1 ? 2 : 1) void wgrad_row_dma_k
     int role[LPS], rr[LPS], rc[LPS], rn[LPS];
 #pragma unroll
     for (int i = 0; i < LPS; ++i) {
-        const int b = wv + NW * i;
+        const int b = wv + KW * i;
         role[i] = 2; rr[i] = 0; rc[i] = 0; rn[i] = 0;
         if (b < 4) { role[i] = 0; rr[i] = 8 * b + rsub; }
-        else {
-            const int sg = (b - 4) / XB;                                 // which kernel row's segment
-            const int L = WgFragRow<SX>::slot(8 * (b - 4 - sg * XB) + rsub);  // the segment row this LDS row holds
-            if (sg < KR && L < XR) {
+        else if (b < 4 + XB) {
+            const int L = WgFragRow<SX>::slot(8 * (b - 4) + rsub);      // the segment row this LDS row holds
+            if (L < XR) {
                 const int r = L / XW;
                 role[i] = 1;
                 rn[i] = r / rows_img;
-                rr[i] = (r - rn[i] * rows_img) * g.sy + row_ty(kh0 + sg); // (ups: an offset in UPSAMPLED rows)
+                rr[i] = (r - rn[i] * rows_img) * g.sy + ty0;           // (ups: an offset in UPSAMPLED rows)
                 rc[i] = ups ? L - r * XW : L - r * XW + tx0;            // (ups: the segment's low-resolution column index)
             }
         }
@@ -2455,7 +2167,7 @@ __global__ __launch_bounds__(64 * KW * KR, KR == 1 ? 2 : 1) void wgrad_row_dma_k
             uint32_t off = OOB;
             if (role[i] == 0) {
                 if (live) off = (uint32_t)(m0 + rr[i]) * d_pix + d_coff;
-                lds_dma16(dr, off, 0u, dst + (uint32_t)((wv + NW * i) * 1024));
+                lds_dma16(dr, off, 0u, dst + (uint32_t)((wv + KW * i) * 1024));
             } else {
                 int iy = iy0 + rr[i], ix = ix0 + rc[i];
                 if (ups) {              // upsampled row v -> low-resolution row v >> 1 (v = -1 and v = 2 IH are the padding)
@@ -2464,7 +2176,7 @@ __global__ __launch_bounds__(64 * KW * KR, KR == 1 ? 2 : 1) void wgrad_row_dma_k
                 }
                 const bool ok = live & (role[i] == 1) & (iy >= 0) & (iy < g.IH) & (ix >= 0) & (ix < g.IW);
                 if (ok) off = (uint32_t)(((n + rn[i]) * g.IH + iy) * g.IW + ix) * x_pix + x_coff;
-                lds_dma16(xr, off, 0u, dst + (uint32_t)((wv + NW * i) * 1024));
+                lds_dma16(xr, off, 0u, dst + (uint32_t)((wv + KW * i) * 1024));
             }
         }
         ++g_ck;
@@ -2489,7 +2201,7 @@ __global__ __launch_bounds__(64 * KW * KR, KR == 1 ? 2 : 1) void wgrad_row_dma_k
         issue(lds_base + (uint32_t)(islot * STAGE));
         if (++islot == D) islot = 0;
         const unsigned char* st = wg_lds + cslot * STAGE;
-        const unsigned char* xs = st + (4 + khl * XB) * 1024;
+        const unsigned char* xs = st + 4 * 1024;
 #pragma unroll
         for (int k16 = 0; k16 < 2; ++k16) {
             bf16x8_t a[2], b[2];
@@ -2953,25 +2665,25 @@ __global__ __launch_bounds__(256) void splitk_finish_group_kernel(const GroupArg
 struct IgemmCfg { int bm, bn, ks, occ; float eff; bool split; };
 // A: big square tile, B: wide-M tile for Cout = 64, C: mid tile, D: small tile (+split-K),
 // E: skinny GEMM tile for the 4x4 / 8x8 maps with thousands of channels (+split-K)
-// (The kernel also instantiates with KG > 1 in-workgroup K-groups and PF = 3 stages of loads in flight;
-// on the latency-bound small layers neither beat D -- 1 KB of LDS fragments per MFMA and one wave per
-// SIMD bound them, not the K loop -- so no shipped configuration uses them.  A 256x128 tile with 128x64
-// per-wave tiles (less LDS traffic per MFMA, but 4 waves and one workgroup per CU) lost to E everywhere.)
+// (In-workgroup K groups and three stages of loads in flight were measured on the latency-bound small layers and removed:
+// neither beat D -- 1 KB of LDS fragments per MFMA and one wave per SIMD bound them, not the K loop.  A 256x128 tile
+// with 128x64 per-wave tiles (less LDS traffic per MFMA, but 4 waves and one workgroup per CU) lost to E everywhere.)
 static const IgemmCfg kCfg[5] = {
     {128, 128, 1, 3, 1.00f, false}, {256, 64, 1, 3, 1.00f, false}, {128, 64, 2, 2, 0.80f, false},
     {64, 64, 2, 4, 0.50f, true},    {320, 128, 2, 1, 0.90f, true}};
+constexpr int IGEMM_SPLIT_MAX_M = 2048;     // split-K only pays on the GEMM-like maps: M up to this
 
-template <typename T, int BM, int BN, int WM, int WN, int KS, int KG = 1, int PF = 1>
+template <typename T, int BM, int BN, int WM, int WN, int KS>
 static void launch_cfg(const T* xp, const T* wp, T* yp, const T* ap, float* stats, const sba_conv_geom& g, int M,
                        int nslabs, int split, float* ws, hipStream_t st, const EpiX ex) {
-    constexpr int NT = (BM / WM) * (BN / WN) * 64 * KG;
+    constexpr int NT = (BM / WM) * (BN / WN) * 64;
     int sps = nslabs;
     if (split > 1) {
         sps = cdiv(cdiv(nslabs, split), KS) * KS;
         split = cdiv(nslabs, sps);
     }
     dim3 grid(cdiv(M, BM), cdiv(g.Cout, BN), split);
-    SBA_LAUNCH((igemm_kernel<T, BM, BN, WM, WN, KS, KG, PF>), grid, dim3(NT), 0, st, xp, wp, yp, ap, stats, g, M,
+    SBA_LAUNCH((igemm_kernel<T, BM, BN, WM, WN, KS>), grid, dim3(NT), 0, st, xp, wp, yp, ap, stats, g, M,
                        split > 1 ? ws : (float*)nullptr, sps, ex);
     if (split > 1) {
         dim3 fgrid(cdiv(g.Cout / 4, 256), cdiv(M, 8));
@@ -2979,31 +2691,15 @@ static void launch_cfg(const T* xp, const T* wp, T* yp, const T* ap, float* stat
     }
 }
 
-// SBA_SPLITK_FUSED=1: the last split to arrive finishes its tile inside the GEMM kernel (splitk_arrive); the tickets
-// live in the last SPLITK_TICKET_BYTES of the (zero-filled, left zero-filled) workspace.  Default 0 = separate
-// splitk_finish_kernel launch: the fused form passes the whole GPU suite but measured no gain on the step (14.96 vs
-// 14.78 ms, 75 finishing launches fewer): the last arrival's 16 KB device-scope reload + epilogue sits at the tail of
-// every tile, where the finishing launch spreads the same work over the whole chip.
-static int* splitk_tickets(float* ws, int64_t ws_bytes, int M, int Cout, int tiles) {
-    static int fused = -1;
-    if (fused < 0) { const char* e = getenv("SBA_SPLITK_FUSED"); fused = (e && e[0] == '1') ? 1 : 0; }
-    if (!fused || !ws || ws_bytes < 2 * SPLITK_TICKET_BYTES) return nullptr;
-    if ((int64_t)M * Cout * 4 > ws_bytes - SPLITK_TICKET_BYTES || tiles > SPLITK_TICKET_BYTES / 4) return nullptr;
-    return reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + ws_bytes - SPLITK_TICKET_BYTES);
-}
-
-// N-major tile numbering (see igemm_dma2_body) when the weights outweigh the input tensor.  SBA_IGEMM_NMAJOR=0 disables it.
+// N-major tile numbering (see igemm_dma2_body) when the weights outweigh the input tensor
 static int nmajor_for(const sba_conv_geom& g) {
-    static int en = -1;
-    if (en < 0) { const char* e = getenv("SBA_IGEMM_NMAJOR"); en = (e && e[0] == '0') ? 0 : 1; }
     const int64_t wb = (int64_t)g.Cout * g.ntaps * g.Cin, xb = (int64_t)g.N * g.IH * g.IW * g.Cin;
-    return (en && wb > xb) ? 1 : 0;
+    return wb > xb ? 1 : 0;
 }
 
 template <int BM, int BN, int WM, int WN, int KS, int D>
 static void launch_dma(const bf16_t* xp, const bf16_t* wp, bf16_t* yp, const bf16_t* ap, float* stats,
-                       const sba_conv_geom& g, int M, int nslabs, int split, float* ws, int64_t ws_bytes, hipStream_t st,
-                       const EpiX ex) {
+                       const sba_conv_geom& g, int M, int nslabs, int split, float* ws, hipStream_t st, const EpiX ex) {
     constexpr int NT = (BM / WM) * (BN / WN) * 64;
     int sps = nslabs;
     if (split > 1) {
@@ -3013,10 +2709,9 @@ static void launch_dma(const bf16_t* xp, const bf16_t* wp, bf16_t* yp, const bf1
     const int gx = cdiv(M, BM), gy = cdiv(g.Cout, BN);
     const int nmajor = nmajor_for(g);
     dim3 grid(nmajor ? 8 * cdiv(gy, 8) * gx : 8 * cdiv(gx, 8) * gy, 1, split);
-    int* tickets = splitk_tickets(ws, ws_bytes, M, g.Cout, (int)grid.x);
     SBA_LAUNCH((igemm_dma_kernel<BM, BN, WM, WN, KS, D>), grid, dim3(NT), 0, st, xp, wp, yp, ap, stats, g, M,
-               split > 1 ? ws : (float*)nullptr, split > 1 ? tickets : (int*)nullptr, sps, ex, gx, gy, nmajor DMA_TRACE_ARG);
-    if (split > 1 && !tickets) {
+               split > 1 ? ws : (float*)nullptr, sps, ex, gx, gy, nmajor DMA_TRACE_ARG);
+    if (split > 1) {
         dim3 fgrid(cdiv(g.Cout / 4, 256), cdiv(M, 8));
         SBA_LAUNCH((splitk_finish_kernel<bf16_t>), fgrid, dim3(256), 0, st, ws, yp, ap, stats, g, M, ex);
     }
@@ -3024,8 +2719,7 @@ static void launch_dma(const bf16_t* xp, const bf16_t* wp, bf16_t* yp, const bf1
 
 template <int BM, int BN, int WM, int WN, int D>
 static void launch_dma2(const bf16_t* xp, const bf16_t* wp, bf16_t* yp, const bf16_t* ap, float* stats,
-                        const sba_conv_geom& g, int M, int nslabs64, int split, float* ws, int64_t ws_bytes, hipStream_t st,
-                        const EpiX ex) {
+                        const sba_conv_geom& g, int M, int nslabs64, int split, float* ws, hipStream_t st, const EpiX ex) {
     constexpr int NT = (BM / WM) * (BN / WN) * 64;
     int sps = nslabs64;
     if (split > 1) {
@@ -3035,42 +2729,19 @@ static void launch_dma2(const bf16_t* xp, const bf16_t* wp, bf16_t* yp, const bf
     const int gx = cdiv(M, BM), gy = cdiv(g.Cout, BN);
     const int nmajor = nmajor_for(g);
     dim3 grid(nmajor ? 8 * cdiv(gy, 8) * gx : 8 * cdiv(gx, 8) * gy, 1, split);
-    int* tickets = splitk_tickets(ws, ws_bytes, M, g.Cout, (int)grid.x);
     SBA_LAUNCH((igemm_dma2_kernel<BM, BN, WM, WN, D>), grid, dim3(NT), 0, st, xp, wp, yp, ap, stats, g, M,
-               split > 1 ? ws : (float*)nullptr, split > 1 ? tickets : (int*)nullptr, sps, ex, gx, gy, nmajor DMA_TRACE_ARG);
-    if (split > 1 && !tickets) {
+               split > 1 ? ws : (float*)nullptr, sps, ex, gx, gy, nmajor DMA_TRACE_ARG);
+    if (split > 1) {
         dim3 fgrid(cdiv(g.Cout / 4, 256), cdiv(M, 8));
         SBA_LAUNCH((splitk_finish_kernel<bf16_t>), fgrid, dim3(256), 0, st, ws, yp, ap, stats, g, M, ex);
     }
 }
 
-// SBA_IGEMM_DMA: 1 (default) = LDS-DMA staged kernels for the bf16 tiles A-D, 0 = register-staged kernels
-static int dma_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("SBA_IGEMM_DMA"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v;
-}
-
-static int forced_cfg() {
-    static int v = -2;
-    if (v == -2) {
-        const char* e = getenv("SBA_IGEMM_CFG");       // tuning aid only: A..E
-        v = (e && e[0] >= 'A' && e[0] <= 'E') ? e[0] - 'A' : -1;
-    }
-    return v;
-}
-
 // ---- halo-tile 3x3 path: which geometries qualify, and its launch
 static bool halo_ok(const sba_conv_geom& g) {
-    static int enabled = -1;
-    if (enabled < 0) { const char* e = getenv("SBA_CONV_HALO"); enabled = (e && e[0] == '0') ? 0 : 1; }
-    if (!enabled) return false;
     if (g.ntaps != 9 || g.sy != 1 || g.sx != 1 || g.osy != 1 || g.osx != 1 || g.ooy || g.oox) return false;
     // Cin = 128 (data gradient of the ResBlocks' 64 -> 128 conv): the kernel walks the tile once per 64-channel chunk
-    static int halo128 = -1;
-    if (halo128 < 0) { const char* e = getenv("SBA_CONV_HALO128"); halo128 = (e && e[0] == '0') ? 0 : 1; }
-    const bool cin_ok = g.Cin == 64 || (g.Cin == 128 && halo128);
-    if (g.OHs != g.OH || g.OWs != g.OW || !cin_ok || g.Cout % 64) return false;
+    if (g.OHs != g.OH || g.OWs != g.OW || (g.Cin != 64 && g.Cin != 128) || g.Cout % 64) return false;
     if (g.OH % 8 || g.OW % 32) return false;
     if (g.ups ? (g.IH * 2 != g.OH || g.IW * 2 != g.OW) : (g.IH != g.OH || g.IW != g.OW)) return false;
     for (int t = 0; t < 9; ++t)
@@ -3114,24 +2785,12 @@ static void launch_halo3g(const sba_conv_geom& g, const bf16_t* x, const bf16_t*
 static void launch_halo(const sba_conv_geom& g, const bf16_t* x, const bf16_t* w, bf16_t* y, const bf16_t* addend,
                         float* stats, const EpiX ex, hipStream_t st) {
     const int tiles = g.N * (g.OH / 8) * (g.OW / 32);
-    // SBA_CONV_HALO2=1: the persistent variant (one workgroup per CU, weights resident, halo by LDS-DMA).  Measured
-    // SLOWER than the per-tile kernel at three workgroups per CU (G3 upBlock 151 vs 113 us, ResBlock 86 vs 80 us):
-    // with one wave per SIMD the epilogue of a tile overlaps nothing.  Kept as an experiment, off by default.
-    static int v2 = -1;
-    if (v2 < 0) { const char* e = getenv("SBA_CONV_HALO2"); v2 = (e && e[0] == '1') ? 1 : 0; }
-    const int nblocks = g.Cout / 64;
-    if (v2 && tiles >= 512 && g.Cin == 64) {
-        // persistent workgroups, one per CU, split evenly over the 64-channel blocks of Cout
-        int per = 256 / nblocks;
-        if (per > tiles) per = tiles;
-        dim3 grid(per * nblocks);
-        if (g.ups) SBA_LAUNCH((conv3x3_halo2_kernel<1>), grid, dim3(256), 0, st, x, w, y, addend, stats, g, ex, tiles, per);
-        else SBA_LAUNCH((conv3x3_halo2_kernel<0>), grid, dim3(256), 0, st, x, w, y, addend, stats, g, ex, tiles, per);
-        return;
-    }
+    // (A persistent variant -- one workgroup per CU, weights resident in LDS, the next tile's halo by LDS-DMA -- measured
+    // SLOWER than these per-tile kernels at three workgroups per CU: G3 upBlock 151 vs 113 us, ResBlock 86 vs 80 us; with
+    // one wave per SIMD the epilogue of a tile overlaps nothing.  Removed.)
     // BN = 64 for every Cout: the 128-wide variant needs 86 KB of LDS (one workgroup per CU) and
     // measured slower; re-staging the halo tile for the second channel block is cheap
-    dim3 grid(tiles, nblocks);
+    dim3 grid(tiles, g.Cout / 64);
     if (g.w_layout == 1) {      // fragment-major weights: the register-resident form (geom_ok has checked the layout's needs)
         if (g.ups) SBA_LAUNCH((conv3x3_halo3_kernel<64, 1>), grid, dim3(256), 0, st, x, w, y, addend, stats, g, ex);
         else SBA_LAUNCH((conv3x3_halo3_kernel<64, 0>), grid, dim3(256), 0, st, x, w, y, addend, stats, g, ex);
@@ -3184,14 +2843,11 @@ int launch_igemm(const void* x, const void* w, void* y, const void* addend, floa
     } else {
         best = 3;       // too few mid tiles to fill the chip: small tiles (+ split-K when K is long)
     }
-    if (forced_cfg() >= 0) best = forced_cfg();
     {
         const IgemmCfg& k = kCfg[best];
         const int tiles = cdiv(M, k.bm) * cdiv(g.Cout, k.bn);
         const int slots = 256 * k.occ;
-        static int split_m = -1;
-        if (split_m < 0) { const char* e = getenv("SBA_IGEMM_SPLIT_M"); split_m = e ? atoi(e) : 2048; }
-        if (k.split && can_split && tiles < slots && M <= split_m) {     // split-K only pays on the GEMM-like maps
+        if (k.split && can_split && tiles < slots && M <= IGEMM_SPLIT_MAX_M) {
             int split = slots / tiles;          // floor: one more split than fits leaves a nearly empty second round
             if (split > nslabs / 8) split = nslabs / 8;
             if (split > 32) split = 32;
@@ -3201,7 +2857,8 @@ int launch_igemm(const void* x, const void* w, void* y, const void* addend, floa
     const bool det = sba_det_on();      // deterministic mode: no split-K (its partial sums meet in f32 atomics)
     if (det) best_split = 1;
     float* ws = (float*)workspace;
-    if (sizeof(T) == 2 && dma_enabled()) {
+    if constexpr (sizeof(T) == 2) {
+        // bf16: the LDS-DMA staged kernels, and the register-staged 320x128 tile (configuration E) as tile 11
         const bf16_t* xb = (const bf16_t*)x; const bf16_t* wb = (const bf16_t*)w; bf16_t* yb = (bf16_t*)y;
         const bf16_t* ab = (const bf16_t*)addend;
         // tile ids (include/sbagan_hip.h: sba_conv_geom.tile): BM x BN, slabs per stage, ring depth
@@ -3213,10 +2870,10 @@ int launch_igemm(const void* x, const void* w, void* y, const void* addend, floa
         //   against 320..640 rows) move 1/3..1/5 of the L2->LDS bytes of the 64- / 96-row tiles; Cin % 64 == 0 only
         // the deep rings keep ~100 KB of loads in flight per CU: an L2-hit load takes ~1 us under load, so a
         // workgroup alone on its CU moves bytes_in_flight / 1 us (measured 36-42 GB/s with 48 KB in flight)
+        static const int rule_tile[4] = {7, 9, 5, 1};
         int tile = g.tile;
         int split = best_split;
         if (tile <= 0 || tile > SBA_IGEMM_TILES) {
-            static const int rule_tile[4] = {7, 9, 5, 1};
             tile = best <= 3 ? rule_tile[best] : 11;
         } else if (g.ksplit >= 1) {
             split = g.ksplit;
@@ -3224,64 +2881,66 @@ int launch_igemm(const void* x, const void* w, void* y, const void* addend, floa
             if (split > nslabs / 2) split = nslabs / 2 > 0 ? nslabs / 2 : 1;
         }
         if (det) split = 1;
-        static int gen2 = -1;       // SBA_IGEMM_DMA2=0: first-generation kernels only (A/B aid)
-        if (gen2 < 0) { const char* e = getenv("SBA_IGEMM_DMA2"); gen2 = (e && e[0] == '0') ? 0 : 1; }
-        if (tile >= 13 && tile != 12 && !(gen2 && g.Cin % 64 == 0)) {       // gen-2 only: back to the rules
-            static const int rule_tile[4] = {7, 9, 5, 1};
+        if (tile >= 13 && g.Cin % 64 != 0) {       // gen-2 only: back to the rules
             tile = best <= 3 ? rule_tile[best] : 11;
             split = det ? 1 : best_split;
         }
-        if (gen2 && g.Cin % 64 == 0 && tile != 11) {
+        if (g.Cin % 64 == 0 && tile != 11) {
             // 128-byte rows, fragment double buffering, DMA issue between the MFMAs (igemm_dma2_kernel)
             const int ns64 = nslabs / 2;
             int sp = split;
             if (sp > ns64 / 2) sp = ns64 / 2 > 0 ? ns64 / 2 : 1;
             if (plan) { plan[0] = 1; plan[1] = tile; plan[2] = sp; return SBA_OK; }
             switch (tile) {
-                case 1: launch_dma2<64, 64, 32, 32, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 2: launch_dma2<64, 64, 32, 32, 8>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 3: launch_dma2<96, 64, 32, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 4: launch_dma2<96, 64, 32, 64, 6>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 5: launch_dma2<128, 64, 32, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 6: launch_dma2<128, 64, 32, 64, 6>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 7: launch_dma2<128, 128, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 8: launch_dma2<128, 128, 64, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 9: launch_dma2<256, 64, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 10: launch_dma2<256, 64, 64, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 13: launch_dma2<320, 64, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 14: launch_dma2<160, 64, 32, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 15: launch_dma2<160, 64, 32, 64, 2>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 16: launch_dma2<256, 128, 128, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 17: launch_dma2<256, 128, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                case 18: launch_dma2<256, 128, 128, 64, 2>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-                default: launch_dma2<96, 128, 32, 128, 5>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
+                case 1: launch_dma2<64, 64, 32, 32, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 2: launch_dma2<64, 64, 32, 32, 8>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 3: launch_dma2<96, 64, 32, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 4: launch_dma2<96, 64, 32, 64, 6>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 5: launch_dma2<128, 64, 32, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 6: launch_dma2<128, 64, 32, 64, 6>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 7: launch_dma2<128, 128, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 8: launch_dma2<128, 128, 64, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 9: launch_dma2<256, 64, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 10: launch_dma2<256, 64, 64, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 13: launch_dma2<320, 64, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 14: launch_dma2<160, 64, 32, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 15: launch_dma2<160, 64, 32, 64, 2>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 16: launch_dma2<256, 128, 128, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 17: launch_dma2<256, 128, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                case 18: launch_dma2<256, 128, 128, 64, 2>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
+                default: launch_dma2<96, 128, 32, 128, 5>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
             }
         }
         if (plan && tile != 11) { plan[0] = 2; plan[1] = tile; plan[2] = split; return SBA_OK; }
         switch (tile) {
-            case 1: launch_dma<64, 64, 32, 32, 2, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 2: launch_dma<64, 64, 32, 32, 2, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 3: launch_dma<96, 64, 32, 64, 2, 3>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 4: launch_dma<96, 64, 32, 64, 2, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 5: launch_dma<128, 64, 32, 64, 1, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 6: launch_dma<128, 64, 32, 64, 2, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 7: launch_dma<128, 128, 64, 64, 1, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 8: launch_dma<128, 128, 64, 64, 1, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 9: launch_dma<256, 64, 64, 64, 1, 3>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 10: launch_dma<256, 64, 64, 64, 1, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            case 12: launch_dma<96, 128, 32, 128, 1, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, ws_bytes, st, ex); return SBA_CHECK_LAUNCH();
-            default: best = 4; best_split = split; break;      // 11: the register-staged 320x128 tile below
+            case 1: launch_dma<64, 64, 32, 32, 2, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 2: launch_dma<64, 64, 32, 32, 2, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 3: launch_dma<96, 64, 32, 64, 2, 3>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 4: launch_dma<96, 64, 32, 64, 2, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 5: launch_dma<128, 64, 32, 64, 1, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 6: launch_dma<128, 64, 32, 64, 2, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 7: launch_dma<128, 128, 64, 64, 1, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 8: launch_dma<128, 128, 64, 64, 1, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 9: launch_dma<256, 64, 64, 64, 1, 3>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 10: launch_dma<256, 64, 64, 64, 1, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            case 12: launch_dma<96, 128, 32, 128, 1, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
+            default: break;
         }
+        // tile 11: the register-staged 320x128 tile (configuration E)
+        if (plan) { plan[0] = 3; plan[1] = 4; plan[2] = split; return SBA_OK; }
+        launch_cfg<T, 320, 128, 64, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, split, ws, st, ex);
+        return SBA_CHECK_LAUNCH();
+    } else {
+        if (plan) { plan[0] = 3; plan[1] = best; plan[2] = best_split; return SBA_OK; }
+        switch (best) {
+            case 0: launch_cfg<T, 128, 128, 64, 64, 1>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
+            case 1: launch_cfg<T, 256, 64, 64, 64, 1>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
+            case 2: launch_cfg<T, 128, 64, 32, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
+            case 3: launch_cfg<T, 64, 64, 32, 32, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
+            default: launch_cfg<T, 320, 128, 64, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
+        }
+        return SBA_CHECK_LAUNCH();
     }
-    if (plan) { plan[0] = 3; plan[1] = best; plan[2] = best_split; return SBA_OK; }
-    switch (best) {
-        case 0: launch_cfg<T, 128, 128, 64, 64, 1>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-        case 1: launch_cfg<T, 256, 64, 64, 64, 1>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-        case 2: launch_cfg<T, 128, 64, 32, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-        case 3: launch_cfg<T, 64, 64, 32, 32, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-        default: launch_cfg<T, 320, 128, 64, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-    }
-    return SBA_CHECK_LAUNCH();
 }
 
 bool geom_ok(const sba_conv_geom* g, int dtype) {
@@ -3482,35 +3141,19 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
     };
     auto det_end = [&](int nsplit) { if (part) sba_det_fold(part, 1, nsplit, dwn, dw, 0, fw == 2 ? 1 : 0, st); };
     // Kernel-row decomposition (wgrad_row_dma_kernel): the kw taps of a kernel row share one staged input row segment.
-    // 4x4 / stride-2 down blocks and 3x3 / stride-1 convs on maps of 8 x 8 .. (below the all-taps halo-row kernel's range).
-    // SBA_WGRAD_S2=0 / SBA_WGRAD_S1=0: off (A/B aids); SBA_WGRAD_S1=1: only below the halo-row kernel's range; 2: also instead
-    // of it; 3 (default): also behind the nearest x2 upsample (G upsample1..4 73 / 92 / 102 / 80 -> 41 / 56 / 55 / 53 us,
-    // upBlock -> 128 px 123 -> 100, -> 256 px 192 -> 187) -- tools/bench_wgrad.py, B = 20: ResBlock 64 x 64 44.0 -> 28.4 us, 64->128 @64 61.6 -> 38.3; at 128 x 128
+    // 4x4 / stride-2 down blocks, and 3x3 / stride-1 convs on maps of 8 x 8 .. -- also in the all-taps halo-row kernel's
+    // range and behind the nearest x2 upsample (G upsample1..4 73 / 92 / 102 / 80 -> 41 / 56 / 55 / 53 us, upBlock -> 128 px
+    // 123 -> 100, -> 256 px 192 -> 187) -- tools/bench_wgrad.py, B = 20: ResBlock 64 x 64 44.0 -> 28.4 us, 64->128 @64 61.6 -> 38.3; at 128 x 128
     // against wgrad_rows_kernel: 64->64 95.8 -> 54.9 us, 64->128 122.8 -> 92.8 (profiles/r04_wgrad_s2_rows.txt).
+    // The 4 x 4 maps (two images per chunk) included -- B = 40: D256's 3x3 2048->1024 78.6 -> 55.8 us, D128's 1024->512
+    // 38.1 -> 27.3, 512->1024 4x4/s2 35.8 -> 27.9.
     {
-        static int s2 = -1, s1 = -1, row_wgs = -1, rows_m1 = -1;
-        if (s2 < 0) { const char* e = getenv("SBA_WGRAD_S2"); s2 = e ? atoi(e) : 1; }
-        if (s1 < 0) { const char* e = getenv("SBA_WGRAD_S1"); s1 = e ? atoi(e) : 3; }
-        if (row_wgs < 0) { const char* e = getenv("SBA_WGRAD_S2_WGS"); row_wgs = e ? atoi(e) : 512; }
-        if (rows_m1 < 0) { const char* e = getenv("SBA_WGRAD_ROWS_M"); rows_m1 = e ? atoi(e) : 131072; }
         const int kwn = g->ntaps == 16 ? 4 : (g->ntaps == 9 ? 3 : 0), sxy = g->sx;
-        bool ok = dtype == SBA_BF16 && kwn && g->sy == sxy && (!g->ups || (kwn == 3 && s1 >= 3)) && g->osy == 1 && g->osx == 1 && g->ooy == 0 &&
+        bool ok = dtype == SBA_BF16 && kwn && g->sy == sxy && (!g->ups || kwn == 3) && g->osy == 1 && g->osx == 1 && g->ooy == 0 &&
                   g->oox == 0 && g->OHs == g->OH && g->OWs == g->OW && g->Cin % 64 == 0 && g->Cout % 64 == 0 &&
                   g->OW >= 4 && (g->OW & (g->OW - 1)) == 0 && !(g->OW == 4 && (g->ups || g->OH != 4)) && M % 32 == 0 &&
                   ((g->OH * g->OW) % 32 == 0 || g->OW == 4);
-        ok = ok && ((kwn == 4 && sxy == 2 && s2) ||
-                    (kwn == 3 && sxy == 1 && s1 && (s1 >= 2 || M < rows_m1 || g->OW % 64 != 0)));
-        // SBA_WGRAD_ALLROWS=1 (experiment, off): all three kernel rows of a small-dW 3x3 conv per workgroup (KR = 3: nine waves,
-        // dy shared by nine taps, 1.2 instead of 3 KB staged per tap).  Measured SLOWER almost everywhere (one workgroup of
-        // nine waves per CU behind one barrier per stage): ResBlock 128 x 128 58.9 -> 71.4 us, 64 x 64 29.5 -> 42.3, upsample4
-        // 54.5 -> 68.9 at 256 workgroups (worse at 320 / 512); only the 256 px upBlock gains (183.6 -> 156.8).
-        static int allrows = -1, all9_wgs = -1;
-        if (allrows < 0) { const char* e = getenv("SBA_WGRAD_ALLROWS"); allrows = e ? atoi(e) : 0; }
-        if (all9_wgs < 0) { const char* e = getenv("SBA_WGRAD_ALL9_WGS"); all9_wgs = e ? atoi(e) : 256; }
-        static int ow4 = -1;        // SBA_WGRAD_ROW_OW4=0: not on the 4 x 4 maps (two images per chunk; A/B aid).  B = 40: D256's 3x3
-                                    // 2048->1024 78.6 -> 55.8 us, D128's 1024->512 38.1 -> 27.3, 512->1024 4x4/s2 35.8 -> 27.9
-        if (ow4 < 0) { const char* e = getenv("SBA_WGRAD_ROW_OW4"); ow4 = e ? atoi(e) : 1; }
-        ok = ok && (g->OW > 4 || ow4);
+        ok = ok && ((kwn == 4 && sxy == 2) || (kwn == 3 && sxy == 1));
         for (int t = 0; t < g->ntaps && ok; ++t)
             ok = g->ty[t] == g->ty[(t / kwn) * kwn] && g->tx[t] == g->tx[(t / kwn) * kwn] + (t % kwn);
         const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
@@ -3518,20 +3161,18 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
             const int wc = g->OW < 32 ? g->OW : 32;
             int wclog = 0;
             while ((1 << wclog) < wc) ++wclog;
-            // all three kernel rows of a 3x3 conv in one workgroup (nine waves, the dy slice shared by the nine taps) where dW
-            // is small: with 1..4 workgroups per pixel split the extra splits' f32 atomics cost nothing
-            const bool all9 = allrows && kwn == 3 && g->OW >= 8 && co_tiles * (g->Cin / 64) <= 4;
-            const int wgs = all9 ? co_tiles * (g->Cin / 64) : co_tiles * kwn * (g->Cin / 64);
+            const int wgs = co_tiles * kwn * (g->Cin / 64);
             const int tc32 = M / 32;
             // pixel splits: each one adds a full f32-atomic copy of dW (~1.3 TB/s chip-wide): fill the chip about twice,
             // keep >= 12 chunks behind a copy
             // (tools/bench_wgrad.py, B = 40: 128->256 @64 71 us at 512 workgroups, 78 at 384, 94 at 256; the 64->128 layers,
-            // 8 workgroups per split: @128 89 / 86 / 94, @64 42 / 37 / 36; all9: one workgroup per CU)
-            int sp = cdiv(all9 ? all9_wgs : (wgs <= 8 ? (row_wgs * 3) / 4 : row_wgs), wgs);
+            // 8 workgroups per split: @128 89 / 86 / 94, @64 42 / 37 / 36)
+            constexpr int ROW_WGS = 512;
+            int sp = cdiv(wgs <= 8 ? (ROW_WGS * 3) / 4 : ROW_WGS, wgs);
             if (sp > tc32 / 12) sp = tc32 / 12 > 0 ? tc32 / 12 : 1;
             const int cps32 = cdiv(tc32, sp);
             sp = cdiv(tc32, cps32);
-            dim3 gd(co_tiles, (all9 ? 1 : kwn) * (g->Cin / 64), sp);
+            dim3 gd(co_tiles, kwn * (g->Cin / 64), sp);
             if (gd.y <= 65535 && gd.z <= 65535) {
                 if (!det_begin(sp)) return SBA_E_ARG;
                 float* dwa = part ? part : dw;
@@ -3550,12 +3191,6 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
                     if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<3, 1, 6, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
                     SBA_LAUNCH((wgrad_row_dma_kernel<3, 1, 6, 4>), gd, dim3(192), LDS, (hipStream_t)stream, (const bf16_t*)x,
                                (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
-                } else if (all9) {
-                    constexpr int LDS = 3 * WgRowCfg<3, 5, 3>::STAGE;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<3, 1, 5, 3, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_row_dma_kernel<3, 1, 5, 3, 3>), gd, dim3(576), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
                 } else {                       // <= 40 rows
                     constexpr int LDS = 4 * WgRowCfg<3, 5>::STAGE;
                     static bool once = false;
@@ -3568,49 +3203,30 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
             }
         }
     }
-    static int small_m = -1;
-    if (small_m < 0) { const char* e = getenv("SBA_WGRAD_SMALL_M"); small_m = e ? atoi(e) : 12000; }
-    if (M <= small_m && co_tiles * items >= 256) {
+    constexpr int SMALL_M = 12000;      // small-pixel-count decomposition: output pixels up to this
+    if (M <= SMALL_M && co_tiles * items >= 256) {
         // GEMM-like layer: one tile per wave, all pixels (ksplit re-derived for this decomposition)
         const int total_chunks = cdiv(M, 16);
         const int wgs = co_tiles * cdiv(items, 4);
         // pixel splits: each one adds a full f32-atomic copy of every 64x64 tile (the atomics run at ~1.3 TB/s),
         // so split only up to ~3 workgroups per CU and keep >= 24 chunks (384 pixels) of MFMA work behind a copy
         // (measured on the discriminator shapes: joint conv 68 -> 44 us, s64_2 68 -> 46, c4 166 -> 133)
-        static int tgt = -1, minc = -1;
-        if (tgt < 0) { const char* e = getenv("SBA_WGRAD_SMALL_WGS"); tgt = e ? atoi(e) : 768; }
-        if (minc < 0) { const char* e = getenv("SBA_WGRAD_SMALL_MINC"); minc = e ? atoi(e) : 24; }
-        int split = wgs >= tgt / 2 ? 1 : cdiv(tgt, wgs);
-        if (split > total_chunks / minc) split = total_chunks / minc > 0 ? total_chunks / minc : 1;
+        constexpr int SMALL_WGS = 768, SMALL_MINC = 24;
+        int split = wgs >= SMALL_WGS / 2 ? 1 : cdiv(SMALL_WGS, wgs);
+        if (split > total_chunks / SMALL_MINC) split = total_chunks / SMALL_MINC > 0 ? total_chunks / SMALL_MINC : 1;
         const int cps = cdiv(total_chunks, split);
         split = cdiv(total_chunks, cps);
         dim3 grid(co_tiles, cdiv(items, 4), split);
         if (grid.y > 65535 || grid.z > 65535) return SBA_E_ARG;
-        static int ct2 = -1;        // SBA_WGRAD_SMALL_CT2: minimum workgroups for the 128-wide variant (0 = never,
-                                    // the default: measured 20-35 % SLOWER than CT = 1 at 4 waves per SIMD)
-        if (ct2 < 0) { const char* e = getenv("SBA_WGRAD_SMALL_CT2"); ct2 = e ? atoi(e) : 0; }
-        if (ct2 > 0 && split == 1 && g->Cout % 128 == 0 && (co_tiles / 2) * (int)grid.y >= ct2) {
-            grid.x = co_tiles / 2;
-            SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_small_kernel<T, 2>), grid, dim3(256), 0, (hipStream_t)stream,
-                                                   (const T*)x, (const T*)dy, dw, *g, M, cps, fw, dsub, dow, (int64_t)0));
-            return SBA_CHECK_LAUNCH();
-        }
-        static int dma = -1;        // SBA_WGRAD_DMA: 0 = register-staged kernel; D = ring depth of the LDS-DMA kernel
-        if (dma < 0) { const char* e = getenv("SBA_WGRAD_DMA"); dma = e ? atoi(e) : 4; }
         const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
-        // measured (tools/bench_wgrad.py, B = 20): 15-25 % faster than the register-staged kernel up to ~512
+        // LDS-DMA ring of depth 4 (tools/bench_wgrad.py, B = 20): 15-25 % faster than the register-staged kernel up to ~512
         // workgroups (joint conv 29 -> 25 us, D s32 61 -> 50, s32_1 49 -> 37); beyond that the launches are bound by
         // the L2 traffic of the operand slices either way and the 80 KB ring costs occupancy (s64 145 -> 175 us)
-        static int dma_wgs = -1;
-        if (dma_wgs < 0) { const char* e = getenv("SBA_WGRAD_DMA_WGS"); dma_wgs = e ? atoi(e) : 512; }
-        // beyond dma_wgs: the DMA kernel with TWO co tiles per wave (0.375 KB of operands per MFMA) -- pays once the
+        constexpr int DMA_WGS = 512;
+        // beyond DMA_WGS: the DMA kernel with TWO co tiles per wave (0.375 KB of operands per MFMA) -- pays once the
         // epilogue is a plain store (first write: D256 s64 119 -> 95 us, s64_1 89 -> 79, G upsample1 84 -> 72); with the
         // read-modify-write epilogue it is no faster than the register-staged kernel (148 vs 146 us).
-        // SBA_WGRAD_DMA_CT2: 1 = always, 0 = never, unset = on first writes.
-        static int dma_ct2 = -2;
-        if (dma_ct2 == -2) { const char* e = getenv("SBA_WGRAD_DMA_CT2"); dma_ct2 = e ? atoi(e) : -1; }
-        if (dma > 0 && (dma_ct2 > 0 || (dma_ct2 < 0 && fw == 2)) && wgs > dma_wgs && g->Cout % 128 == 0 &&
-            dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
+        if (fw == 2 && wgs > DMA_WGS && g->Cout % 128 == 0 && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
             const int tc32 = cdiv(M, 32);
             dim3 gd(co_tiles / 2, cdiv(items, 4), 1);
             constexpr int LDS = 3 * 6 * 32 * 128;
@@ -3620,11 +3236,11 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
                        (const bf16_t*)dy, dw, *g, M, tc32, fw, dsub, dow, (int64_t)0);
             return SBA_CHECK_LAUNCH();
         }
-        if (dma > 0 && wgs <= dma_wgs && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
+        if (wgs <= DMA_WGS && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
             // stages of 32 pixels; the same split rule restated in 32-pixel chunks
             const int tc32 = cdiv(M, 32);
-            int sp = wgs >= tgt / 2 ? 1 : cdiv(tgt, wgs);
-            const int mc = minc / 2 > 0 ? minc / 2 : 1;
+            int sp = wgs >= SMALL_WGS / 2 ? 1 : cdiv(SMALL_WGS, wgs);
+            constexpr int mc = SMALL_MINC / 2;
             if (sp > tc32 / mc) sp = tc32 / mc > 0 ? tc32 / mc : 1;
             const int cps32 = cdiv(tc32, sp);
             sp = cdiv(tc32, cps32);
@@ -3634,24 +3250,16 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
             float* dwa = part ? part : dw;
             const int md = part ? 2 : (sp > 1 ? 1 : fw);
             const int64_t zs = part ? dwn : 0;
-            if (dma == 3) {
-                constexpr int LDS = 3 * 5 * 32 * 128;
-                static bool once = false;
-                if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                SBA_LAUNCH((wgrad_small_dma_kernel<1, 3>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-            } else {
-                constexpr int LDS = 4 * 5 * 32 * 128;
-                static bool once = false;
-                if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-            }
+            constexpr int LDS = 4 * 5 * 32 * 128;
+            static bool once = false;
+            if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
+            SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
+                       (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
             det_end(sp);
             return SBA_CHECK_LAUNCH();
         }
         if (!det_begin(split)) return SBA_E_ARG;
-        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_small_kernel<T, 1>), grid, dim3(256), 0, (hipStream_t)stream,
+        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_small_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream,
                                                (const T*)x, (const T*)dy, part ? part : dw, *g, M, cps,
                                                part ? 2 : (split > 1 ? 1 : fw), dsub, dow, part ? dwn : (int64_t)0));
         det_end(split);
@@ -3660,14 +3268,11 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
     // generator-style 3x3 stride-1 conv on a wide map: all nine taps per workgroup from halo tiles.  From 128x128 maps
     // up (B = 20: M >= 327 k) it beats the LDS-DMA decomposition below (upBlock -> 256 px 189 vs 349 us); at 64x64
     // (M = 82 k) the DMA kernel wins (ResBlock 51 -> 40 us, 64->128: 69 -> 60), tools/bench_wgrad.py.
-    static int rows_m = -1;
-    if (rows_m < 0) { const char* e = getenv("SBA_WGRAD_ROWS_M"); rows_m = e ? atoi(e) : 131072; }
+    constexpr int ROWS_M = 131072;
     bool rows_ok = g->ntaps == 9 && g->sy == 1 && g->sx == 1 && g->osy == 1 && g->osx == 1 && g->ooy == 0 &&
-                   g->oox == 0 && g->OHs == g->OH && g->OWs == g->OW && g->OW % 64 == 0 && M >= rows_m;
+                   g->oox == 0 && g->OHs == g->OH && g->OWs == g->OW && g->OW % 64 == 0 && M >= ROWS_M;
     for (int t = 0; t < 9 && rows_ok; ++t) rows_ok = g->ty[t] == t / 3 - 1 && g->tx[t] == t % 3 - 1;
-    static int rows_en = -1;        // SBA_WGRAD_ROWS=0: skip the all-taps halo-row kernel (A/B aid)
-    if (rows_en < 0) { const char* e = getenv("SBA_WGRAD_ROWS"); rows_en = (e && e[0] == '0') ? 0 : 1; }
-    if (rows_ok && rows_en) {
+    if (rows_ok) {
         const int total_segs = g->N * g->OH * (g->OW / 64);
         const int ci_t = cdiv(g->Cin, 64);
         // every pixel split adds a full copy of the tile's 9 x 64 x 64 outputs to the f32 atomics
@@ -3692,42 +3297,29 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
         // Big-M layers that are not 3x3 / OW % 64 == 0 (the discriminators' 4x4/s2 down blocks at 32..128 px): the
         // register-staged kernel below shares nothing between its waves (1 KB of operands per MFMA from L2 = the
         // 300 TFLOP/s on-chip-bandwidth roofline of a 64x64 tile); the small-pixel-count decomposition shares the dy
-        // slices between the four (tap, ci tile) items of a workgroup (0.625 KB, CT = 2: 0.375 KB per MFMA) and walks
-        // its pixel split through the LDS-DMA ring.  Measured (tools/bench_wgrad.py, B = 20): D256 down 64->128 @128 px
-        // 200 -> 110 us, 128->256 @64 193 -> 107, D128 down @64 99 -> 48, D64 down @32 43 -> 24; CT = 2 is no better.
-        // SBA_WGRAD_GEN_DMA: 0 = off, 1 = CT 1 (default), 2 = CT 2 where Cout % 128 == 0.
-        static int gen = -1, gen_wgs = -1;
-        if (gen < 0) { const char* e = getenv("SBA_WGRAD_GEN_DMA"); gen = e ? atoi(e) : 1; }
-        if (gen_wgs < 0) { const char* e = getenv("SBA_WGRAD_GEN_WGS"); gen_wgs = e ? atoi(e) : 512; }
+        // slices between the four (tap, ci tile) items of a workgroup (0.625 KB per MFMA) and walks its pixel split
+        // through the LDS-DMA ring.  Measured (tools/bench_wgrad.py, B = 20): D256 down 64->128 @128 px 200 -> 110 us,
+        // 128->256 @64 193 -> 107, D128 down @64 99 -> 48, D64 down @32 43 -> 24; two co tiles per wave are no better.
         const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
-        if (gen > 0 && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
-            const bool ct2 = gen >= 2 && g->Cout % 128 == 0;
-            const int cot = ct2 ? co_tiles / 2 : co_tiles;
-            const int wgs = cot * cdiv(items, 4);
+        if (dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
+            constexpr int GEN_WGS = 512;
+            const int wgs = co_tiles * cdiv(items, 4);
             const int tc32 = cdiv(M, 32);
-            int sp = cdiv(gen_wgs, wgs);
+            int sp = cdiv(GEN_WGS, wgs);
             if (sp > tc32 / 12) sp = tc32 / 12 > 0 ? tc32 / 12 : 1;
             const int cps32 = cdiv(tc32, sp);
             sp = cdiv(tc32, cps32);
-            dim3 gd(cot, cdiv(items, 4), sp);
+            dim3 gd(co_tiles, cdiv(items, 4), sp);
             if (gd.y <= 65535 && gd.z <= 65535) {
                 if (!det_begin(sp)) return SBA_E_ARG;
                 float* dwa = part ? part : dw;
                 const int md = part ? 2 : (sp > 1 ? 1 : fw);
                 const int64_t zs = part ? dwn : 0;
-                if (ct2) {
-                    constexpr int LDS = 3 * 6 * 32 * 128;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_small_dma_kernel<2, 3>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-                } else {
-                    constexpr int LDS = 4 * 5 * 32 * 128;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-                }
+                constexpr int LDS = 4 * 5 * 32 * 128;
+                static bool once = false;
+                if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
+                SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
+                           (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
                 det_end(sp);
                 return SBA_CHECK_LAUNCH();
             }

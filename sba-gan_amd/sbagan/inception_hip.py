@@ -220,7 +220,7 @@ class InceptionHIP(object):
         """the fragment-major copy of the packed weights `w` ([R][9][K], frozen) when this launch goes to the register-weight
         halo-tile kernel (include/sbagan_hip.h: sba_conv_geom.w_layout): stride-1 3 x 3 convs on the big maps of the trunk's
         first layers (>= 64 pixels wide) and their data gradients; None otherwise"""
-        if not (ops.FRAG_WEIGHTS and FRAG_STEM) or self.dtype != torch.bfloat16 or g.ntaps != 9 or g.sy != 1 or \
+        if not FRAG_STEM or self.dtype != torch.bfloat16 or g.ntaps != 9 or g.sy != 1 or \
                 g.osy != 1 or g.OW < 64 or g.OWs != g.OW or w.dim() != 3 or w.shape[0] % 32 or w.shape[2] % 32:
             return None
         key = (w.data_ptr(), g.OH, g.OW, g.IH, g.IW, g.N)

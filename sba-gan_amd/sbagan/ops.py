@@ -220,7 +220,7 @@ class PackedWeight(object):
         """the forward operand FRAGMENT-MAJOR (include/sbagan_hip.h: sba_pack_frag_multi), or None when the layer does not
         qualify (bf16, Cin 64 / 128, Cout % 64 == 0, 3 x 3)"""
         O, I, KH, KW = self.param.shape
-        if not FRAG_WEIGHTS or dtype != torch.bfloat16 or KH != 3 or KW != 3 or I not in (64, 128) or O % 64:
+        if dtype != torch.bfloat16 or KH != 3 or KW != 3 or I not in (64, 128) or O % 64:
             return None
         src = self.fwd(dtype)                   # (refreshes the group, frag copies included, when stale)
         k = self._key(dtype)
@@ -234,7 +234,7 @@ class PackedWeight(object):
     def dgrad_frag(self, dtype, kind):
         """the data-gradient operand of a stride-1 3 x 3 conv ([Cin][flipped tap][Cout]) fragment-major, or None"""
         O, I, KH, KW = self.param.shape
-        if not FRAG_WEIGHTS or dtype != torch.bfloat16 or kind != '3x3' or O not in (64, 128) or I % 64:
+        if dtype != torch.bfloat16 or kind != '3x3' or O not in (64, 128) or I % 64:
             return None
         src = self.dgrad(dtype, kind)
         k = self._key(dtype) + (kind,)
@@ -263,7 +263,6 @@ class PackedWeight(object):
         return self._dgrad
 
 
-FRAG_WEIGHTS = os.environ.get('SBA_FRAG_WEIGHTS', '1') != '0'
 _FRAG_DESC = [('src', '<u8'), ('dst', '<u8'), ('R', '<i4'), ('taps', '<i4'), ('K', '<i4'), ('unit_begin', '<i4')]
 
 
@@ -343,7 +342,7 @@ class PackGroup(object):
         st['tiles'] = tiles
         # fragment-major copies of the 3 x 3 layers the halo-tile kernel serves (ONE more launch per refresh)
         st['frag'] = None
-        if FRAG_WEIGHTS and dtype == torch.bfloat16:
+        if dtype == torch.bfloat16:
             items = []
             for pw, kind in self.layers:
                 O, I, KH, KW = pw.param.shape
@@ -602,8 +601,8 @@ def conv_dgrad(dy, pw, kind, in_hw, addend=None):
     raise ValueError(kind)
 
 
-DGRAD4_GROUP = os.environ.get('SBA_DGRAD4_GROUP', '1') != '0'
-_DGRAD4_FORCE = os.environ.get('SBA_DGRAD4_PLAN')          # tuning aid: "tile,split"
+DGRAD4_GROUP = True         # False: four single launches (the reference of tests/test_kernels_gpu.py, tools/tune_dgrad4.py)
+_DGRAD4_FORCE = None        # "tile,split": forces the grouped launch's plan (tests and tools/tune_dgrad4.py)
 
 
 def dgrad4_plan(g):
@@ -627,8 +626,8 @@ def dgrad4_plan(g):
     return tile, split
 
 
-_KSPLIT_TARGET = int(os.environ.get('SBA_WGRAD_WGS', '640'))
-_KSPLIT_MIN_CHUNKS = int(os.environ.get('SBA_WGRAD_MIN_CHUNKS', '24'))
+_KSPLIT_TARGET = 640
+_KSPLIT_MIN_CHUNKS = 24
 
 
 def _ksplit(tiles, M):
@@ -637,9 +636,6 @@ def _ksplit(tiles, M):
     # ... but every split adds a full copy of the tile's outputs to the f32 atomics: keep >= 24 pixel
     # chunks (1536 pixels) of MFMA work per workgroup behind each copy
     return max(1, min(want, chunks // _KSPLIT_MIN_CHUNKS if chunks >= 2 * _KSPLIT_MIN_CHUNKS else 1))
-
-
-FIRST_WRITE = os.environ.get('SBA_WGRAD_FIRST_WRITE', '1') != '0'
 
 
 def conv_wgrad(x, dy, param, kind):
@@ -655,7 +651,7 @@ def conv_wgrad(x, dy, param, kind):
     # qualify (somebody else owns their .grad).
     cell = getattr(param, '_sba_gepoch', None)
     first = 0
-    if FIRST_WRITE and cell is not None and getattr(param, '_sba_wepoch', None) != cell[0]:
+    if cell is not None and getattr(param, '_sba_wepoch', None) != cell[0]:
         param._sba_wepoch = cell[0]
         first = 1
     g.first_write = first

@@ -79,9 +79,9 @@ CONV_CASES = [
     ('3x3', 2, 64, 64, 128, 128),     # M = 32768, OW % 64 == 0: all-taps halo-tile wgrad
     ('3x3up', 2, 64, 128, 64, 64),    # same with the fused nearest x2 (output 128 x 128)
     ('3x3', 1, 128, 64, 128, 256),    # two ci tiles, non-square map
-    ('3x3', 8, 64, 64, 128, 128),     # 512 tiles: persistent halo-tile kernel (conv3x3_halo2_kernel), 2 tiles per workgroup
-    ('3x3', 5, 64, 128, 128, 128),    # ... two 64-channel blocks of Cout, 320 tiles per block: uneven tile counts
-    ('3x3up', 9, 64, 64, 64, 64),     # ... behind the nearest x2 upsample (576 tiles, 3 per workgroup for some)
+    ('3x3', 8, 64, 64, 128, 128),     # 512 8 x 32 tiles: register-weight halo-tile kernel (conv3x3_halo3_kernel)
+    ('3x3', 5, 64, 128, 128, 128),    # ... two 64-channel blocks of Cout, 320 tiles per block
+    ('3x3up', 9, 64, 64, 64, 64),     # ... behind the nearest x2 upsample (576 tiles, LDS-weight conv3x3_halo_kernel)
     ('3x3up', 2, 128, 128, 64, 64),   # halo-tile kernel walking TWO 64-channel chunks of Cin = 128, behind the nearest x2 upsample
     ('3x3', 8, 128, 64, 64, 64),      # ... plain 3x3 (the shape of the data gradient of the ResBlocks' 64 -> 128 conv)
     ('3x3', 20, 768, 512, 4, 4),      # D_GET_LOGITS.jointConv at B = 20 (M = 320): LDS-DMA small-pixel-count wgrad, 10 stages
@@ -199,8 +199,8 @@ def test_dgrad4_grouped_plans(dev, case):
         ops.DGRAD4_GROUP, ops._DGRAD4_FORCE = old
 
 
-def test_conv_addend_epilogue_persistent_halo(dev):
-    """the persistent halo-tile kernel with the residual-add epilogue (ResBlock skip gradient) and statistics"""
+def test_conv_addend_epilogue_halo_tile(dev):
+    """the halo-tile kernel (conv3x3_halo3_kernel, 512 tiles) with the residual-add epilogue (ResBlock skip gradient)"""
     from sbagan import ops
     dt = torch.bfloat16
     x, w = fill.unit((8, 64, 128, 128), 1), fill.unit((64, 64, 3, 3), 2) / 24

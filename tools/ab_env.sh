@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of environment knobs on the benched step: each argument is one "NAME=VALUE[,NAME=VALUE...]" setting ("base" = none);
-# prints ms per step (short child runs of bench.py, all launch modes probed).   bash tools/ab_env.sh base SBA_SPLITK_FUSED=1
+# prints ms per step (short child runs of bench.py, all launch modes probed).   bash tools/ab_env.sh base SBA_Y_F16=1
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 for setting in "$@"; do
     envs=()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the implicit-GEMM conv kernels on the layer shapes of the B=20 step
-(tuning aid; SBA_IGEMM_CFG=A..E forces one tile configuration).  Prints one line per shape:
+(tuning aid: the library's dispatch and the measured tile table, as in the step).  Prints one line per shape:
 fwd / dgrad / wgrad microseconds and TFLOP/s."""
 import os
 import sys
@@ -41,7 +41,7 @@ def timeit(fn, n=10):
 def main():
     dev = torch.device('cuda:0')
     dt = torch.bfloat16 if os.environ.get('DT', 'bf16') == 'bf16' else torch.float32
-    print('cfg=%s B=%d dtype=%s' % (os.environ.get('SBA_IGEMM_CFG', 'auto'), B, dt))
+    print('B=%d dtype=%s' % (B, dt))
     print('%-12s %-7s %5s %5s %4s %8s | %8s %7s | %8s %7s | %8s %7s' % (
         'layer', 'kind', 'Cin', 'Cout', 'H', 'M', 'fwd_us', 'TF/s', 'dgrad_us', 'TF/s', 'wgrad_us', 'TF/s'))
     tot = [0.0, 0.0, 0.0]

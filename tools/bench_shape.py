@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of sba_conv_igemm on arbitrary (kh x kw, stride 1, same-padded) shapes, e.g. the
-Inception trunk's 17x17 factorised convs (tuning aid; SBA_IGEMM_CFG=A..E forces one configuration).
+Inception trunk's 17x17 factorised convs (tuning aid; TILE=1..18 forces a bf16 tile through sba_conv_geom.tile,
+KSPLIT its K splits).
 usage: bench_shape.py N H W Cin Cout KH KW [N H W Cin Cout KH KW ...]"""
 import ctypes
 import os
@@ -30,7 +31,8 @@ DEFAULT = [20, 17, 17, 192, 192, 1, 7, 20, 17, 17, 768, 192, 1, 1, 20, 17, 17, 1
 def main():
     a = [int(v) for v in sys.argv[1:]] or DEFAULT
     dev = torch.device('cuda:0')
-    print('cfg=%s d2f=%s' % (os.environ.get('SBA_IGEMM_CFG', 'auto'), os.environ.get('SBA_IGEMM_D2F', '0')))
+    tile, ksplit = int(os.environ.get('TILE', '0')), int(os.environ.get('KSPLIT', '0'))
+    print('tile=%s ksplit=%s' % (tile or 'rules', ksplit or 'rules'))
     for i in range(0, len(a), 7):
         N, H, W, Cin, Cout, KH, KW = a[i:i + 7]
         g = ConvGeom()
@@ -39,6 +41,7 @@ def main():
         g.OW = g.OWs = W
         g.sy = g.sx = g.osy = g.osx = 1
         g.ntaps = KH * KW
+        g.tile, g.ksplit = tile, ksplit
         for t in range(KH * KW):
             g.ty[t], g.tx[t] = t // KW - KH // 2, t % KW - KW // 2
         x = torch.randn(N, H, W, Cin, device=dev).bfloat16()

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Weight-gradient launches of the benched step, one shape at a time (B = 20): time per launch under the library's
-current dispatch.  Run once per setting of SBA_WGRAD_DMA (0 = register-staged, 3 / 4 = LDS-DMA ring depth); the
-library reads it once.  python tools/bench_wgrad.py"""
+current dispatch (SBA_LIB_PATH: time another build of the library).  python tools/bench_wgrad.py"""
 import os
 import sys
 
@@ -42,7 +41,7 @@ def main():
     from sbagan import ops
     dev = torch.device('cuda:0')
     ops.set_compute_dtype(torch.bfloat16)
-    print('SBA_WGRAD_DMA=%s SBA_WGRAD_GEN_DMA=%s' % (os.environ.get('SBA_WGRAD_DMA', '(default)'), os.environ.get('SBA_WGRAD_GEN_DMA', '(default)')))
+    print('library: %s' % os.environ.get('SBA_LIB_PATH', '(in-tree build)'))
     only = os.environ.get('BENCH_WGRAD_ONLY')           # substring of the shape's name: that shape alone (PMC runs)
     for kind, N, Cin, Cout, H, W, name in SHAPES:
         if only and only not in name:

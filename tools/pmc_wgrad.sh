@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes (rocprofv3, one counter group per run, --kernel-trace only) over ONE weight-gradient shape of tools/bench_wgrad.py
-# under the environment given:   SBA_WGRAD_S2=0 bash tools/pmc_wgrad.sh <out_prefix> "<substring of the shape's name>"
+# under the environment given:   SBA_LIB_PATH=tools/_ab/libsbagan_hip.so bash tools/pmc_wgrad.sh <out_prefix> "<substring of the shape's name>"
 cd "$(dirname "$0")/.."
 ROOT=$PWD
 out=$1; export BENCH_WGRAD_ONLY="$2"; export BENCH_FIRST_WRITE=1
