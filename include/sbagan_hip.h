@@ -146,6 +146,31 @@ int sba_conv_igemm_bias(int dtype, const void* x, const void* w, void* y, const 
  * register-weight halo kernel conv3x3_halo3g_kernel -- only with g->w_layout = 1),
  * plan[1] = tile id (families 1 / 2: the ids of sba_conv_geom.tile) or configuration, plan[2] = K splits. */
 int sba_conv_igemm_plan(int dtype, const sba_conv_geom* g, int64_t workspace_bytes, int* plan);
+
+/* ---- inference: conv + BatchNorm(eval) + GLU as ONE launch (sbagan/infer.py) ----
+ * sba_fold_bn_pack: fold an eval-mode BatchNorm into the layer in front of it and pack the result for the forward
+ * kernels.  w: f32 [O][taps][Cin] (a conv parameter stored channels_last, or a dense weight with taps = 1);
+ *   out[r][tap][ci] = w[src(r)][tap][ci] * s,   bias[r] = beta - running_mean * s,   s = gamma / sqrt(running_var + eps)
+ * with the product formed in f32 and rounded once to `dtype`.  glu = 0: O rows, src(r) = r.  glu = 1 (O = 2C, channel c
+ * gated by channel C + c): 64 * ceil(C / 32) rows, interleaved in granules of 32 -- rows 64 b .. 64 b + 31 are value
+ * channels 32 b .. 32 b + 31, rows 64 b + 32 .. 64 b + 63 their gates, rows of channels >= C are zero -- so that the
+ * 32 x 32 MFMA output layout leaves a value and its gate in the same lane.  The fragment-major copy the register-weight
+ * halo kernel reads is sba_pack_frag_multi of `out`. */
+int sba_fold_bn_pack(int dtype, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                     const float* running_var, float eps, void* out, float* bias, int O, int taps, int Cin, int glu,
+                     void* stream);
+/* y[pixel][c] = (acc[c] + bias[row of c]) * sigmoid(acc[C + c] + bias[row of C + c]), c < C, dense NHWC, for the
+ * stride-1 3 x 3 geometries ('3x3', and '3x3up' behind the nearest x2 upsample) with w / bias from
+ * sba_fold_bn_pack(glu = 1); g->Cout = the PACKED row count 64 * ceil(C / 32), g->y_cstride = g->y_coff = 0,
+ * g->w_layout = 1 for the fragment-major copy where the plan reports family 0.  bf16: C % 8 == 0.  No split-K, no
+ * workspace.  The residual half of a ResBlock (bias + addend, no activation) is sba_conv_igemm_bias with
+ * sba_fold_bn_pack(glu = 0) operands. */
+int sba_conv_igemm_glu(int dtype, const void* x, const void* w, const float* bias, void* y, int C,
+                       const sba_conv_geom* g, void* stream);
+/* the kernel sba_conv_igemm_glu launches: plan[0] = 0 halo-tile kernels (plan[1]: bit 0 = behind the upsample, bit 1 =
+ * conv3x3_halo3_kernel, fragment-major weights), 3 igemm_kernel (plan[1] = configuration: 0 128x128, 1 256x64, 2 128x64,
+ * 5 64x64 two waves); plan[2] = 1. */
+int sba_conv_igemm_glu_plan(int dtype, const sba_conv_geom* g, int C, int* plan);
 /* GROUPED launch: n <= SBA_GROUP_MAX independent convolutions -- no output of one is an input of another, their outputs
  * do not overlap -- as ONE grid (bf16 only, no split-K, no statistics; bias / ReLU (g->relu) / addend /
  * relu_mask per item as in sba_conv_igemm_bias).  For the branches of an Inception block at one depth level (model.py:226-262:
@@ -271,6 +296,11 @@ int sba_bn1d_glu_bwd(int dtype, const float* y, const void* dout, const float* g
 /* ---- small dense layers, f32 (CA_NET, MAPPING_NET, INIT fc, AdaIN style; model.py:278,306-313,330,354) ---- */
 int sba_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int K, int N,
                    void* stream);
+/* inference INIT_STAGE_G.fc: Linear(no bias) + BatchNorm1d(eval) + GLU + view(B, F2 / 16, 4, 4) in one launch:
+ * out[b][p][c] (NHWC, `dtype`) = GLU feature 16 c + p of x[b] with wp / bias = sba_fold_bn_pack(SBA_F32, ..., O = 2 F2,
+ * taps = 1, Cin = K, glu = 1).  F2 % 16 == 0. */
+int sba_linear_glu_fwd(int dtype, const float* x, const float* wp, const float* bias, void* out, int B, int K,
+                       int F2, void* stream);
 /* dx = dy*W (may be NULL); dw += dy^T x; dbias += sum dy (may be NULL). */
 int sba_linear_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw,
                    float* dbias, int B, int K, int N, void* stream);

@@ -36,7 +36,8 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
 // optional epilogue operands: per-channel bias, and a ReLU mask source (same layout as y): outputs are
 // zeroed where mask <= 0 -- the backward of the ReLU that produced the tensor whose gradient this is
 // yh: store the (bf16-typed) output as IEEE binary16 bits (SBA_BF16_YH: the pre-BatchNorm tensor)
-struct EpiX { const float* bias; const void* mask; int yh; };
+// glu_c > 0: the folded-BatchNorm GLU epilogue of the inference generator (tile_epilogue_glu): glu_c output channels
+struct EpiX { const float* bias; const void* mask; int yh; int glu_c; };
 
 // keep the bf16 halves of v whose counterpart in m is > 0
 __device__ __forceinline__ uint32_t relu_mask_bf16x2(uint32_t v, uint32_t m) {
@@ -219,6 +220,67 @@ __device__ __forceinline__ void tile_epilogue(f32x16_t (&acc)[TM][TN], const boo
 }
 
 // ---------------------------------------------------------------------------
+// GLU epilogue of the inference path (sba_conv_igemm_glu): the weight rows were packed by sba_fold_bn_pack with the
+// eval-mode BatchNorm scale folded in and the output channels interleaved in granules of 32 -- packed rows
+// 64 b .. 64 b + 31 are value channels 32 b .. 32 b + 31, rows 64 b + 32 .. 64 b + 63 their gates.  The C/D layout of
+// the 32 x 32 MFMA puts column (lane & 31) of an accumulator tile in one lane, so a wave that owns an EVEN number of
+// 32-column tiles (WN % 64 == 0) holds value channel c in acc[i][j] and its gate in acc[i][j + 1] of the SAME lane:
+//     out[pixel][c] = (acc_v + b'_v) * sigmoid(acc_g + b'_g)
+// needs no cross-lane or LDS exchange.  The C = ex.glu_c output channels are stored NHWC: f32 directly, one dword per
+// lane (the 32 lanes of a half-wave hold 32 consecutive channels of one pixel = one coalesced 128-byte row segment;
+// 16-byte stores per lane would need the transpose through LDS this path avoids), bf16 through the staging tile the plain epilogue uses as well (half its width), as 16-byte
+// row stores.  g.Cout is the PACKED row count (a multiple of 64; rows of channels >= C are zero).
+// ---------------------------------------------------------------------------
+template <typename T, int BM, int BN, int TM, int TN, int NTT, int STAGE_BYTES>
+__device__ __forceinline__ void tile_epilogue_glu(f32x16_t (&acc)[TM][TN], unsigned char* lds_all, const int* rowoff,
+                                                  const int wm0, const int wn0, const int lane, const int n_base,
+                                                  const sba_conv_geom& g, T* __restrict__ y, const EpiX ex) {
+    static_assert(TN % 2 == 0 && BN % 64 == 0, "a wave owns whole (value, gate) granule pairs");
+    const float* __restrict__ bias = ex.bias;
+    const int C = ex.glu_c;
+    const int ycs = g.y_cstride ? g.y_cstride : C;
+    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
+    constexpr bool kStageOut = sizeof(T) == 2;
+    constexpr int BNO = BN / 2;                      // output channels of the tile
+    constexpr int OROW = BNO * 2 + 16;
+    static_assert(!kStageOut || BM * OROW <= STAGE_BYTES, "output tile fits in the staging buffers");
+#pragma unroll
+    for (int j = 0; j < TN; j += 2) {
+        const int rv = n_base + wn0 + j * 32 + col_l;               // packed row of the value channel; gate: rv + 32
+        // (in range: g.Cout is a multiple of 64 and every launch grid covers exactly g.Cout packed rows)
+        const float bv = bias[rv], bg = bias[rv + 32];
+        const int lc = (wn0 >> 1) + (j >> 1) * 32 + col_l;          // output column inside the tile
+        const int oc = (n_base >> 1) + lc;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
+                const float v = (acc[i][j][r] + bv) * sigmoidf_(acc[i][j + 1][r] + bg);
+                if (kStageOut) {
+                    *reinterpret_cast<bf16_t*>(lds_all + row * OROW + lc * 2) = f2bf(v);
+                } else {
+                    const int pix = rowoff[row];
+                    if (pix >= 0 && oc < C) y[(int64_t)pix * ycs + g.y_coff + oc] = from_f<T>(v);
+                }
+            }
+        }
+    }
+    if (kStageOut) {
+        __syncthreads();
+        constexpr int CPRO = BNO / 8;                // 16-byte chunks per output row
+        for (int idx = threadIdx.x; idx < BM * CPRO; idx += NTT) {
+            const int row = idx / CPRO, cc = idx - row * CPRO;
+            const int pix = rowoff[row];
+            const int oc = (n_base >> 1) + cc * 8;
+            if (pix < 0 || oc >= C) continue;        // (C % 8 == 0 is checked on the host: whole chunks only)
+            const uint4 v = *reinterpret_cast<const uint4*>(lds_all + row * OROW + cc * 16);
+            *reinterpret_cast<uint4*>(y + (int64_t)pix * ycs + g.y_coff + oc) = v;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // forward / data-gradient implicit GEMM
 //   rows  = output pixels of the (OHs x OWs) sub-grid, M = N*OHs*OWs
 //   cols  = output channels
@@ -227,7 +289,7 @@ __device__ __forceinline__ void tile_epilogue(f32x16_t (&acc)[TM][TN], const boo
 // LDS: double-buffered A[BM] and B[BN] rows of 80 B (64 data + 16 pad: the
 // pad makes the 16-lane ds_read_b128 groups hit 16 distinct 4-bank slots).
 // ---------------------------------------------------------------------------
-template <typename T, int BM, int BN, int WM, int WN, int KS>
+template <typename T, int BM, int BN, int WM, int WN, int KS, int GLU = 0>
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM * BN == 128 * 128 && KS == 1) ? 3 : 1) void igemm_kernel(const T* __restrict__ x, const T* __restrict__ w,
                                                     T* __restrict__ y, const T* __restrict__ addend,
                                                     float* __restrict__ stats, const sba_conv_geom g,
@@ -432,8 +494,12 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
     }
     for (int c = threadIdx.x; c < 2 * BN; c += NT) s_stat[c] = 0.f;
     __syncthreads();
-    tile_epilogue<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, true, lds, rowoff, s_stat, wm0, wn0, lane, n_base, ycs, g,
-                                                    y, addend, stats, ex);
+    if constexpr (GLU) {
+        tile_epilogue_glu<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, lds, rowoff, wm0, wn0, lane, n_base, g, y, ex);
+    } else {
+        tile_epilogue<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, true, lds, rowoff, s_stat, wm0, wn0, lane, n_base, ycs, g,
+                                                        y, addend, stats, ex);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1088,7 +1154,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_dma_group_ke
 // distinct 4-bank groups (x2 upsampling: lane pairs share a pixel -> broadcast).
 // Waves: wave w owns tile rows 2w, 2w+1 (two 32-pixel M tiles) x all BN output channels.
 // ---------------------------------------------------------------------------
-template <int CIN, int BN, int UPS>
+template <int CIN, int BN, int UPS, int GLU = 0>
 __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
                                                            bf16_t* __restrict__ y, const bf16_t* __restrict__ addend,
                                                            float* __restrict__ stats, const sba_conv_geom g,
@@ -1239,8 +1305,12 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const bf16_t* __restr
             __syncthreads();
         }
     }
-    tile_epilogue<T, BM, BN, TM, TN, 256, STAGE>(acc, true, lds, rowoff, s_stat, wid * 64, 0, lane, n_base, ycs, g, y,
-                                                 addend, stats, ex);
+    if constexpr (GLU) {
+        tile_epilogue_glu<T, BM, BN, TM, TN, 256, STAGE>(acc, lds, rowoff, wid * 64, 0, lane, n_base, g, y, ex);
+    } else {
+        tile_epilogue<T, BM, BN, TM, TN, 256, STAGE>(acc, true, lds, rowoff, s_stat, wid * 64, 0, lane, n_base, ycs, g, y,
+                                                     addend, stats, ex);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1255,7 +1325,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const bf16_t* __restr
 // after the staging barrier.  LDS = the halo tile alone (49 KB; 37 KB behind the nearest x2 upsample): three workgroups
 // per CU, and half the LDS reads per MFMA (A fragments only).
 // ---------------------------------------------------------------------------
-template <int CIN, int UPS>
+template <int CIN, int UPS, int GLU = 0>
 __global__ __launch_bounds__(256, 3) void conv3x3_halo3_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wf,
                                                                bf16_t* __restrict__ y, const bf16_t* __restrict__ addend,
                                                                float* __restrict__ stats, const sba_conv_geom g,
@@ -1391,8 +1461,12 @@ __global__ __launch_bounds__(256, 3) void conv3x3_halo3_kernel(const bf16_t* __r
         }
     }
     __syncthreads();                            // the epilogue stages through the halo buffer
-    tile_epilogue<T, BM, BN, TM, TN, 256, STAGE>(acc, true, lds, rowoff, s_stat, wid * 64, 0, lane, n_base, ycs, g, y,
-                                                 addend, stats, ex);
+    if constexpr (GLU) {
+        tile_epilogue_glu<T, BM, BN, TM, TN, 256, STAGE>(acc, lds, rowoff, wid * 64, 0, lane, n_base, g, y, ex);
+    } else {
+        tile_epilogue<T, BM, BN, TM, TN, 256, STAGE>(acc, true, lds, rowoff, s_stat, wid * 64, 0, lane, n_base, ycs, g, y,
+                                                     addend, stats, ex);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2974,7 +3048,137 @@ bool dense_output(const sba_conv_geom& g) {
            (g.y_cstride == 0 || g.y_cstride == g.Cout) && g.y_coff == 0;
 }
 
+// ---- inference: conv + folded BatchNorm(eval) + GLU in one launch ----------------------------------------------
+// Kernel choice for sba_conv_igemm_glu.  plan[0] = family: 0 the halo-tile kernels (plan[1] = 0 / 1: plain / behind the
+// nearest x2 upsample; +2 with fragment-major weights = conv3x3_halo3_kernel), 3 the register-staged igemm_kernel
+// (plan[1] = configuration: 0 128x128, 1 256x64, 2 128x64, 5 the two-wave 64x64 tile).  Every configuration gives a
+// wave 64 packed columns (one value granule + its gate granule).
+// NO split-K in this path (plan[2] = 1 always): the partial sums of a split meet in the f32 workspace and the GLU would
+// have to move into the finishing pass, i.e. a second launch over the 2C-channel tensor -- the traffic this path exists
+// to remove.  The shape that decided it: the first upBlock (512 -> 2 x 256 at 8 x 8, B = 20: M = 1280, 144 K slabs) is
+// 160 workgroups of the 64x64 tile and ~1 % of the generator's forward time; the generator's large layers never split.
+template <typename T>
+int launch_igemm_glu(const void* x, const void* w, void* y, const sba_conv_geom& g, hipStream_t st, const EpiX ex,
+                     int* plan = nullptr) {
+    const int M = g.N * g.OHs * g.OWs;
+    const T* xp = (const T*)x; const T* wp = (const T*)w; T* yp = (T*)y;
+    if (g.w_layout != 0 && !(g.w_layout == 1 && sizeof(T) == 2 && halo_ok(g))) return SBA_E_ARG;
+    if constexpr (sizeof(T) == 2) {
+        if (halo_ok(g)) {
+            if (plan) { plan[0] = 0; plan[1] = (g.ups ? 1 : 0) + (g.w_layout == 1 ? 2 : 0); plan[2] = 1; return SBA_OK; }
+            dim3 grid(g.N * (g.OH / 8) * (g.OW / 32), g.Cout / 64);
+            const bf16_t* np = nullptr;
+            if (g.w_layout == 1) {
+                if (g.ups) SBA_LAUNCH((conv3x3_halo3_kernel<64, 1, 1>), grid, dim3(256), 0, st, xp, wp, yp, np, (float*)nullptr, g, ex);
+                else SBA_LAUNCH((conv3x3_halo3_kernel<64, 0, 1>), grid, dim3(256), 0, st, xp, wp, yp, np, (float*)nullptr, g, ex);
+            } else {
+                if (g.ups) SBA_LAUNCH((conv3x3_halo_kernel<64, 64, 1, 1>), grid, dim3(256), 0, st, xp, wp, yp, np, (float*)nullptr, g, ex);
+                else SBA_LAUNCH((conv3x3_halo_kernel<64, 64, 0, 1>), grid, dim3(256), 0, st, xp, wp, yp, np, (float*)nullptr, g, ex);
+            }
+            return SBA_CHECK_LAUNCH();
+        }
+    }
+    const int nslabs = g.ntaps * (g.Cin / (64 / (int)sizeof(T)));
+    int cfg;
+    if (g.Cout % 128 == 0 && cdiv(M, 128) * (g.Cout / 128) >= 320) cfg = 0;
+    else if (cdiv(M, 256) * (g.Cout / 64) >= 256) cfg = 1;
+    else if (cdiv(M, 128) * (g.Cout / 64) >= 256) cfg = 2;
+    else cfg = 5;
+    if (plan) { plan[0] = 3; plan[1] = cfg; plan[2] = 1; return SBA_OK; }
+    const T* np = nullptr;
+    float* nf = nullptr;
+    switch (cfg) {
+        case 0:
+            SBA_LAUNCH((igemm_kernel<T, 128, 128, 64, 64, 1, 1>), dim3(cdiv(M, 128), g.Cout / 128), dim3(256), 0, st, xp, wp,
+                       yp, np, nf, g, M, nf, nslabs, ex);
+            break;
+        case 1:
+            SBA_LAUNCH((igemm_kernel<T, 256, 64, 64, 64, 1, 1>), dim3(cdiv(M, 256), g.Cout / 64), dim3(256), 0, st, xp, wp,
+                       yp, np, nf, g, M, nf, nslabs, ex);
+            break;
+        case 2:
+            SBA_LAUNCH((igemm_kernel<T, 128, 64, 32, 64, 2, 1>), dim3(cdiv(M, 128), g.Cout / 64), dim3(256), 0, st, xp, wp,
+                       yp, np, nf, g, M, nf, nslabs, ex);
+            break;
+        default:
+            SBA_LAUNCH((igemm_kernel<T, 64, 64, 32, 64, 2, 1>), dim3(cdiv(M, 64), g.Cout / 64), dim3(128), 0, st, xp, wp,
+                       yp, np, nf, g, M, nf, nslabs, ex);
+            break;
+    }
+    return SBA_CHECK_LAUNCH();
+}
+
+// argument check shared by sba_conv_igemm_glu and its plan query; *out = the geometry the kernels get
+bool glu_geom(int dtype, const sba_conv_geom* g, int C, sba_conv_geom* out) {
+    if (!g || C <= 0 || g->Cout != 64 * ((C + 31) / 32)) return false;     // packed rows: 64 per 32 output channels
+    if (g->y_cstride != 0 || g->y_coff != 0 || g->relu) return false;       // dense C-channel output
+    if (dtype == SBA_BF16 && C % 8) return false;                           // 16-byte row stores
+    if (!geom_ok(g, dtype)) return false;
+    if (g->OHs != g->OH || g->OWs != g->OW) return false;
+    *out = *g;
+    out->y_cstride = C;
+    return true;
+}
+
+// Fold the eval-mode BatchNorm of a conv (or dense) layer into its weights and pack them for the forward kernels:
+//   out[r][tap][ci] = w[src(r)][tap][ci] * s,  bias[r] = beta - mean * s,  s = gamma / sqrt(var + eps)   (of row src(r))
+// the product in f32, rounded ONCE to the storage type.  glu = 0: src(r) = r.  glu = 1: the O = 2C rows are interleaved in
+// granules of 32 (tile_epilogue_glu): r = 64 b + q -> value channel 32 b + q (q < 32) or gate channel C + 32 b + q - 32;
+// rows of channels >= C are zero.
+template <typename T>
+__global__ __launch_bounds__(256) void fold_bn_pack_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, const float* __restrict__ mean,
+                                                           const float* __restrict__ var, const float eps,
+                                                           T* __restrict__ out, float* __restrict__ bias, const int O,
+                                                           const int rowlen, const int glu, const int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / rowlen), k = (int)(i - (int64_t)r * rowlen);
+        int src = r;
+        if (glu) {
+            const int C = O / 2, q = r & 63, c = (r >> 6) * 32 + (q & 31);
+            src = c < C ? c + (q >= 32 ? C : 0) : -1;
+        }
+        float v = 0.f, b = 0.f;
+        if (src >= 0) {
+            const float s = gamma[src] / sqrtf(var[src] + eps);
+            v = w[(int64_t)src * rowlen + k] * s;
+            b = beta[src] - mean[src] * s;
+        }
+        out[i] = from_f<T>(v);
+        if (k == 0) bias[r] = b;
+    }
+}
+
 }  // namespace
+
+extern "C" int sba_fold_bn_pack(int dtype, const float* w, const float* gamma, const float* beta,
+                                const float* running_mean, const float* running_var, float eps, void* out, float* bias,
+                                int O, int taps, int Cin, int glu, void* stream) {
+    if (!w || !gamma || !beta || !running_mean || !running_var || !out || !bias) return SBA_E_ARG;
+    if (O <= 0 || taps <= 0 || Cin <= 0 || (glu && O % 2)) return SBA_E_ARG;
+    const int rows = glu ? 64 * ((O / 2 + 31) / 32) : O;
+    const int64_t n = (int64_t)rows * taps * Cin;
+    if ((int64_t)taps * Cin > 0x7fffffff) return SBA_E_ARG;
+    const int blocks = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
+    SBA_DISPATCH(dtype, SBA_LAUNCH((fold_bn_pack_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, gamma,
+                                   beta, running_mean, running_var, eps, (T*)out, bias, O, taps * Cin, glu, n));
+    return SBA_CHECK_LAUNCH();
+}
+
+extern "C" int sba_conv_igemm_glu(int dtype, const void* x, const void* w, const float* bias, void* y, int C,
+                                  const sba_conv_geom* g, void* stream) {
+    sba_conv_geom gg;
+    if (!x || !w || !bias || !y || !glu_geom(dtype, g, C, &gg)) return SBA_E_ARG;
+    SBA_DISPATCH(dtype, return launch_igemm_glu<T>(x, w, y, gg, (hipStream_t)stream, EpiX{bias, nullptr, 0, C}));
+    return SBA_E_ARG;
+}
+
+extern "C" int sba_conv_igemm_glu_plan(int dtype, const sba_conv_geom* g, int C, int* plan) {
+    sba_conv_geom gg;
+    if (!plan || !glu_geom(dtype, g, C, &gg)) return SBA_E_ARG;
+    SBA_DISPATCH(dtype, return launch_igemm_glu<T>(nullptr, nullptr, nullptr, gg, nullptr, EpiX{nullptr, nullptr, 0, C}, plan));
+    return SBA_E_ARG;
+}
 
 extern "C" int sba_conv_igemm(int dtype, const void* x, const void* w, void* y, const void* addend,
                               float* stats, const sba_conv_geom* g, void* workspace, int64_t workspace_bytes,

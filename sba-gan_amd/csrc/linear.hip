@@ -415,7 +415,84 @@ __global__ void ctx_proj_bwd_kernel(const float* __restrict__ words, const float
     }
 }
 
+// ---------------------------------------------------------------------------
+// Inference INIT_STAGE_G.fc: Linear(no bias) + BatchNorm1d(eval) + GLU + view(B, F/32, 4, 4) in ONE launch on the f32
+// matrix cores (the kernel above with two accumulators).  wp / bias are the folded, granule-interleaved rows of
+// sba_fold_bn_pack(glu = 1): rows 64 b .. 64 b + 31 = value features 32 b .. 32 b + 31, the next 32 rows their gates, so
+// lane (r, h) holds feature 32 b + r of both and the GLU needs no exchange.  One wave = 32 samples x 32 output features;
+// value feature f = channel f / 16, pixel f % 16 of the NHWC output [B][16][F2 / 16].
+// VEC: K % 4 == 0 (16-byte operand loads); otherwise element loads (reduced-size configurations only).
+// ---------------------------------------------------------------------------
+template <typename T, bool VEC>
+__global__ __launch_bounds__(64) void linear_glu_mfma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
+                                                             const float* __restrict__ bias, T* __restrict__ out,
+                                                             int B, int K, int F2) {
+    const int lane = threadIdx.x, rl = lane & 31, hf = lane >> 5;
+    const int b0 = blockIdx.y * 32;
+    const int f = blockIdx.x * 32 + rl;
+    const bool bv = b0 + rl < B;
+    const float* xr = x + (int64_t)(bv ? b0 + rl : 0) * K;
+    const float* wv_ = wp + ((int64_t)blockIdx.x * 64 + rl) * K;         // (packed rows are padded: always in range)
+    const float* wg_ = wv_ + (int64_t)32 * K;
+    f32x16_t av, ag;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { av[r] = 0.f; ag[r] = 0.f; }
+    if (VEC) {
+        const int K4 = K / 4;
+        for (int j0 = 0; j0 < K4; j0 += 4) {
+            float4 xv[4], wv[4], gv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool ok = j0 + u < K4;
+                xv[u] = (ok && bv) ? *reinterpret_cast<const float4*>(xr + 4 * (j0 + u)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                wv[u] = ok ? *reinterpret_cast<const float4*>(wv_ + 4 * (j0 + u)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                gv[u] = ok ? *reinterpret_cast<const float4*>(wg_ + 4 * (j0 + u)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float x0 = hf ? xv[u].y : xv[u].x, x1 = hf ? xv[u].w : xv[u].z;
+                av = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, hf ? wv[u].y : wv[u].x, av, 0, 0, 0);
+                ag = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, hf ? gv[u].y : gv[u].x, ag, 0, 0, 0);
+                av = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, hf ? wv[u].w : wv[u].z, av, 0, 0, 0);
+                ag = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, hf ? gv[u].w : gv[u].z, ag, 0, 0, 0);
+            }
+        }
+    } else {
+        for (int k0 = 0; k0 < K; k0 += 2) {
+            const int k = k0 + hf;
+            const bool ok = k < K;
+            const float xa = (ok && bv) ? xr[k] : 0.f;
+            av = __builtin_amdgcn_mfma_f32_32x32x2f32(xa, ok ? wv_[k] : 0.f, av, 0, 0, 0);
+            ag = __builtin_amdgcn_mfma_f32_32x32x2f32(xa, ok ? wg_[k] : 0.f, ag, 0, 0, 0);
+        }
+    }
+    if (f < F2) {
+        const float bvv = bias[blockIdx.x * 64 + rl], bgg = bias[blockIdx.x * 64 + 32 + rl];
+        const int Cg = F2 / 16, c = f >> 4, p = f & 15;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int b = b0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+            if (b < B) out[((int64_t)b * 16 + p) * Cg + c] = from_f<T>((av[r] + bvv) * sigmoidf_(ag[r] + bgg));
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int sba_linear_glu_fwd(int dtype, const float* x, const float* wp, const float* bias, void* out, int B, int K,
+                                  int F2, void* stream) {
+    if (!x || !wp || !bias || !out || B <= 0 || K <= 0 || F2 <= 0 || F2 % 16) return SBA_E_ARG;
+    const dim3 grid(cdiv(F2, 32), cdiv(B, 32));
+    if (grid.y > 65535) return SBA_E_ARG;
+    if (K % 4 == 0) {
+        SBA_DISPATCH(dtype, SBA_LAUNCH((linear_glu_mfma_kernel<T, true>), grid, dim3(64), 0, (hipStream_t)stream, x, wp,
+                                       bias, (T*)out, B, K, F2));
+    } else {
+        SBA_DISPATCH(dtype, SBA_LAUNCH((linear_glu_mfma_kernel<T, false>), grid, dim3(64), 0, (hipStream_t)stream, x, wp,
+                                       bias, (T*)out, B, K, F2));
+    }
+    return SBA_CHECK_LAUNCH();
+}
 
 extern "C" int sba_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int K, int N,
                               void* stream) {

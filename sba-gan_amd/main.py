@@ -74,6 +74,7 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     if make_trainer is None:
         from trainer import condGANTrainer as make_trainer
     algo = make_trainer(output_dir, dataloader, dataset.n_words, dataset.ixtoword)
+    algo.fused_inference = bool(getattr(args, 'fused_inference', False))
     start_t = time.time()
     if training:
         algo.train()

@@ -1,6 +1,6 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
-    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--bert_dir DIR: the BERT entry points]
+    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
 reference's evaluation runs are seeded that way), the given one or a random one in training, and every run gets an
@@ -25,6 +25,9 @@ def options(what, default_cfg, argv=None, bert=False):
     ap.add_argument('--gpu', dest='gpu_id', type=int, default=0)
     ap.add_argument('--data_dir', dest='data_dir', type=str, default='')
     ap.add_argument('--manualSeed', type=int, help='manual seed')
+    ap.add_argument('--fused_inference', dest='fused_inference', action='store_true', default=False,
+                    help='sampling / gen_example: run the generator through sbagan.infer.FusedGenerator (BatchNorm '
+                         'folded into the convs, GLU in the conv epilogue)')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

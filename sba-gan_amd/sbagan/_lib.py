@@ -55,6 +55,9 @@ SIGNATURES = {
     'sba_conv_igemm': [I, P, P, P, P, P, G, P, L, P],
     'sba_conv_igemm_bias': [I, P, P, P, P, P, P, P, G, P, L, P],
     'sba_conv_igemm_plan': [I, G, L, POINTER(c_int)],
+    'sba_fold_bn_pack': [I, P, P, P, P, P, F, P, P, I, I, I, I, P],
+    'sba_conv_igemm_glu': [I, P, P, P, P, I, G, P],
+    'sba_conv_igemm_glu_plan': [I, G, I, POINTER(c_int)],
     'sba_conv_igemm_group': [I, I, POINTER(ConvGroupItem), I, P],
     'sba_conv_igemm_group_splitk': [I, I, POINTER(ConvGroupItem), I, I, P, L, P],
     'sba_conv_wgrad': [I, P, P, P, G, I, P],
@@ -71,6 +74,7 @@ SIGNATURES = {
     'sba_bn1d_glu_fwd': [I, P, P, P, P, P, P, P, P, P, I, I, F, F, P],
     'sba_bn1d_glu_bwd': [I, P, P, P, P, P, P, P, P, P, I, I, P],
     'sba_linear_fwd': [P, P, P, P, I, I, I, P],
+    'sba_linear_glu_fwd': [I, P, P, P, P, I, I, I, P],
     'sba_linear_bwd': [P, P, P, P, P, P, I, I, I, P],
     'sba_ca_fwd': [P, P, P, P, P, I, I, P],
     'sba_ca_bwd': [P, P, P, P, P, P, I, I, P],

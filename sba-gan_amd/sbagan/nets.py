@@ -54,6 +54,15 @@ class GLU(nn.Module):
         return x[:, :nc] * torch.sigmoid(x[:, nc:])
 
 
+# The sbagan.infer.FusedGenerator whose call is running, or None (always None in training).  While it is set, the three
+# layer types of a GENERATOR that end in an eval-mode BatchNorm hand their forward to it: _UpBlock (the only _ConvBNAct
+# subclass a generator holds: GLU, no residual, groups = 1), ResBlock and _FcBnGlu.  The wrapper looks the module up in
+# its own table and raises for any module it did not fold (a discriminator block, a layer of another generator), so
+# nothing is silently computed with the wrong operands.  One cell per process: fused calls are not re-entrant and not
+# thread-safe (FusedGenerator.__call__ refuses a nested call).
+_FUSED = [None]
+
+
 class _Layer(object):
     """(conv, bn, packed weight) triple handed to the autograd Functions."""
 
@@ -76,6 +85,10 @@ class _ConvBNAct(nn.Sequential):
         return l
 
     def forward(self, x, residual=None, groups=1):
+        if _FUSED[0] is not None:
+            if self.act != ACT_GLU or residual is not None or groups != 1:
+                raise RuntimeError('a fused inference call reached a %s: only generator upBlocks are folded' % type(self).__name__)
+            return _FUSED[0].conv_glu(self, x)
         l = self._layer()
         return ops.ConvBNActFn.apply(x, l.conv.weight, l.bn.weight, l.bn.bias, l, self.kind, self.act, residual,
                                      groups)
@@ -132,6 +145,8 @@ class ResBlock(nn.Module):
         return self._layers()[1]
 
     def forward(self, x):
+        if _FUSED[0] is not None:
+            return _FUSED[0].res_block(self, x)
         l1, l2 = self._layers()
         return ops.ResBlockFn.apply(x, l1.conv.weight, l1.bn.weight, l1.bn.bias,
                                     l2.conv.weight, l2.bn.weight, l2.bn.bias, self)
@@ -254,6 +269,8 @@ class _FcBnGlu(nn.Sequential):
         return self[1]
 
     def forward(self, x):
+        if _FUSED[0] is not None:
+            return _FUSED[0].fc_glu(self, x)
         if not self[1].training and torch.is_grad_enabled() and \
                 (x.requires_grad or self[0].weight.requires_grad or self[1].weight.requires_grad):
             # (checked here: grad mode is always off inside autograd.Function.forward)

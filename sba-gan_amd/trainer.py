@@ -245,7 +245,16 @@ class condGANTrainer(object):
             raise RuntimeError('cfg.TRAIN.NET_E is empty: no text encoder to load')
         netG.load_state_dict(torch.load(cfg.TRAIN.NET_G, map_location='cpu'))
         print('Load G from: ', cfg.TRAIN.NET_G)
-        return netG.to(dev).eval(), text_encoder.to(dev).eval()
+        return self._inference_generator(netG.to(dev).eval()), text_encoder.to(dev).eval()
+
+    fused_inference = False     # --fused_inference: sampling() / gen_example() call the generator through FusedGenerator
+
+    def _inference_generator(self, netG):
+        """netG (in eval mode, on the device) itself, or its fused inference wrapper (sbagan/infer.py)"""
+        if not self.fused_inference:
+            return netG
+        from sbagan.infer import FusedGenerator
+        return FusedGenerator(netG)
 
     @staticmethod
     def _output_root():

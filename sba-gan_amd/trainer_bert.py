@@ -63,7 +63,7 @@ class condGANTrainer(trainer.condGANTrainer):
         for net in (G_NET(), G_NET_MIX()):
             net.apply(weights_init)
             net.load_state_dict(state)
-            nets.append(net.to(dev).eval())
+            nets.append(self._inference_generator(net.to(dev).eval()))
         netG, netG_mix = nets
         print('Load G from: ', cfg.TRAIN.NET_G)
         for key, (captions, cap_lens, order) in data_dic.items():

@@ -9,6 +9,7 @@ inputs from oracle/fill.py, and only numeric outputs are written.
 
     python tools/make_golden.py            # all fixtures
     python tools/make_golden.py units      # just the reduced-size units
+    python tools/make_golden.py infer      # the eval-mode generator fixtures (infer_*.npz)
 """
 import os
 import sys
@@ -376,6 +377,37 @@ def gen_text_train(ref):
     print('text_encoder_train.npz: %d arrays' % len(S))
 
 
+def gen_infer(ref):
+    """The reference generators in eval() mode (running statistics; trainer.py:368 sampling / :437 gen_example) on
+    closed-form parameters: inputs are rebuilt by the tests (helpers.make_inputs, tag below), eps is recorded, every
+    stage's image and mu / logvar are stored as summaries."""
+    cfg, GA, model, model_bert, losses = ref
+    for name, d, B, variant, tag in (('infer_tiny_model.npz', TINY, 3, 'model', 1300),
+                                     ('infer_tiny_bert.npz', TINY, 3, 'bert', 1310),
+                                     ('infer_tiny_mix.npz', TINY, 3, 'mix', 1320),
+                                     ('infer_full_model_b4.npz', FULL, 4, 'model', 1330),
+                                     ('infer_full_bert_b4.npz', FULL, 4, 'bert', 1340),
+                                     ('infer_full_mix_b4.npz', FULL, 4, 'mix', 1350)):
+        set_dims(cfg, dict(d, branch=3))
+        x = make_inputs(d, B, 18, branch=3, lmax=18, tag=tag)
+        netG = {'model': model.G_NET, 'bert': model_bert.G_NET, 'mix': model_bert.G_NET_MIX}[variant]()
+        load_filled(netG)
+        netG.eval()
+        noise = x['z2'] if variant == 'mix' else x['z']
+        S = {'B': np.int64(B), 'tag': np.int64(tag)}
+        torch.manual_seed(4242)
+        S['eps'] = torch.FloatTensor(B, d['ncf']).normal_().numpy()
+        torch.manual_seed(4242)
+        with torch.no_grad():
+            fake, _, mu, logvar = netG(noise, x['sent'], x['words'], x['mask'])
+        for i, f in enumerate(fake):
+            put(S, 'img%d' % i, f)
+        put(S, 'mu', mu)
+        put(S, 'logvar', logvar)
+        np.savez_compressed(os.path.join(OUT, name), **S)
+        print('%s: %d arrays, %d bytes' % (name, len(S), os.path.getsize(os.path.join(OUT, name))))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     what = sys.argv[1:] or ['units', 'step_tiny', 'step_full']
@@ -385,6 +417,8 @@ def main():
         gen_text(ref)
     if 'text_train' in what:
         gen_text_train(ref)
+    if 'infer' in what:
+        gen_infer(ref)
     if 'units' in what:
         gen_units(ref)
     if 'step_tiny' in what:
