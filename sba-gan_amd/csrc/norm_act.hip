@@ -586,6 +586,8 @@ __global__ __launch_bounds__(256) void bn1d_glu_fwd_kernel(const float* __restri
         }
         const float var = q / B;
         m[h] = mean; r[h] = rsqrtf(var + eps);
+        // (y * scale + shift: the form the step's forward values were validated with.  The backward kernel recomputes the
+        // pre-activation as (y - mean) * scale + beta, which does not cancel at a tiny batch variance; see there)
         sc[h] = gamma[ff] * r[h]; sh[h] = beta[ff] - mean * sc[h];
         mean_o[ff] = mean; rstd_o[ff] = r[h];
         if (rmean) {
@@ -622,13 +624,16 @@ __global__ __launch_bounds__(256) void bn1d_glu_bwd_kernel(const float* __restri
     if (f >= fh) return;
     const int c = f / 16, s16 = f % 16;
     const int fa = f, fg = f + fh;
-    const float sca = gamma[fa] * rstd[fa], sha = beta[fa] - mean[fa] * sca;
-    const float scg = gamma[fg] * rstd[fg], shg = beta[fg] - mean[fg] * scg;
+    // the pre-activations are recomputed as (y - mean) * scale + beta, not y * scale + shift: with a tiny batch variance
+    // (B = 2, two nearly equal samples: rstd up to 316) y * scale and shift are two large numbers that cancel, and the
+    // gate's rounding error (4e-5) reaches dgamma / dbeta
+    const float sca = gamma[fa] * rstd[fa], ba = beta[fa], ma = mean[fa];
+    const float scg = gamma[fg] * rstd[fg], bg = beta[fg], mg = mean[fg];
     float a0 = 0.f, a1 = 0.f, g0 = 0.f, g1 = 0.f;
     constexpr int BM = 32;
     if (B <= BM) {          // one pass of loads, all in flight together (see bn1d_glu_fwd_kernel); same sums, same order
         float ya_[BM], yg_[BM], dd_[BM];
-        const float ma = mean[fa], ra = rstd[fa], mg = mean[fg], rg = rstd[fg];
+        const float ra = rstd[fa], rg = rstd[fg];
 #pragma unroll
         for (int b = 0; b < BM; ++b) {
             ya_[b] = b < B ? y[(int64_t)b * F + fa] : 0.f;
@@ -638,7 +643,7 @@ __global__ __launch_bounds__(256) void bn1d_glu_bwd_kernel(const float* __restri
 #pragma unroll
         for (int b = 0; b < BM; ++b)
             if (b < B) {
-                const float n = ya_[b] * sca + sha, gp = yg_[b] * scg + shg, s = sigmoidf_(gp);
+                const float n = (ya_[b] - ma) * sca + ba, gp = (yg_[b] - mg) * scg + bg, s = sigmoidf_(gp);
                 const float dza = dd_[b] * s, dzg = dd_[b] * n * s * (1.f - s);
                 a0 += dza; a1 += dza * (ya_[b] - ma) * ra;
                 g0 += dzg; g1 += dzg * (yg_[b] - mg) * rg;
@@ -649,7 +654,7 @@ __global__ __launch_bounds__(256) void bn1d_glu_bwd_kernel(const float* __restri
 #pragma unroll
         for (int b = 0; b < BM; ++b)
             if (b < B) {
-                const float n = ya_[b] * sca + sha, gp = yg_[b] * scg + shg, s = sigmoidf_(gp);
+                const float n = (ya_[b] - ma) * sca + ba, gp = (yg_[b] - mg) * scg + bg, s = sigmoidf_(gp);
                 const float dza = dd_[b] * s, dzg = dd_[b] * n * s * (1.f - s);
                 dy[(int64_t)b * F + fa] = sca * (dza - a0 * inv - (ya_[b] - ma) * ra * a1 * inv);
                 dy[(int64_t)b * F + fg] = scg * (dzg - g0 * inv - (yg_[b] - mg) * rg * g1 * inv);
@@ -658,7 +663,7 @@ __global__ __launch_bounds__(256) void bn1d_glu_bwd_kernel(const float* __restri
     }
     for (int b = 0; b < B; ++b) {
         const float ya = y[(int64_t)b * F + fa], yg = y[(int64_t)b * F + fg];
-        const float n = ya * sca + sha, gp = yg * scg + shg, s = sigmoidf_(gp);
+        const float n = (ya - ma) * sca + ba, gp = (yg - mg) * scg + bg, s = sigmoidf_(gp);
         const float dd = to_f<T>(dout[((int64_t)b * 16 + s16) * Cg + c]);
         const float dza = dd * s, dzg = dd * n * s * (1.f - s);
         a0 += dza; a1 += dza * (ya - mean[fa]) * rstd[fa];
@@ -669,7 +674,7 @@ __global__ __launch_bounds__(256) void bn1d_glu_bwd_kernel(const float* __restri
     const float inv = 1.f / B;
     for (int b = 0; b < B; ++b) {
         const float ya = y[(int64_t)b * F + fa], yg = y[(int64_t)b * F + fg];
-        const float n = ya * sca + sha, gp = yg * scg + shg, s = sigmoidf_(gp);
+        const float n = (ya - ma) * sca + ba, gp = (yg - mg) * scg + bg, s = sigmoidf_(gp);
         const float dd = to_f<T>(dout[((int64_t)b * 16 + s16) * Cg + c]);
         const float dza = dd * s, dzg = dd * n * s * (1.f - s);
         dy[(int64_t)b * F + fa] = sca * (dza - a0 * inv - (ya - mean[fa]) * rstd[fa] * a1 * inv);
@@ -1099,6 +1104,7 @@ extern "C" int sba_bn1d_glu_fwd(int dtype, const float* y, const float* gamma, c
                                 float* running_mean, float* running_var, int64_t* nbt, float* mean, float* rstd,
                                 void* out, int B, int F, float eps, float momentum, void* stream) {
     if (!y || !gamma || !beta || !mean || !rstd || !out || B <= 0 || F <= 0 || F % 32 != 0) return SBA_E_ARG;
+    if ((running_mean == nullptr) != (running_var == nullptr)) return SBA_E_ARG;
     SBA_DISPATCH(dtype, SBA_LAUNCH((bn1d_glu_fwd_kernel<T>), dim3(cdiv(F / 2, 64)), dim3(64), 0,
                                            (hipStream_t)stream, y, gamma, beta, running_mean, running_var, nbt,
                                            mean, rstd, (T*)out, B, F, eps, momentum));
@@ -1118,6 +1124,8 @@ extern "C" int sba_bn1d_glu_bwd(int dtype, const float* y, const void* dout, con
 }
 
 static bool in_shape_ok(int dtype, int N, int HW, int C) {
+    // (the dtype is refused HERE, before sba_instnorm_stats clears its outputs: a refused call writes nothing)
+    if (dtype != SBA_F32 && dtype != SBA_BF16) return false;
     const int V = dtype != SBA_F32 ? 8 : 4;
     return N > 0 && HW > 0 && C > 0 && C % V == 0 && C / V <= 256 && pow2(C / V);
 }
