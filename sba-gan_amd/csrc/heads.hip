@@ -516,7 +516,7 @@ __global__ __launch_bounds__(256) void d_stem_dgrad_kernel(const float* __restri
 }
 
 // fragment of columns [c32, c32 + 32) over the 16 pixel rows of a slice whose rows are 192 B apart: 8 consecutive
-// pixels per lane via ds_read_b64_tr_b16 (same addressing as WgFrag<bf16_t>::load of igemm.hip)
+// pixels per lane via ds_read_b64_tr_b16 (same addressing as WgFrag<bf16_t>::load of wgrad.hip)
 __device__ __forceinline__ bf16x8_t stem_tr_frag(const unsigned char* slice, const int c32, const int lane) {
     constexpr int ROWS = 192;
     const int g16 = lane >> 4, i16 = lane & 15;
@@ -664,7 +664,7 @@ __global__ __launch_bounds__(256, 2) void d_stem_dgrad_mfma_kernel(const float* 
 }
 
 // WEIGHT GRADIENT.  dw[co][k] += sum_pix dpre[pix][co] * patch[pix][k]: the contraction runs over PIXELS, both operands
-// are pixel-major, so the fragments are read with ds_read_b64_tr_b16 (WgFrag of igemm.hip: 4 pixels x 16 columns
+// are pixel-major, so the fragments are read with ds_read_b64_tr_b16 (WgFrag of wgrad.hip: 4 pixels x 16 columns
 // transposed per 16-lane group).  Per 64-pixel tile the workgroup stages dpre [64][64] and the patches [64][48 (+16 zero)]
 // as hi / lo bf16 rows of 192 B; wave (i, j) accumulates its 32 (co) x 32 (k') tile with 4 x 3 v_mfma_f32_32x32x16_bf16.
 // Patch columns are kept as k' = ci * 16 + kh * 4 + kw (a thread's four consecutive image floats = one 8-byte LDS

@@ -1,7 +1,11 @@
-// Implicit-GEMM convolution kernels for gfx950 (MI355X): forward / data-gradient
-// (one kernel, driven by a tap table) and weight-gradient.  NHWC activations,
+// Implicit-GEMM convolution kernels for gfx950 (MI355X): forward / data-gradient (one kernel,
+// driven by a tap table), its LDS-DMA and grouped variants, the halo-tile 3x3 kernels, the split-K
+// finishing pass, the folded-BatchNorm GLU epilogue of the inference generator, and the dispatch
+// behind the sba_conv_igemm* entry points.  NHWC activations,
 // [Cout][tap][Cin] packed weights, MFMA 32x32 tiles with f32 accumulation
 // (v_mfma_f32_32x32x16_bf16 for bf16 storage, v_mfma_f32_32x32x2_f32 for f32).
+// The weight gradients (sba_conv_wgrad) are in wgrad.hip, weight packing and 2x2 pooling in pack.hip;
+// conv_common.h holds what this file and wgrad.hip share (the LDS-DMA primitives, geom_ok).
 //
 // Replaces cuDNN under nn.Conv2d forward/backward in the reference
 // (model.py:32-35 conv3x3, :552 downBlock conv4x4 s2, :41 fused nearest x2).
@@ -9,26 +13,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_common.h"
 #include <type_traits>
 
 namespace {
-
-// Division of a pixel index (< 2^21) by a launch-constant: one 64-bit multiply instead of the
-// ~30-instruction integer division sequence (the weight-gradient kernels decode (n, oy, ox) for
-// every staged pixel, which made address generation their bottleneck).
-struct FastDiv {
-    uint64_t magic;     // ceil(2^42 / d), 0 = use the plain division
-    uint32_t d;
-};
-static inline FastDiv make_fastdiv(uint32_t d, int64_t max_n) {
-    FastDiv f;
-    f.d = d;
-    f.magic = (max_n < (1 << 21) && d > 0) ? (((uint64_t)1 << 42) + d - 1) / d : 0;
-    return f;
-}
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
-    return f.magic ? (uint32_t)(((uint64_t)n * f.magic) >> 42) : n / f.d;
-}
 
 // ---------------------------------------------------------------------------
 // MFMA over one 64-byte K slab held in LDS as rows of ROWB bytes
@@ -514,30 +502,13 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
 //     16-lane phase of a ds_read_b128 then covers all 64 banks.
 //   * out-of-image taps, rows beyond M and slabs beyond the split's range are out-of-range buffer offsets:
 //     the DMA writes zeros (tools/ldsdma_probe.hip).
-//   * the DMA is issued from inline asm (hipcc would otherwise drain ALL of it -- vmcnt(0) -- in front of
+//   * the DMA is issued from inline asm (lds_dma16 of conv_common.h; hipcc would otherwise drain ALL of it -- vmcnt(0) -- in front of
 //     every LDS read); completion is counted by hand: before stage s is read every wave waits until only the
 //     (D-2) younger stages it issued are outstanding, then the workgroup barrier makes all waves' parts visible
 //     and proves that nobody still reads the buffer the next issue overwrites.
 //   * workgroups are numbered so that the N tiles of one M tile run on one XCD, back to back (shared A rows
 //     are served by that XCD's L2).
 // ---------------------------------------------------------------------------
-// M0 = LDS destination of the DMA.  M0 is compiler-reserved; nothing else in these kernels uses it (LDS
-// instructions need no M0 on gfx9+, no dynamic register indexing, no LDS-DMA builtins), so it is simply
-// overwritten: saving and restoring it around every load cost two of the ~10 scalar instructions per load, and
-// with one wave per SIMD the main loop is instruction-ISSUE bound (rocprofv3: SQ_ACTIVE_INST_ANY 45 % of the wave
-// cycles against 10 % SQ_VALU_MFMA_BUSY_CYCLES on the 17x17 layers, profiles/r02_pmc_igemm_dma_v1.txt).
-// voff: per-lane byte offset (bounds-checked: 0xFFFFFFFF -> zeros); soff: wave-uniform byte offset added after
-// the bounds check -- the walk along K costs no per-lane arithmetic.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void lds_dma16(const __amdgpu_buffer_rsrc_t rsrc, const uint32_t voff, const uint32_t soff,
-                                          const uint32_t lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                 :: "v"(voff), "s"(rsrc), "s"(lds_dst), "s"(soff) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // Split-K partial sums: every split adds its partial tile into the zero-filled f32 workspace with device-scope
 // atomics; splitk_finish_kernel then runs the epilogue and leaves the workspace zero.  (The last arriving split finishing
@@ -1612,1050 +1583,6 @@ __global__ __launch_bounds__(256, 3) void conv3x3_halo3g_kernel(const bf16_t* __
                                                  addend, nullptr, ex);
 }
 
-// row-major packed conv operand [R][taps][K] (bf16; R a multiple of 32, K of 16) -> fragment-major
-// [ceil(R/64)][taps][2][K/16][64 lanes][8]: lane = ((k >> 3) & 1) * 32 + (r & 31).  One thread = 16 bytes.
-__global__ __launch_bounds__(256) void pack_frag_kernel(const sba_frag_desc* __restrict__ descs, const int ndesc,
-                                                        const int total_units) {
-    const int u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= total_units) return;
-    int lo = 0, hi = ndesc - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].unit_begin <= u) lo = mid; else hi = mid - 1;
-    }
-    const sba_frag_desc d = descs[lo];
-    const int local = u - d.unit_begin;
-    const int k8n = d.K / 8;
-    const int k8 = local % k8n, rest = local / k8n;
-    const int t = rest % d.taps, r = rest / d.taps;
-    const uint4 v = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(d.src) + ((int64_t)r * d.taps + t) * d.K + 8 * k8);
-    const int nb = r >> 6, j = (r >> 5) & 1, nn = r & 31, k16 = k8 >> 1, gg = k8 & 1, ks = d.K / 16;
-    const int64_t o = (((((int64_t)nb * d.taps + t) * 2 + j) * ks + k16) * 512) + (gg * 32 + nn) * 8;
-    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(d.dst) + o) = v;
-}
-
-// ---------------------------------------------------------------------------
-// weight gradient: dw[co][tap][ci] += sum_pixels dy[pixel][co] * x[gather(pixel,tap)][ci]
-// Workgroup = one 64(co) x 64(ci) tile of one tap; its 4 waves each walk their
-// own 16-pixel slices of the workgroup's pixel range, then reduce through LDS.
-// Both operands are pixel-major in memory; the MFMA wants 8 consecutive
-// pixels per lane, so bf16 fragments are read with ds_read_b64_tr_b16 (4
-// pixels x 16 channels transposed per 16-lane group); f32 fragments are single
-// elements and need no transpose.
-// ---------------------------------------------------------------------------
-template <typename T> struct WgFrag;
-
-template <> struct WgFrag<bf16_t> {
-    static constexpr int ROWS = 64 * 2 + 64;   // bytes per pixel row: 128 data + 64 pad (bank spread)
-    // fragment of channels [c32, c32+32) over pixels [0,16) of a slice
-    static __device__ __forceinline__ bf16x8_t load(const unsigned char* slice, int c32, int lane) {
-        const int g16 = lane >> 4, i16 = lane & 15;
-        const int cbase = c32 + 16 * (g16 & 1), kbase = 8 * (g16 >> 1);
-        const int q = i16 >> 2, p = i16 & 3;
-        const unsigned char* a0 = slice + (kbase + q) * ROWS + (cbase + 4 * p) * 2;
-        typedef __attribute__((address_space(3))) s16x4_t* lptr;
-        s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(a0));
-        s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(a0 + 4 * ROWS));
-        bf16x8_t r;
-        r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-        r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-        return r;
-    }
-    static __device__ __forceinline__ void mma(const unsigned char* sa, const unsigned char* sb, int lane,
-                                               f32x16_t (&acc)[2][2]) {
-        bf16x8_t a[2], b[2];
-        a[0] = load(sa, 0, lane); a[1] = load(sa, 32, lane);
-        b[0] = load(sb, 0, lane); b[1] = load(sb, 32, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-};
-
-template <> struct WgFrag<float> {
-    static constexpr int ROWS = 64 * 4 + 64;
-    static __device__ __forceinline__ void mma(const unsigned char* sa, const unsigned char* sb, int lane,
-                                               f32x16_t (&acc)[2][2]) {
-        const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            float a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                a[i] = *reinterpret_cast<const float*>(sa + (2 * kk + h) * ROWS + (i * 32 + r) * 4);
-                b[i] = *reinterpret_cast<const float*>(sb + (2 * kk + h) * ROWS + (i * 32 + r) * 4);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-    }
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy,
-                                                    float* __restrict__ dw, const sba_conv_geom g,
-                                                    const int M, const int chunks_per_split,
-                                                    const int use_atomic, const FastDiv dsub, const FastDiv dow,
-                                                    const int64_t zstride) {
-    constexpr int ROWS = WgFrag<T>::ROWS;
-    constexpr int CH = 16 / (int)sizeof(T);          // elements per 16-byte chunk
-    constexpr int CPR = 64 / CH;                     // chunks per 64-channel pixel row
-    constexpr int LPT = 16 * CPR / 64;               // 16-byte loads per lane per slice
-    constexpr int SLICE = 16 * ROWS;
-    static_assert(4 * 2 * SLICE >= 64 * 64 * 4, "reduction buffer fits in the staging area");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[4 * 2 * SLICE];
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int co0 = blockIdx.x * 64;
-    const int ci_tiles = (g.Cin + 63) / 64;
-    const int tap = blockIdx.y / ci_tiles, ci0 = (blockIdx.y - tap * ci_tiles) * 64;
-    int ty = 0, tx = 0;
-#pragma unroll
-    for (int t = 0; t < SBA_MAX_TAPS; ++t)
-        if (t == tap) { ty = g.ty[t]; tx = g.tx[t]; }
-    const int IHL = g.ups ? 2 * g.IH : g.IH, IWL = g.ups ? 2 * g.IW : g.IW;
-    const int sub = g.OHs * g.OWs;
-
-    unsigned char* sa = lds + wid * 2 * SLICE;
-    unsigned char* sb = sa + SLICE;
-
-    f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int chunk_lo = blockIdx.z * chunks_per_split;
-    const int total_chunks = (M + 63) / 64;
-    const int chunk_hi = min(chunk_lo + chunks_per_split, total_chunks);
-
-    uint4 va[LPT], vb[LPT];
-    auto gload = [&](int ck) {
-        const int m0 = ck * 64 + wid * 16;          // this wave's 16 pixels
-#pragma unroll
-        for (int u = 0; u < LPT; ++u) {
-            const int idx = lane + 64 * u;
-            const int pix = idx / CPR, cc = idx - pix * CPR;
-            const int m = m0 + pix;
-            va[u] = make_uint4(0, 0, 0, 0);
-            vb[u] = make_uint4(0, 0, 0, 0);
-            if (m < M) {
-                const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
-                const int co = co0 + cc * CH;
-                if (co < g.Cout) {
-                    const int64_t po = (int64_t)(n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
-                    va[u] = *reinterpret_cast<const uint4*>(dy + po * g.Cout + co);
-                }
-                int iy = oy * g.sy + ty, ix = ox * g.sx + tx;
-                const bool ok = (iy >= 0) & (iy < IHL) & (ix >= 0) & (ix < IWL);
-                if (g.ups) { iy >>= 1; ix >>= 1; }
-                const int ci = ci0 + cc * CH;
-                if (ok && ci < g.Cin) {
-                    const int64_t pi = (int64_t)(n * g.IH + iy) * g.IW + ix;
-                    vb[u] = *reinterpret_cast<const uint4*>(x + pi * g.Cin + ci);
-                }
-            }
-        }
-    };
-    if (chunk_lo < chunk_hi) gload(chunk_lo);
-    for (int ck = chunk_lo; ck < chunk_hi; ++ck) {
-        __syncthreads();    // previous slice fully consumed by this wave's MFMA reads
-#pragma unroll
-        for (int u = 0; u < LPT; ++u) {
-            const int idx = lane + 64 * u;
-            const int pix = idx / CPR, cc = idx - pix * CPR;
-            *reinterpret_cast<uint4*>(sa + pix * ROWS + cc * 16) = va[u];
-            *reinterpret_cast<uint4*>(sb + pix * ROWS + cc * 16) = vb[u];
-        }
-        __syncthreads();
-        if (ck + 1 < chunk_hi) gload(ck + 1);     // next chunk's loads fly under this chunk's MFMAs
-        WgFrag<T>::mma(sa, sb, lane, acc);
-    }
-
-    // cross-wave reduction through LDS, wave by wave (a fixed order: no LDS atomics), then one add per element
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(lds);
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
-#pragma unroll 1
-    for (int wv = 0; wv < 4; ++wv) {
-        if (wid == wv) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = i * 32 + (r & 3) + 8 * (r >> 2) + rsel;   // co
-                        float* q = &red[row * 64 + j * 32 + col_l];
-                        *q = wv == 0 ? acc[i][j][r] : *q + acc[i][j][r];
-                    }
-        }
-        __syncthreads();
-    }
-    float* dwz = dw + (int64_t)blockIdx.z * zstride;    // deterministic mode: this pixel split's own partial tensor
-    for (int i = tid; i < 64 * 64; i += 256) {
-        const int co = co0 + (i >> 6), ci = ci0 + (i & 63);
-        if (co < g.Cout && ci < g.Cin) {
-            float* p = dwz + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-            if (use_atomic == 1) atomicAdd(p, red[i]);
-            else if (use_atomic == 2) *p = red[i];
-            else *p += red[i];
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// weight gradient, small-pixel-count regime (GEMM-like layers at 4x4 / 8x8 maps with
-// thousands of channels): every wave owns its own 64(co) x 64(ci) tile of one tap and walks
-// ALL pixels of the block's range, so there is no cross-wave reduction; the four waves of a
-// workgroup share the dy slice (same co tile) and differ in (tap, ci tile).  (Two co tiles per wave against the
-// same x slice, 0.375 instead of 0.625 KB of operands per MFMA: measured 20-35 % SLOWER at 4 waves per SIMD, removed.)
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict__ x, const T* __restrict__ dy,
-                                                          float* __restrict__ dw, const sba_conv_geom g,
-                                                          const int M, const int chunks_per_split,
-                                                          const int use_atomic, const FastDiv dsub,
-                                                          const FastDiv dow, const int64_t zstride) {
-    constexpr int ROWS = WgFrag<T>::ROWS;
-    constexpr int CH = 16 / (int)sizeof(T);
-    constexpr int CPR = 64 / CH;
-    constexpr int LPT = 16 * CPR / 64;               // 16-byte loads per lane for a wave-private slice
-    constexpr int APT = (16 * CPR + 255) / 256;      // 16-byte loads per thread for the shared dy slice
-    constexpr int SLICE = 16 * ROWS;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[5 * SLICE];
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int co0 = blockIdx.x * 64;
-    const int ci_tiles = (g.Cin + 63) / 64;
-    const int item = blockIdx.y * 4 + wid;
-    const bool active = item < g.ntaps * ci_tiles;
-    const int tap = active ? item / ci_tiles : 0;
-    const int ci0 = active ? (item - tap * ci_tiles) * 64 : 0;
-    int ty = 0, tx = 0;
-#pragma unroll
-    for (int t = 0; t < SBA_MAX_TAPS; ++t)
-        if (t == tap) { ty = g.ty[t]; tx = g.tx[t]; }
-    const int IHL = g.ups ? 2 * g.IH : g.IH, IWL = g.ups ? 2 * g.IW : g.IW;
-    const int sub = g.OHs * g.OWs;
-
-    unsigned char* sa = lds;
-    unsigned char* sb = lds + (1 + wid) * SLICE;
-
-    f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int total_chunks = (M + 15) / 16;
-    const int chunk_lo = blockIdx.z * chunks_per_split;
-    const int chunk_hi = min(chunk_lo + chunks_per_split, total_chunks);
-
-    uint4 va[APT], vb[LPT];
-    auto gload = [&](int ck) {
-        const int m0 = ck * 16;
-#pragma unroll
-        for (int u = 0; u < APT; ++u) {
-            const int idx = tid + 256 * u;
-            va[u] = make_uint4(0, 0, 0, 0);
-            if (idx < 16 * CPR) {
-                const int pix = idx / CPR, cc = idx - pix * CPR;
-                const int m = m0 + pix, co = co0 + cc * CH;
-                if (m < M && co < g.Cout) {
-                    const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                    const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
-                    const int64_t po = (int64_t)(n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
-                    va[u] = *reinterpret_cast<const uint4*>(dy + po * g.Cout + co);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < LPT; ++u) {
-            const int idx = lane + 64 * u;
-            const int pix = idx / CPR, cc = idx - pix * CPR;
-            const int m = m0 + pix;
-            vb[u] = make_uint4(0, 0, 0, 0);
-            if (active && m < M) {
-                const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
-                int iy = oy * g.sy + ty, ix = ox * g.sx + tx;
-                const bool ok = (iy >= 0) & (iy < IHL) & (ix >= 0) & (ix < IWL);
-                if (g.ups) { iy >>= 1; ix >>= 1; }
-                const int ci = ci0 + cc * CH;
-                if (ok && ci < g.Cin) {
-                    const int64_t pi = (int64_t)(n * g.IH + iy) * g.IW + ix;
-                    vb[u] = *reinterpret_cast<const uint4*>(x + pi * g.Cin + ci);
-                }
-            }
-        }
-    };
-    if (chunk_lo < chunk_hi) gload(chunk_lo);
-    for (int ck = chunk_lo; ck < chunk_hi; ++ck) {
-        __syncthreads();          // everyone is done reading the previous slices
-#pragma unroll
-        for (int u = 0; u < APT; ++u) {
-            const int idx = tid + 256 * u;
-            if (idx < 16 * CPR) {
-                const int pix = idx / CPR, cc = idx - pix * CPR;
-                *reinterpret_cast<uint4*>(sa + pix * ROWS + cc * 16) = va[u];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < LPT; ++u) {
-            const int idx = lane + 64 * u;
-            const int pix = idx / CPR, cc = idx - pix * CPR;
-            *reinterpret_cast<uint4*>(sb + pix * ROWS + cc * 16) = vb[u];
-        }
-        __syncthreads();
-        if (ck + 1 < chunk_hi) gload(ck + 1);
-        WgFrag<T>::mma(sa, sb, lane, acc);
-    }
-
-    if (!active) return;
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                const int ci = ci0 + j * 32 + col_l;
-                if (co < g.Cout && ci < g.Cin) {
-                    float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-                    if (use_atomic == 1) atomicAdd(p, acc[i][j][r]);
-                    else if (use_atomic == 2) *p = acc[i][j][r];       // first write of a cleared gradient
-                    else *p += acc[i][j][r];
-                }
-            }
-}
-
-// ---------------------------------------------------------------------------
-// The same decomposition (one 64 x 64 tile of one tap per wave, the workgroup's waves share the dy slices) fed by
-// LDS-DMA through a D-deep ring instead of register staging.  The register-staged kernel above prefetches ONE
-// 16-pixel chunk (four MFMAs, ~0.1 us) ahead of an L2 round trip of ~1 us, so every chunk costs a full memory
-// latency: 320 pixels = 20 chunks ~ 30 us per workgroup whatever the MFMA work is.  Here a stage is 32 pixels
-// (two MFMA k-steps): per wave four 1 KB DMA instructions for its own x slice (the im2col gather is the per-lane
-// address) and CT for its share of the dy slices; D - 1 stages are in flight, completion is counted with
-// s_waitcnt vmcnt + one workgroup barrier per stage, exactly like igemm_dma_kernel.  Rows are 128 bytes (64
-// channels, no padding: the DMA writes lane l at M0 + 16 l); the 16-byte chunk position is XORed with bit 1 of the
-// row so that the four rows x 32 bytes a 16-lane group reads with ds_read_b64_tr_b16 fall in different banks.
-// ---------------------------------------------------------------------------
-struct WgFragDma {
-    // fragment of channels [c32, c32+32) over pixels [16 k16, 16 k16 + 16) of a 32-row slice
-    static __device__ __forceinline__ bf16x8_t load(const unsigned char* slice, int k16, int c32, int lane) {
-        const int g16 = lane >> 4, i16 = lane & 15;
-        const int cbase = c32 + 16 * (g16 & 1), row = 16 * k16 + 8 * (g16 >> 1) + (i16 >> 2), p = i16 & 3;
-        const int cpos = (cbase >> 3) ^ (((row >> 1) & 1) << 2);
-        const unsigned char* a0 = slice + row * 128 + cpos * 16 + p * 8;
-        typedef __attribute__((address_space(3))) s16x4_t* lptr;
-        s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(a0));
-        s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(a0 + 4 * 128));
-        bf16x8_t r;
-        r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-        r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-        return r;
-    }
-};
-
-template <int CT, int D>
-__global__ __launch_bounds__(256, 2) void wgrad_small_dma_kernel(const bf16_t* __restrict__ x,
-                                                              const bf16_t* __restrict__ dy,
-                                                              float* __restrict__ dw, const sba_conv_geom g,
-                                                              const int M, const int chunks_per_split,
-                                                              const int use_atomic, const FastDiv dsub,
-                                                              const FastDiv dow, const int64_t zstride) {
-    constexpr int SL = 32 * 128;                 // one slice: 32 pixels x 64 channels
-    constexpr int STAGE = (CT + 4) * SL;         // [dy slices (shared)] [x slice of wave 0..3]
-    constexpr int LPS = 4 + CT;                  // DMA instructions per wave per stage
-    extern __shared__ __attribute__((aligned(1024))) unsigned char wg_lds[];
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int co0 = blockIdx.x * (64 * CT);
-    const int ci_tiles = (g.Cin + 63) / 64;
-    const int item = blockIdx.y * 4 + wid;
-    const bool active = item < g.ntaps * ci_tiles;
-    const int tap = active ? item / ci_tiles : 0;
-    const int ci0 = active ? (item - tap * ci_tiles) * 64 : 0;
-    int ty = 0, tx = 0;
-#pragma unroll
-    for (int t = 0; t < SBA_MAX_TAPS; ++t)
-        if (t == tap) { ty = g.ty[t]; tx = g.tx[t]; }
-    const int IHL = g.ups ? 2 * g.IH : g.IH, IWL = g.ups ? 2 * g.IW : g.IW;
-    const int sub = g.OHs * g.OWs;
-
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)wg_lds;
-    const uint32_t x_bytes = (uint32_t)((int64_t)g.N * g.IH * g.IW * g.Cin * 2);
-    const uint32_t dy_bytes = (uint32_t)((int64_t)g.N * g.OH * g.OW * g.Cout * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, dy_bytes, 0x00020000);
-    constexpr uint32_t OOB = 0xFFFFFFFFu;
-
-    // lane l of a DMA instruction fills 16-byte position (l & 7) of row (l >> 3) of its 8-row block; that position
-    // holds channel chunk (l & 7) ^ 4 * bit1(row)
-    const int rsub = lane >> 3, cg = (lane & 7) ^ (((lane >> 4) & 1) << 2);
-    const bool x_ok = active && ci0 + cg * 8 < g.Cin;
-    const uint32_t x_coff = (uint32_t)(ci0 + cg * 8) * 2u;
-    const int dslice = CT == 1 ? 0 : (wid >> 1);
-    const bool d_ok = co0 + dslice * 64 + cg * 8 < g.Cout;
-    const uint32_t d_coff = (uint32_t)(co0 + dslice * 64 + cg * 8) * 2u;
-    const uint32_t x_pix = (uint32_t)g.Cin * 2u, d_pix = (uint32_t)g.Cout * 2u;
-
-    const int total_chunks = (M + 31) / 32;
-    const int chunk_lo = blockIdx.z * chunks_per_split;
-    const int chunk_hi = min(chunk_lo + chunks_per_split, total_chunks);
-    int g_ck = chunk_lo;
-
-    auto issue = [&](const uint32_t dst) {
-        const bool live = g_ck < chunk_hi;
-        const int m0 = g_ck * 32;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + 8 * i + rsub;
-            uint32_t off = OOB;
-            if (live && x_ok && m < M) {
-                const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
-                int iy = oy * g.sy + ty, ix = ox * g.sx + tx;
-                const bool ok = (iy >= 0) & (iy < IHL) & (ix >= 0) & (ix < IWL);
-                if (g.ups) { iy >>= 1; ix >>= 1; }
-                if (ok) off = (uint32_t)((n * g.IH + iy) * g.IW + ix) * x_pix + x_coff;
-            }
-            lds_dma16(xr, off, 0u, dst + (uint32_t)((CT + wid) * SL + i * 1024));
-        }
-#pragma unroll
-        for (int j = 0; j < CT; ++j) {
-            const int i = CT == 1 ? wid : 2 * (wid & 1) + j;
-            const int m = m0 + 8 * i + rsub;
-            uint32_t off = OOB;
-            if (live && d_ok && m < M) {
-                const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
-                off = (uint32_t)((n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox) * d_pix + d_coff;
-            }
-            lds_dma16(dr, off, 0u, dst + (uint32_t)(dslice * SL + i * 1024));
-        }
-        ++g_ck;
-    };
-
-    f32x16_t acc[CT][2][2];
-#pragma unroll
-    for (int s = 0; s < CT; ++s)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[s][i][j][r] = 0.f;
-
-    int islot = 0;
-#pragma unroll
-    for (int p = 0; p < D - 1; ++p) { issue(lds_base + (uint32_t)(islot * STAGE)); ++islot; }
-    if (islot == D) islot = 0;
-    int cslot = 0;
-    for (int ck = chunk_lo; ck < chunk_hi; ++ck) {
-        wait_vmcnt<(D - 2) * LPS>();         // this wave's part of stage ck has landed ...
-        wg_barrier();                        // ... and everybody else's; nobody reads slot (ck - 1) % D any more
-        issue(lds_base + (uint32_t)(islot * STAGE));
-        if (++islot == D) islot = 0;
-        const unsigned char* st = wg_lds + cslot * STAGE;
-        const unsigned char* sb = st + (CT + wid) * SL;
-#pragma unroll
-        for (int k16 = 0; k16 < 2; ++k16) {
-            bf16x8_t b[2];
-            b[0] = WgFragDma::load(sb, k16, 0, lane);
-            b[1] = WgFragDma::load(sb, k16, 32, lane);
-#pragma unroll
-            for (int s = 0; s < CT; ++s) {
-                bf16x8_t a[2];
-                a[0] = WgFragDma::load(st + s * SL, k16, 0, lane);
-                a[1] = WgFragDma::load(st + s * SL, k16, 32, lane);
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[s][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[s][i][j], 0, 0, 0);
-            }
-        }
-        if (++cslot == D) cslot = 0;
-    }
-    wait_vmcnt<0>();            // the dead stages issued past the end still write (zeros) into the ring
-    wg_barrier();
-
-    if (!active) return;
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
-#pragma unroll
-    for (int s = 0; s < CT; ++s)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + s * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                    const int ci = ci0 + j * 32 + col_l;
-                    if (co < g.Cout && ci < g.Cin) {
-                        float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-                        if (use_atomic == 1) atomicAdd(p, acc[s][i][j][r]);
-                        else if (use_atomic == 2) *p = acc[s][i][j][r];       // first write of a cleared gradient
-                        else *p += acc[s][i][j][r];
-                    }
-                }
-}
-
-// ---------------------------------------------------------------------------
-// Kernel-row decomposition: the workgroup's waves = the KW taps of ONE kernel row kh and one 64-channel input tile.
-// wgrad_small_dma_kernel gathers a 32-pixel x slice per wave (tap): 32 KW pixel rows per stage.  The kw taps of a kernel
-// row read the SAME input row(s) at column offsets 0..KW-1 of a stride-SX walk, so here the stage holds that input row
-// segment once -- R output rows x Wc output columns = 32 pixels (Wc = min(OW, 32)) need R x (SX (Wc - 1) + KW) input
-// pixels -- and wave kw reads pixel (r, j) of it at LDS row r XW + SX j + kw.
-//   <4, 2>: the 4x4 / stride-2 down blocks (encode_image_by_16times and the extra down blocks, model.py:540-575): <= 72
-//           input pixels instead of 128: 4 KB (dy) + 9 KB per stage instead of 20 KB, four DMA instructions per wave
-//           instead of five, 1.6x fewer bytes L2 -> LDS per MFMA (the roofline of this family);
-//   <3, 1>: 3x3 stride-1 convs (the generator's 64 x 64 maps): <= 40 input pixels instead of 96, three waves.
-// DMA blocks (8 rows x 128 B) of a stage: 0..3 = the dy slice, 4.. = the x rows, dealt round-robin to the waves.
-// Stride 2: channel chunk c of LDS row L sits at 16-byte position c ^ 2 ((L >> 1) & 3) -- the four stride-2 rows a 16-lane
-// group reads with ds_read_b64_tr_b16 fall into four different 32-byte bank groups; stride 1: c ^ 4 bit1(L) as above.
-// ---------------------------------------------------------------------------
-template <int SX>
-struct WgFragRow {
-    // fragment of channels [c32, c32+32) over output pixels [16 k16, 16 k16 + 16) of the chunk, tap column kw
-    static __device__ __forceinline__ int swz(int L) { return SX == 2 ? (((L >> 1) & 3) << 1) : (((L >> 1) & 1) << 2); }
-    // Stride 2: a wave's rows all have the parity of kw, and a 128-byte row covers half the banks -- every read would use 32 of
-    // the 64 banks (PMC: SQ_LDS_BANK_CONFLICT = a third of the LDS cycles).  Segment row L therefore lives in LDS row
-    // L ^ bit1(L) (an involution; swz() does not see bit 0): rows L and L + 2 fall into different halves.
-    static __device__ __forceinline__ int slot(int L) { return SX == 2 ? (L ^ ((L >> 1) & 1)) : L; }
-    static __device__ __forceinline__ bf16x8_t load(const unsigned char* xs, int k16, int c32, int lane, int kw, int wclog,
-                                                    int xw, int ups, int tx0) {
-        const int g16 = lane >> 4, i16 = lane & 15;
-        const int cbase = c32 + 16 * (g16 & 1), p = 16 * k16 + 8 * (g16 >> 1) + (i16 >> 2), q = i16 & 3;
-        const int r = p >> wclog, j = p & ((1 << wclog) - 1);
-        // (behind a nearest x2 upsample the segment holds LOW-resolution pixels: column (ox0 + j + kw + tx0) >> 1, ox0 even)
-        const int col = ups ? ((j + kw + tx0) >> 1) - (tx0 >> 1) : SX * j + kw;
-        // pixel p + 4: four columns on in the same output row (Wc >= 8), or the next output row (Wc = 4)
-        const int L0 = r * xw + col, L1 = L0 + (wclog == 2 ? xw : (ups ? 2 : 4 * SX));
-        const int c0 = (cbase >> 3) ^ swz(L0), c1 = (cbase >> 3) ^ swz(L1);
-        typedef __attribute__((address_space(3))) s16x4_t* lptr;
-        s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(xs + slot(L0) * 128 + c0 * 16 + q * 8));
-        s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(xs + slot(L1) * 128 + c1 * 16 + q * 8));
-        bf16x8_t v;
-        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-        v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-        return v;
-    }
-};
-
-// One kernel row per workgroup, one wave per tap column.  (All kernel rows per workgroup -- nine waves for a 3x3 conv,
-// the dy slice shared by the nine taps -- measured SLOWER almost everywhere: ResBlock 128 x 128 58.9 -> 71.4 us, 64 x 64
-// 29.5 -> 42.3, upsample4 54.5 -> 68.9; only the 256 px upBlock gained, 183.6 -> 156.8; removed.)
-template <int KW, int XB> struct WgRowCfg {         // XB: 8-row DMA blocks of one x segment
-    static constexpr int LPS = (4 + XB + KW - 1) / KW;           // DMA instructions per wave per stage
-    static constexpr int STAGE = LPS * KW * 1024;
-};
-
-template <int KW, int SX, int XB, int D>
-__global__ __launch_bounds__(64 * KW, 2) void wgrad_row_dma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
-                                                                float* __restrict__ dw, const sba_conv_geom g, const int M,
-                                                                const int chunks_per_split, const int use_atomic,
-                                                                const FastDiv dsub, const FastDiv dow, const int64_t zstride,
-                                                                const int wclog) {
-    constexpr int LPS = WgRowCfg<KW, XB>::LPS, STAGE = WgRowCfg<KW, XB>::STAGE;
-    extern __shared__ __attribute__((aligned(1024))) unsigned char wg_lds[];
-
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kw = wv;                                      // this wave's tap column
-    const int co0 = blockIdx.x * 64;
-    const int ci_tiles = g.Cin / 64;
-    const int kh = blockIdx.y / ci_tiles;                   // the workgroup's kernel row
-    const int ci0 = (blockIdx.y - kh * ci_tiles) * 64;
-    const int tap = kh * KW + kw;
-    // taps are row-structured (checked by the host): row kh starts at (ty0, tx0) = (g.ty[kh KW], g.tx[kh KW])
-    int ty0 = 0, tx0 = 0;
-#pragma unroll
-    for (int t = 0; t < SBA_MAX_TAPS; ++t) {
-        if (t == kh * KW) { ty0 = g.ty[t]; tx0 = g.tx[t]; }
-    }
-    const int ups = g.ups;            // (KW = 3, SX = 1 only) x is the LOW-resolution input of a nearest x2 upsample
-    const int Wc = 1 << wclog, R = 32 >> wclog, XW = ups ? (Wc >> 1) + 2 : SX * (Wc - 1) + KW, XR = R * XW;
-    const int sub = g.OH * g.OW;
-
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)wg_lds;
-    const uint32_t x_bytes = (uint32_t)((int64_t)g.N * g.IH * g.IW * g.Cin * 2);
-    const uint32_t dy_bytes = (uint32_t)((int64_t)g.N * g.OH * g.OW * g.Cout * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, dy_bytes, 0x00020000);
-    constexpr uint32_t OOB = 0xFFFFFFFFu;
-
-    // lane l of a DMA instruction fills 16-byte position (l & 7) of row (l >> 3) of its 8-row block
-    const int rsub = lane >> 3;
-    const int cgx = (lane & 7) ^ WgFragRow<SX>::swz(rsub);              // x rows (8-row blocks: swz(L) = swz(L & 7))
-    const int cgd = (lane & 7) ^ (((lane >> 4) & 1) << 2);              // dy rows: as in wgrad_small_dma_kernel
-    const uint32_t x_coff = (uint32_t)(ci0 + cgx * 8) * 2u, d_coff = (uint32_t)(co0 + cgd * 8) * 2u;
-    const uint32_t x_pix = (uint32_t)g.Cin * 2u, d_pix = (uint32_t)g.Cout * 2u;
-    // this wave's blocks b = kw + KW i.  b < 4: rows 8 b .. of the dy slice (role 0: rr = pixel of the chunk);
-    // 4 <= b < 4 + XB: rows of the x segment (role 1: rr / rc = input row / column relative to the chunk's first pixel);
-    // else a dummy that zero-fills its block (role 2)
-    // (a 4 x 4 map has 16 pixels: a chunk then spans rows_img = OH rows of each of 32 / 16 = 2 images)
-    const int rows_img = g.OH < R ? g.OH : R;
-    int role[LPS], rr[LPS], rc[LPS], rn[LPS];
-#pragma unroll
-    for (int i = 0; i < LPS; ++i) {
-        const int b = wv + KW * i;
-        role[i] = 2; rr[i] = 0; rc[i] = 0; rn[i] = 0;
-        if (b < 4) { role[i] = 0; rr[i] = 8 * b + rsub; }
-        else if (b < 4 + XB) {
-            const int L = WgFragRow<SX>::slot(8 * (b - 4) + rsub);      // the segment row this LDS row holds
-            if (L < XR) {
-                const int r = L / XW;
-                role[i] = 1;
-                rn[i] = r / rows_img;
-                rr[i] = (r - rn[i] * rows_img) * g.sy + ty0;           // (ups: an offset in UPSAMPLED rows)
-                rc[i] = ups ? L - r * XW : L - r * XW + tx0;            // (ups: the segment's low-resolution column index)
-            }
-        }
-    }
-
-    const int chunk_lo = blockIdx.z * chunks_per_split;
-    const int chunk_hi = min(chunk_lo + chunks_per_split, M >> 5);
-    int g_ck = chunk_lo;
-
-    auto issue = [&](const uint32_t dst) {
-        const bool live = g_ck < chunk_hi;
-        const int m0 = g_ck * 32;
-        const int n = (int)fdiv(m0, dsub), rem = m0 - n * sub;
-        const int oy0 = (int)fdiv(rem, dow), ox0 = rem - oy0 * g.OW;
-        const int iy0 = oy0 * g.sy, ix0 = ox0 * g.sx;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) {
-            uint32_t off = OOB;
-            if (role[i] == 0) {
-                if (live) off = (uint32_t)(m0 + rr[i]) * d_pix + d_coff;
-                lds_dma16(dr, off, 0u, dst + (uint32_t)((wv + KW * i) * 1024));
-            } else {
-                int iy = iy0 + rr[i], ix = ix0 + rc[i];
-                if (ups) {              // upsampled row v -> low-resolution row v >> 1 (v = -1 and v = 2 IH are the padding)
-                    iy >>= 1;
-                    ix = ((ox0 + tx0) >> 1) + rc[i];
-                }
-                const bool ok = live & (role[i] == 1) & (iy >= 0) & (iy < g.IH) & (ix >= 0) & (ix < g.IW);
-                if (ok) off = (uint32_t)(((n + rn[i]) * g.IH + iy) * g.IW + ix) * x_pix + x_coff;
-                lds_dma16(xr, off, 0u, dst + (uint32_t)((wv + KW * i) * 1024));
-            }
-        }
-        ++g_ck;
-    };
-
-    f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    int islot = 0;
-#pragma unroll
-    for (int p = 0; p < D - 1; ++p) { issue(lds_base + (uint32_t)(islot * STAGE)); ++islot; }
-    if (islot == D) islot = 0;
-    int cslot = 0;
-    for (int ck = chunk_lo; ck < chunk_hi; ++ck) {
-        wait_vmcnt<(D - 2) * LPS>();         // this wave's part of stage ck has landed ...
-        wg_barrier();                        // ... and everybody else's; nobody reads slot (ck - 1) % D any more
-        issue(lds_base + (uint32_t)(islot * STAGE));
-        if (++islot == D) islot = 0;
-        const unsigned char* st = wg_lds + cslot * STAGE;
-        const unsigned char* xs = st + 4 * 1024;
-#pragma unroll
-        for (int k16 = 0; k16 < 2; ++k16) {
-            bf16x8_t a[2], b[2];
-            b[0] = WgFragRow<SX>::load(xs, k16, 0, lane, kw, wclog, XW, ups, tx0);
-            b[1] = WgFragRow<SX>::load(xs, k16, 32, lane, kw, wclog, XW, ups, tx0);
-            a[0] = WgFragDma::load(st, k16, 0, lane);
-            a[1] = WgFragDma::load(st, k16, 32, lane);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        if (++cslot == D) cslot = 0;
-    }
-    wait_vmcnt<0>();            // the dead stages issued past the end still write (zeros) into the ring
-    wg_barrier();
-
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                const int ci = ci0 + j * 32 + col_l;
-                float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-                if (use_atomic == 1) atomicAdd(p, acc[i][j][r]);
-                else if (use_atomic == 2) *p = acc[i][j][r];       // first write of a cleared gradient
-                else *p += acc[i][j][r];
-            }
-}
-
-// ---------------------------------------------------------------------------
-// weight gradient, large-map 3x3 stride-1 convs (optionally over a nearest-x2 upsampled input)
-// with OW % 64 == 0: the generator's 64..256 px layers, where ~all wgrad FLOPs are.
-// A workgroup owns one 64(co) x 64(ci) tile for ALL nine taps: per 64-pixel segment of an output
-// row it stages the dy tile once and, per kernel row kh, ONE input row with a 1-pixel halo
-// (66 x 64 channels); the three kw taps are the same LDS rows read at a +kw row offset, so each
-// input pixel is fetched once per kh instead of once per tap.  Wave kh (3 waves) accumulates its
-// three taps (192 accumulator registers) over the workgroup's whole pixel range, then adds them
-// to dw with f32 atomics.
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(192) void wgrad_rows_kernel(const T* __restrict__ x, const T* __restrict__ dy,
-                                                         float* __restrict__ dw, const sba_conv_geom g,
-                                                         const int total_segs, const int segs_per_wg,
-                                                         const int store, const int64_t zstride) {
-    constexpr int ROWS = WgFrag<T>::ROWS;
-    constexpr int CH = 16 / (int)sizeof(T);
-    constexpr int CPR = 64 / CH;                       // 16-byte chunks per 64-channel pixel row
-    constexpr int XR = 66;                             // 64 pixels + halo
-    constexpr int XROWS_ALLOC = 80;                    // rows reserved per x tile (>= 64 + 2 + 15 read slack)
-    __shared__ __attribute__((aligned(16))) unsigned char lds[(64 + 3 * XROWS_ALLOC) * ROWS];
-
-    const int tid = threadIdx.x, lane = tid & 63, kh = tid >> 6;
-    const int co0 = blockIdx.x * 64, ci0 = blockIdx.y * 64;
-    const int IHL = g.ups ? 2 * g.IH : g.IH, IWL = g.ups ? 2 * g.IW : g.IW;
-    const int segs_per_row = g.OW / 64;
-    unsigned char* sa = lds;
-    unsigned char* sx = lds + (64 + kh * XROWS_ALLOC) * ROWS;
-
-    // rows 66..79 of the x tile are only ever read by discarded k positions? no: every read row
-    // index is < 16*3 + 2 + 16 = 66, so the slack rows are never touched; zero them once anyway
-    for (int i = lane; i < (XROWS_ALLOC - XR) * ROWS / 16; i += 64)
-        *reinterpret_cast<uint4*>(sx + XR * ROWS + i * 16) = make_uint4(0, 0, 0, 0);
-
-    f32x16_t acc[3][2][2];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][i][j][r] = 0.f;
-
-    const int seg_lo = blockIdx.z * segs_per_wg;
-    const int seg_hi = min(seg_lo + segs_per_wg, total_segs);
-    constexpr int A_PT = (64 * CPR + 191) / 192;
-    constexpr int X_PT = (XR * CPR + 63) / 64;
-    uint4 va[A_PT], vx[X_PT];
-    auto gload = [&](int seg) {
-        const int n = seg / (g.OH * segs_per_row);
-        const int rem = seg - n * g.OH * segs_per_row;
-        const int oy = rem / segs_per_row, ox0 = (rem - oy * segs_per_row) * 64;
-#pragma unroll
-        for (int u = 0; u < A_PT; ++u) {
-            const int idx = tid + 192 * u;
-            va[u] = make_uint4(0, 0, 0, 0);
-            if (idx < 64 * CPR) {
-                const int pix = idx / CPR, cc = idx - pix * CPR;
-                const int co = co0 + cc * CH;
-                if (co < g.Cout) {
-                    const int64_t po = ((int64_t)(n * g.OH + oy) * g.OW + ox0 + pix);
-                    va[u] = *reinterpret_cast<const uint4*>(dy + po * g.Cout + co);
-                }
-            }
-        }
-        int iy = oy + kh - 1;
-        const bool row_ok = (iy >= 0) & (iy < IHL);
-        if (g.ups) iy >>= 1;
-#pragma unroll
-        for (int u = 0; u < X_PT; ++u) {
-            const int idx = lane + 64 * u;
-            vx[u] = make_uint4(0, 0, 0, 0);
-            if (idx < XR * CPR) {
-                const int j = idx / CPR, cc = idx - j * CPR;
-                int ix = ox0 - 1 + j;
-                const bool ok = row_ok & (ix >= 0) & (ix < IWL);
-                if (g.ups) ix >>= 1;
-                const int ci = ci0 + cc * CH;
-                if (ok && ci < g.Cin) {
-                    const int64_t pi = (int64_t)(n * g.IH + iy) * g.IW + ix;
-                    vx[u] = *reinterpret_cast<const uint4*>(x + pi * g.Cin + ci);
-                }
-            }
-        }
-    };
-    if (seg_lo < seg_hi) gload(seg_lo);
-    for (int seg = seg_lo; seg < seg_hi; ++seg) {
-        __syncthreads();        // previous segment's tiles fully consumed
-#pragma unroll
-        for (int u = 0; u < A_PT; ++u) {
-            const int idx = tid + 192 * u;
-            if (idx < 64 * CPR) {
-                const int pix = idx / CPR, cc = idx - pix * CPR;
-                *reinterpret_cast<uint4*>(sa + pix * ROWS + cc * 16) = va[u];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < X_PT; ++u) {
-            const int idx = lane + 64 * u;
-            if (idx < XR * CPR) {
-                const int j = idx / CPR, cc = idx - j * CPR;
-                *reinterpret_cast<uint4*>(sx + j * ROWS + cc * 16) = vx[u];
-            }
-        }
-        __syncthreads();
-        if (seg + 1 < seg_hi) gload(seg + 1);     // prefetch the next segment under the 48 MFMAs below
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-                WgFrag<T>::mma(sa + 16 * ks * ROWS, sx + (16 * ks + kw) * ROWS, lane, acc[kw]);
-        }
-    }
-
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-        const int tap = kh * 3 + kw;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                    const int ci = ci0 + j * 32 + col_l;
-                    if (co < g.Cout && ci < g.Cin) {
-                        float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * 9 + tap) * g.Cin + ci;
-                        if (store) *p = acc[kw][i][j][r];       // deterministic mode: this split's own partial tensor
-                        else atomicAdd(p, acc[kw][i][j][r]);
-                    }
-                }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// weight packing and 2x2 sum pooling
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ out, int Cout, int KH,
-                                   int KW, int Cin, int mode) {
-    const int64_t n = (int64_t)Cout * (mode == 3 ? 16 : KH * KW) * Cin;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        // i indexes the OUTPUT (so that writes are coalesced)
-        float v;
-        if (mode == 0) {
-            v = w[i];
-        } else if (mode == 1) {
-            // out[ci][kh'][kw'][co] = w[co][KH-1-kh'][KW-1-kw'][ci]
-            const int co = (int)(i % Cout);
-            int64_t t = i / Cout;
-            const int kw = (int)(t % KW); t /= KW;
-            const int kh = (int)(t % KH);
-            const int ci = (int)(t / KH);
-            v = w[(((int64_t)co * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)) * Cin + ci];
-        } else if (mode == 3) {
-            // data-gradient of (nearest x2 -> conv3x3) as ONE 4x4 stride-2 pad-1 conv over dy:
-            // out[ci][dd*4+ee][co] = sum_{kh in S(dd)} sum_{kw in S(ee)} w[co][kh][kw][ci],
-            // S(0) = {2}, S(1) = {1,2}, S(2) = {0,1}, S(3) = {0}
-            const int co = (int)(i % Cout);
-            int64_t t = i / Cout;
-            const int sl = (int)(t % 16);
-            const int ci = (int)(t / 16);
-            const int dd = sl >> 2, ee = sl & 3;
-            const int kh0 = dd == 0 ? 2 : (dd == 1 ? 1 : 0), khn = (dd == 1 || dd == 2) ? 2 : 1;
-            const int kw0 = ee == 0 ? 2 : (ee == 1 ? 1 : 0), kwn = (ee == 1 || ee == 2) ? 2 : 1;
-            v = 0.f;
-            for (int a = 0; a < khn; ++a)
-                for (int b2 = 0; b2 < kwn; ++b2)
-                    v += w[(((int64_t)co * 3 + kh0 + a) * 3 + kw0 + b2) * Cin + ci];
-        } else {
-            // out[cls][ci][j*2+i2][co], cls = py*2+px, kh = (1-py)+2j, kw = (1-px)+2*i2  (KH=KW=4)
-            const int co = (int)(i % Cout);
-            int64_t t = i / Cout;
-            const int tp = (int)(t % 4); t /= 4;
-            const int ci = (int)(t % Cin);
-            const int cls = (int)(t / Cin);
-            const int py = cls >> 1, px = cls & 1, j = tp >> 1, i2 = tp & 1;
-            const int kh = (1 - py) + 2 * j, kw = (1 - px) + 2 * i2;
-            v = w[(((int64_t)co * 4 + kh) * 4 + kw) * Cin + ci];
-        }
-        out[i] = from_f<T>(v);
-    }
-}
-
-// modes 1 / 2 as tiled transposes: for one (source tap -> destination tap) pair the job is
-// out[ci][co] = w[co][ci] with row strides of taps*Cin resp. dtaps*Cout; 32x32 tiles through LDS
-// keep both the global reads (along ci) and writes (along co) coalesced.
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weight_tr_kernel(const float* __restrict__ w, T* __restrict__ out,
-                                                             int Cout, int KH, int KW, int Cin, int mode) {
-    __shared__ float tile[32][33];
-    const int z = blockIdx.z;
-    int src_tap, dst_tap, dtaps;
-    int64_t dst_base = 0;
-    if (mode == 1) {
-        const int kh = z / KW, kw = z - kh * KW;
-        dst_tap = z;
-        src_tap = (KH - 1 - kh) * KW + (KW - 1 - kw);
-        dtaps = KH * KW;
-    } else {
-        const int cls = z >> 2, tp = z & 3;
-        const int py = cls >> 1, px = cls & 1, j = tp >> 1, i2 = tp & 1;
-        src_tap = ((1 - py) + 2 * j) * 4 + (1 - px) + 2 * i2;
-        dst_tap = tp;
-        dtaps = 4;
-        dst_base = (int64_t)cls * Cin * 4 * Cout;
-    }
-    const int taps = KH * KW;
-    const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
-#pragma unroll
-    for (int r = ty; r < 32; r += 8) {
-        const int co = co0 + r, ci = ci0 + tx;
-        tile[r][tx] = (co < Cout && ci < Cin) ? w[((int64_t)co * taps + src_tap) * Cin + ci] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = ty; r < 32; r += 8) {
-        const int ci = ci0 + r, co = co0 + tx;
-        if (ci < Cin && co < Cout) out[dst_base + ((int64_t)ci * dtaps + dst_tap) * Cout + co] = from_f<T>(tile[tx][r]);
-    }
-}
-
-// every packed copy of one network in one launch: a workgroup owns one 64(co) x 64(ci) tile of one
-// source tap of one tensor, reads it once (float4 rows), writes the forward copy (same order) and
-// the transposed data-gradient copy (64 co contiguous = full 128-byte lines) through LDS
-template <typename T>
-__global__ __launch_bounds__(256) void pack_multi_kernel(const sba_pack_desc* __restrict__ descs, int ndesc) {
-    __shared__ float tile[64][65];
-    int lo = 0, hi = ndesc - 1;
-    const int b = blockIdx.x;
-    while (lo < hi) {                                   // last desc with tile_begin <= b (uniform)
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].tile_begin <= b) lo = mid; else hi = mid - 1;
-    }
-    const sba_pack_desc d = descs[lo];
-    const int local = b - d.tile_begin;
-    const int per_tap = d.co_tiles * d.ci_tiles;
-    const int src_tap = local / per_tap;                 // mode 3: the destination tap slot (0..15)
-    const int rem = local - src_tap * per_tap;
-    const int co0 = (rem / d.ci_tiles) * 64, ci0 = (rem % d.ci_tiles) * 64;
-    const int taps = d.KH * d.KW;
-    const int slots = d.mode == 3 ? 16 : taps;
-    if (src_tap >= slots) return;
-    const int tid = threadIdx.x;
-    const int c4 = (tid & 15) * 4;
-    T* fwd = reinterpret_cast<T*>(d.fwd);
-    // mode 3 (data-gradient of nearest x2 -> conv3x3 as one 4x4/s2 conv): slot (dd, ee) sums the source
-    // taps kh in S(dd), kw in S(ee);  S(0) = {2}, S(1) = {1,2}, S(2) = {0,1}, S(3) = {0}
-    int kh0 = 0, khn = 1, kw0 = 0, kwn = 1;
-    if (d.mode == 3) {
-        const int dd = src_tap >> 2, ee = src_tap & 3;
-        kh0 = dd == 0 ? 2 : (dd == 1 ? 1 : 0); khn = (dd == 1 || dd == 2) ? 2 : 1;
-        kw0 = ee == 0 ? 2 : (ee == 1 ? 1 : 0); kwn = (ee == 1 || ee == 2) ? 2 : 1;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (tid >> 4) + 16 * i;
-        const int co = co0 + r, ci = ci0 + c4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (co < d.Cout && ci < d.Cin) {
-            if (d.mode != 3 || src_tap < taps) {           // forward copy of source tap `src_tap`
-                const int64_t o = ((int64_t)co * taps + src_tap) * d.Cin + ci;
-                const float4 f = *reinterpret_cast<const float4*>(d.w + o);
-                if (fwd) {
-                    fwd[o] = from_f<T>(f.x); fwd[o + 1] = from_f<T>(f.y);
-                    fwd[o + 2] = from_f<T>(f.z); fwd[o + 3] = from_f<T>(f.w);
-                }
-                if (d.mode != 3) v = f;
-            }
-            if (d.mode == 3) {
-                for (int a = 0; a < khn; ++a)
-                    for (int b2 = 0; b2 < kwn; ++b2) {
-                        const float4 f = *reinterpret_cast<const float4*>(
-                            d.w + ((int64_t)co * 9 + (kh0 + a) * 3 + kw0 + b2) * d.Cin + ci);
-                        v.x += f.x; v.y += f.y; v.z += f.z; v.w += f.w;
-                    }
-            }
-        }
-        tile[r][c4] = v.x; tile[r][c4 + 1] = v.y; tile[r][c4 + 2] = v.z; tile[r][c4 + 3] = v.w;
-    }
-    if (!d.tr) return;
-    __syncthreads();
-    int dst_tap, dtaps;
-    int64_t dst_base = 0;
-    if (d.mode == 1) {
-        const int kh = src_tap / d.KW, kw = src_tap - kh * d.KW;
-        dst_tap = (d.KH - 1 - kh) * d.KW + (d.KW - 1 - kw);
-        dtaps = taps;
-    } else if (d.mode == 3) {
-        dst_tap = src_tap;
-        dtaps = 16;
-    } else {
-        const int kh = src_tap >> 2, kw = src_tap & 3;      // kh = (1-py) + 2j, kw = (1-px) + 2i
-        const int py = 1 - (kh & 1), px = 1 - (kw & 1);
-        dst_tap = (kh >> 1) * 2 + (kw >> 1);
-        dtaps = 4;
-        dst_base = (int64_t)(py * 2 + px) * d.Cin * 4 * d.Cout;
-    }
-    T* tr = reinterpret_cast<T*>(d.tr);
-    const int c8 = (tid & 7) * 8;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int r = (tid >> 3) + 32 * i;                  // ci within the tile
-        const int ci = ci0 + r, co = co0 + c8;
-        if (ci >= d.Cin || co >= d.Cout) continue;
-        T* op = tr + dst_base + ((int64_t)ci * dtaps + dst_tap) * d.Cout + co;
-        if (co + 8 <= d.Cout && sizeof(T) == 2) {
-            uint4 o;
-            o.x = (uint32_t)f2bf(tile[c8 + 0][r]) | ((uint32_t)f2bf(tile[c8 + 1][r]) << 16);
-            o.y = (uint32_t)f2bf(tile[c8 + 2][r]) | ((uint32_t)f2bf(tile[c8 + 3][r]) << 16);
-            o.z = (uint32_t)f2bf(tile[c8 + 4][r]) | ((uint32_t)f2bf(tile[c8 + 5][r]) << 16);
-            o.w = (uint32_t)f2bf(tile[c8 + 6][r]) | ((uint32_t)f2bf(tile[c8 + 7][r]) << 16);
-            *reinterpret_cast<uint4*>(op) = o;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (co + k < d.Cout) op[k] = from_f<T>(tile[c8 + k][r]);
-        }
-    }
-}
-
-template <typename T>
-__global__ void pool2x2_kernel(const T* __restrict__ up, T* __restrict__ dx, int N, int H, int W, int C) {
-    constexpr int V = Vec16<T>::N;
-    const int cv = C / V;
-    const int64_t total = (int64_t)N * H * W * cv;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % cv) * V;
-        int64_t p = i / cv;
-        const int xx = (int)(p % W); p /= W;
-        const int yy = (int)(p % H);
-        const int n = (int)(p / H);
-        const T* b = up + (((int64_t)n * 2 * H + 2 * yy) * 2 * W + 2 * xx) * C + c;
-        Vec16<T> v00 = ld16(b), v01 = ld16(b + C), v10 = ld16(b + (int64_t)2 * W * C),
-                 v11 = ld16(b + (int64_t)2 * W * C + C), o;
-#pragma unroll
-        for (int k = 0; k < V; ++k) o.set(k, v00.get(k) + v01.get(k) + v10.get(k) + v11.get(k));
-        st16(dx + (((int64_t)n * H + yy) * W + xx) * C + c, o);
-    }
-}
-
 // split-K finish: y[pix(m)][co] = ws[m][co] (+ addend), per-channel stats; thread = 4 channels x 8 rows
 template <typename T>
 __device__ __forceinline__ void splitk_finish_body(float* __restrict__ ws, T* __restrict__ y,
@@ -3017,31 +1944,6 @@ int launch_igemm(const void* x, const void* w, void* y, const void* addend, floa
     }
 }
 
-bool geom_ok(const sba_conv_geom* g, int dtype) {
-    if (!g) return false;
-    const int ks = dtype == SBA_BF16 ? 32 : 16;
-    if (g->ntaps < 1 || g->ntaps > SBA_MAX_TAPS) return false;
-    for (int t = 0; t < g->ntaps; ++t)
-        if (g->ty[t] < -8 || g->ty[t] > 7 || g->tx[t] < -8 || g->tx[t] > 7) return false;
-    if (g->Cin <= 0 || g->Cin % ks != 0) return false;
-    if (g->N <= 0 || g->IH <= 0 || g->IW <= 0 || g->OH <= 0 || g->OW <= 0 || g->Cout <= 0) return false;
-    if (g->OHs <= 0 || g->OWs <= 0 || g->osy <= 0 || g->osx <= 0) return false;
-    // every written output pixel must lie inside OH x OW
-    if ((g->OHs - 1) * g->osy + g->ooy >= g->OH || (g->OWs - 1) * g->osx + g->oox >= g->OW) return false;
-    if (g->ooy < 0 || g->oox < 0) return false;
-    if ((int64_t)g->N * g->OHs * g->OWs > 0x7fffffff) return false;
-    const int64_t esz = dtype == SBA_BF16 ? 2 : 4;
-    const int vec = dtype == SBA_BF16 ? 8 : 4;
-    const int xcs = g->x_cstride ? g->x_cstride : g->Cin, ycs = g->y_cstride ? g->y_cstride : g->Cout;
-    if (xcs < g->Cin + g->x_coff || ycs < g->Cout + g->y_coff || g->x_coff < 0 || g->y_coff < 0) return false;
-    if (xcs % vec || g->x_coff % vec || ycs % vec || g->y_coff % vec) return false;
-    if ((int64_t)g->N * g->IH * g->IW * xcs * esz >= ((int64_t)1 << 32)) return false;    // 32-bit byte offsets
-    if ((int64_t)g->Cout * g->ntaps * g->Cin * esz >= ((int64_t)1 << 32)) return false;
-    if ((int64_t)g->N * g->IH * g->IW > 0x7fffffff / 2 || (int64_t)g->N * g->OH * g->OW > 0x7fffffff / 2)
-        return false;
-    return true;
-}
-
 // the launch writes every pixel and channel of a dense [N*OH*OW][Cout] tensor
 bool dense_output(const sba_conv_geom& g) {
     return g.OHs == g.OH && g.OWs == g.OW && g.osy == 1 && g.osx == 1 && g.ooy == 0 && g.oox == 0 &&
@@ -3120,50 +2022,7 @@ bool glu_geom(int dtype, const sba_conv_geom* g, int C, sba_conv_geom* out) {
     return true;
 }
 
-// Fold the eval-mode BatchNorm of a conv (or dense) layer into its weights and pack them for the forward kernels:
-//   out[r][tap][ci] = w[src(r)][tap][ci] * s,  bias[r] = beta - mean * s,  s = gamma / sqrt(var + eps)   (of row src(r))
-// the product in f32, rounded ONCE to the storage type.  glu = 0: src(r) = r.  glu = 1: the O = 2C rows are interleaved in
-// granules of 32 (tile_epilogue_glu): r = 64 b + q -> value channel 32 b + q (q < 32) or gate channel C + 32 b + q - 32;
-// rows of channels >= C are zero.
-template <typename T>
-__global__ __launch_bounds__(256) void fold_bn_pack_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ mean,
-                                                           const float* __restrict__ var, const float eps,
-                                                           T* __restrict__ out, float* __restrict__ bias, const int O,
-                                                           const int rowlen, const int glu, const int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int r = (int)(i / rowlen), k = (int)(i - (int64_t)r * rowlen);
-        int src = r;
-        if (glu) {
-            const int C = O / 2, q = r & 63, c = (r >> 6) * 32 + (q & 31);
-            src = c < C ? c + (q >= 32 ? C : 0) : -1;
-        }
-        float v = 0.f, b = 0.f;
-        if (src >= 0) {
-            const float s = gamma[src] / sqrtf(var[src] + eps);
-            v = w[(int64_t)src * rowlen + k] * s;
-            b = beta[src] - mean[src] * s;
-        }
-        out[i] = from_f<T>(v);
-        if (k == 0) bias[r] = b;
-    }
-}
-
 }  // namespace
-
-extern "C" int sba_fold_bn_pack(int dtype, const float* w, const float* gamma, const float* beta,
-                                const float* running_mean, const float* running_var, float eps, void* out, float* bias,
-                                int O, int taps, int Cin, int glu, void* stream) {
-    if (!w || !gamma || !beta || !running_mean || !running_var || !out || !bias) return SBA_E_ARG;
-    if (O <= 0 || taps <= 0 || Cin <= 0 || (glu && O % 2)) return SBA_E_ARG;
-    const int rows = glu ? 64 * ((O / 2 + 31) / 32) : O;
-    const int64_t n = (int64_t)rows * taps * Cin;
-    if ((int64_t)taps * Cin > 0x7fffffff) return SBA_E_ARG;
-    const int blocks = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-    SBA_DISPATCH(dtype, SBA_LAUNCH((fold_bn_pack_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, gamma,
-                                   beta, running_mean, running_var, eps, (T*)out, bias, O, taps * Cin, glu, n));
-    return SBA_CHECK_LAUNCH();
-}
 
 extern "C" int sba_conv_igemm_glu(int dtype, const void* x, const void* w, const float* bias, void* y, int C,
                                   const sba_conv_geom* g, void* stream) {
@@ -3320,268 +2179,4 @@ extern "C" int sba_conv_igemm_group(int dtype, int n, const sba_conv_group_item*
 extern "C" int sba_conv_igemm_group_splitk(int dtype, int n, const sba_conv_group_item* items, int tile, int ksplit,
                                            void* workspace, int64_t workspace_bytes, void* stream) {
     return group_dispatch(dtype, n, items, tile, ksplit, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* dw, const sba_conv_geom* g,
-                              int ksplit, void* stream) {
-    if (!x || !dy || !dw || !geom_ok(g, dtype)) return SBA_E_ARG;
-    if (g->Cin % 8 != 0 || g->Cout % 8 != 0) return SBA_E_ARG;
-    if (g->x_cstride || g->x_coff || g->y_cstride || g->y_coff || g->ntaps > 16) return SBA_E_ARG;
-    const int M = g->N * g->OHs * g->OWs;
-    if (ksplit < 1) ksplit = 1;
-    const int fw = g->first_write ? 2 : 0;       // epilogue mode of the exclusive-owner kernels: 0 = +=, 1 = atomic, 2 = store
-    const int co_tiles = cdiv(g->Cout, 64), items = cdiv(g->Cin, 64) * g->ntaps;
-    const FastDiv dsub = make_fastdiv((uint32_t)(g->OHs * g->OWs), (int64_t)M + 64);
-    const FastDiv dow = make_fastdiv((uint32_t)g->OWs, (int64_t)M + 64);
-    // Deterministic mode: pixel splits do not meet in f32 atomics -- split z STORES its partial gradient into its own
-    // tensor of the scratch ring (mode 2, offset z * zstride) and sba_det_fold adds the splits up in order.
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t dwn = (int64_t)g->Cout * g->ntaps * g->Cin;
-    float* part = nullptr;
-    auto det_begin = [&](int nsplit) -> bool {
-        part = nullptr;
-        if (sba_det_on() && nsplit > 1) { part = sba_det_alloc((int64_t)nsplit * dwn); return part != nullptr; }
-        return true;
-    };
-    auto det_end = [&](int nsplit) { if (part) sba_det_fold(part, 1, nsplit, dwn, dw, 0, fw == 2 ? 1 : 0, st); };
-    // Kernel-row decomposition (wgrad_row_dma_kernel): the kw taps of a kernel row share one staged input row segment.
-    // 4x4 / stride-2 down blocks, and 3x3 / stride-1 convs on maps of 8 x 8 .. -- also in the all-taps halo-row kernel's
-    // range and behind the nearest x2 upsample (G upsample1..4 73 / 92 / 102 / 80 -> 41 / 56 / 55 / 53 us, upBlock -> 128 px
-    // 123 -> 100, -> 256 px 192 -> 187) -- tools/bench_wgrad.py, B = 20: ResBlock 64 x 64 44.0 -> 28.4 us, 64->128 @64 61.6 -> 38.3; at 128 x 128
-    // against wgrad_rows_kernel: 64->64 95.8 -> 54.9 us, 64->128 122.8 -> 92.8 (profiles/r04_wgrad_s2_rows.txt).
-    // The 4 x 4 maps (two images per chunk) included -- B = 40: D256's 3x3 2048->1024 78.6 -> 55.8 us, D128's 1024->512
-    // 38.1 -> 27.3, 512->1024 4x4/s2 35.8 -> 27.9.
-    {
-        const int kwn = g->ntaps == 16 ? 4 : (g->ntaps == 9 ? 3 : 0), sxy = g->sx;
-        bool ok = dtype == SBA_BF16 && kwn && g->sy == sxy && (!g->ups || kwn == 3) && g->osy == 1 && g->osx == 1 && g->ooy == 0 &&
-                  g->oox == 0 && g->OHs == g->OH && g->OWs == g->OW && g->Cin % 64 == 0 && g->Cout % 64 == 0 &&
-                  g->OW >= 4 && (g->OW & (g->OW - 1)) == 0 && !(g->OW == 4 && (g->ups || g->OH != 4)) && M % 32 == 0 &&
-                  ((g->OH * g->OW) % 32 == 0 || g->OW == 4);
-        ok = ok && ((kwn == 4 && sxy == 2) || (kwn == 3 && sxy == 1));
-        for (int t = 0; t < g->ntaps && ok; ++t)
-            ok = g->ty[t] == g->ty[(t / kwn) * kwn] && g->tx[t] == g->tx[(t / kwn) * kwn] + (t % kwn);
-        const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
-        if (ok && xb < (1ll << 32) && db < (1ll << 32)) {
-            const int wc = g->OW < 32 ? g->OW : 32;
-            int wclog = 0;
-            while ((1 << wclog) < wc) ++wclog;
-            const int wgs = co_tiles * kwn * (g->Cin / 64);
-            const int tc32 = M / 32;
-            // pixel splits: each one adds a full f32-atomic copy of dW (~1.3 TB/s chip-wide): fill the chip about twice,
-            // keep >= 12 chunks behind a copy
-            // (tools/bench_wgrad.py, B = 40: 128->256 @64 71 us at 512 workgroups, 78 at 384, 94 at 256; the 64->128 layers,
-            // 8 workgroups per split: @128 89 / 86 / 94, @64 42 / 37 / 36)
-            constexpr int ROW_WGS = 512;
-            int sp = cdiv(wgs <= 8 ? (ROW_WGS * 3) / 4 : ROW_WGS, wgs);
-            if (sp > tc32 / 12) sp = tc32 / 12 > 0 ? tc32 / 12 : 1;
-            const int cps32 = cdiv(tc32, sp);
-            sp = cdiv(tc32, cps32);
-            dim3 gd(co_tiles, kwn * (g->Cin / 64), sp);
-            if (gd.y <= 65535 && gd.z <= 65535) {
-                if (!det_begin(sp)) return SBA_E_ARG;
-                float* dwa = part ? part : dw;
-                const int md = part ? 2 : (sp > 1 ? 1 : fw);
-                const int64_t zs = part ? dwn : 0;
-                // (ring depth: 3 and 4 measure the same, 6 is 30-60 % slower -- occupancy: profiles/r04_wgrad_s2_rows.txt)
-                if (kwn == 4) {         // x segment: <= 72 rows (OW >= 8), 80 rows (two 4 x 4 maps)
-                    constexpr int LDS = 4 * WgRowCfg<4, 10>::STAGE;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<4, 2, 10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_row_dma_kernel<4, 2, 10, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
-                } else if (g->OW == 4) {       // 8 rows x 6 = 48 rows
-                    constexpr int LDS = 4 * WgRowCfg<3, 6>::STAGE;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<3, 1, 6, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_row_dma_kernel<3, 1, 6, 4>), gd, dim3(192), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
-                } else {                       // <= 40 rows
-                    constexpr int LDS = 4 * WgRowCfg<3, 5>::STAGE;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<3, 1, 5, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_row_dma_kernel<3, 1, 5, 4>), gd, dim3(192), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
-                }
-                det_end(sp);
-                return SBA_CHECK_LAUNCH();
-            }
-        }
-    }
-    constexpr int SMALL_M = 12000;      // small-pixel-count decomposition: output pixels up to this
-    if (M <= SMALL_M && co_tiles * items >= 256) {
-        // GEMM-like layer: one tile per wave, all pixels (ksplit re-derived for this decomposition)
-        const int total_chunks = cdiv(M, 16);
-        const int wgs = co_tiles * cdiv(items, 4);
-        // pixel splits: each one adds a full f32-atomic copy of every 64x64 tile (the atomics run at ~1.3 TB/s),
-        // so split only up to ~3 workgroups per CU and keep >= 24 chunks (384 pixels) of MFMA work behind a copy
-        // (measured on the discriminator shapes: joint conv 68 -> 44 us, s64_2 68 -> 46, c4 166 -> 133)
-        constexpr int SMALL_WGS = 768, SMALL_MINC = 24;
-        int split = wgs >= SMALL_WGS / 2 ? 1 : cdiv(SMALL_WGS, wgs);
-        if (split > total_chunks / SMALL_MINC) split = total_chunks / SMALL_MINC > 0 ? total_chunks / SMALL_MINC : 1;
-        const int cps = cdiv(total_chunks, split);
-        split = cdiv(total_chunks, cps);
-        dim3 grid(co_tiles, cdiv(items, 4), split);
-        if (grid.y > 65535 || grid.z > 65535) return SBA_E_ARG;
-        const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
-        // LDS-DMA ring of depth 4 (tools/bench_wgrad.py, B = 20): 15-25 % faster than the register-staged kernel up to ~512
-        // workgroups (joint conv 29 -> 25 us, D s32 61 -> 50, s32_1 49 -> 37); beyond that the launches are bound by
-        // the L2 traffic of the operand slices either way and the 80 KB ring costs occupancy (s64 145 -> 175 us)
-        constexpr int DMA_WGS = 512;
-        // beyond DMA_WGS: the DMA kernel with TWO co tiles per wave (0.375 KB of operands per MFMA) -- pays once the
-        // epilogue is a plain store (first write: D256 s64 119 -> 95 us, s64_1 89 -> 79, G upsample1 84 -> 72); with the
-        // read-modify-write epilogue it is no faster than the register-staged kernel (148 vs 146 us).
-        if (fw == 2 && wgs > DMA_WGS && g->Cout % 128 == 0 && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
-            const int tc32 = cdiv(M, 32);
-            dim3 gd(co_tiles / 2, cdiv(items, 4), 1);
-            constexpr int LDS = 3 * 6 * 32 * 128;
-            static bool once = false;
-            if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-            SBA_LAUNCH((wgrad_small_dma_kernel<2, 3>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)dy, dw, *g, M, tc32, fw, dsub, dow, (int64_t)0);
-            return SBA_CHECK_LAUNCH();
-        }
-        if (wgs <= DMA_WGS && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
-            // stages of 32 pixels; the same split rule restated in 32-pixel chunks
-            const int tc32 = cdiv(M, 32);
-            int sp = wgs >= SMALL_WGS / 2 ? 1 : cdiv(SMALL_WGS, wgs);
-            constexpr int mc = SMALL_MINC / 2;
-            if (sp > tc32 / mc) sp = tc32 / mc > 0 ? tc32 / mc : 1;
-            const int cps32 = cdiv(tc32, sp);
-            sp = cdiv(tc32, cps32);
-            dim3 gd(co_tiles, cdiv(items, 4), sp);
-            if (gd.z > 65535) return SBA_E_ARG;
-            if (!det_begin(sp)) return SBA_E_ARG;
-            float* dwa = part ? part : dw;
-            const int md = part ? 2 : (sp > 1 ? 1 : fw);
-            const int64_t zs = part ? dwn : 0;
-            constexpr int LDS = 4 * 5 * 32 * 128;
-            static bool once = false;
-            if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-            SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-            det_end(sp);
-            return SBA_CHECK_LAUNCH();
-        }
-        if (!det_begin(split)) return SBA_E_ARG;
-        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_small_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream,
-                                               (const T*)x, (const T*)dy, part ? part : dw, *g, M, cps,
-                                               part ? 2 : (split > 1 ? 1 : fw), dsub, dow, part ? dwn : (int64_t)0));
-        det_end(split);
-        return SBA_CHECK_LAUNCH();
-    }
-    // generator-style 3x3 stride-1 conv on a wide map: all nine taps per workgroup from halo tiles.  From 128x128 maps
-    // up (B = 20: M >= 327 k) it beats the LDS-DMA decomposition below (upBlock -> 256 px 189 vs 349 us); at 64x64
-    // (M = 82 k) the DMA kernel wins (ResBlock 51 -> 40 us, 64->128: 69 -> 60), tools/bench_wgrad.py.
-    constexpr int ROWS_M = 131072;
-    bool rows_ok = g->ntaps == 9 && g->sy == 1 && g->sx == 1 && g->osy == 1 && g->osx == 1 && g->ooy == 0 &&
-                   g->oox == 0 && g->OHs == g->OH && g->OWs == g->OW && g->OW % 64 == 0 && M >= ROWS_M;
-    for (int t = 0; t < 9 && rows_ok; ++t) rows_ok = g->ty[t] == t / 3 - 1 && g->tx[t] == t % 3 - 1;
-    if (rows_ok) {
-        const int total_segs = g->N * g->OH * (g->OW / 64);
-        const int ci_t = cdiv(g->Cin, 64);
-        // every pixel split adds a full copy of the tile's 9 x 64 x 64 outputs to the f32 atomics
-        // (~1.3 TB/s chip-wide), so use few, fat workgroups: ~1 per CU and >= 16 segments each
-        int nz = cdiv(256, co_tiles * ci_t);
-        if (nz > total_segs / 16) nz = total_segs / 16;
-        if (nz < 1) nz = 1;
-        const int spw = cdiv(total_segs, nz);
-        nz = cdiv(total_segs, spw);
-        dim3 grid(co_tiles, ci_t, nz);
-        if (grid.z > 65535) return SBA_E_ARG;
-        // (deterministic mode: also for nz == 1 -- every workgroup's three waves store, nothing adds)
-        part = nullptr;
-        if (sba_det_on()) { part = sba_det_alloc((int64_t)nz * dwn); if (!part) return SBA_E_ARG; }
-        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_rows_kernel<T>), grid, dim3(192), 0, (hipStream_t)stream,
-                                               (const T*)x, (const T*)dy, part ? part : dw, *g, total_segs, spw,
-                                               part ? 1 : 0, part ? dwn : (int64_t)0));
-        det_end(nz);
-        return SBA_CHECK_LAUNCH();
-    }
-    {
-        // Big-M layers that are not 3x3 / OW % 64 == 0 (the discriminators' 4x4/s2 down blocks at 32..128 px): the
-        // register-staged kernel below shares nothing between its waves (1 KB of operands per MFMA from L2 = the
-        // 300 TFLOP/s on-chip-bandwidth roofline of a 64x64 tile); the small-pixel-count decomposition shares the dy
-        // slices between the four (tap, ci tile) items of a workgroup (0.625 KB per MFMA) and walks its pixel split
-        // through the LDS-DMA ring.  Measured (tools/bench_wgrad.py, B = 20): D256 down 64->128 @128 px 200 -> 110 us,
-        // 128->256 @64 193 -> 107, D128 down @64 99 -> 48, D64 down @32 43 -> 24; two co tiles per wave are no better.
-        const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
-        if (dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
-            constexpr int GEN_WGS = 512;
-            const int wgs = co_tiles * cdiv(items, 4);
-            const int tc32 = cdiv(M, 32);
-            int sp = cdiv(GEN_WGS, wgs);
-            if (sp > tc32 / 12) sp = tc32 / 12 > 0 ? tc32 / 12 : 1;
-            const int cps32 = cdiv(tc32, sp);
-            sp = cdiv(tc32, cps32);
-            dim3 gd(co_tiles, cdiv(items, 4), sp);
-            if (gd.y <= 65535 && gd.z <= 65535) {
-                if (!det_begin(sp)) return SBA_E_ARG;
-                float* dwa = part ? part : dw;
-                const int md = part ? 2 : (sp > 1 ? 1 : fw);
-                const int64_t zs = part ? dwn : 0;
-                constexpr int LDS = 4 * 5 * 32 * 128;
-                static bool once = false;
-                if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-                det_end(sp);
-                return SBA_CHECK_LAUNCH();
-            }
-        }
-    }
-    const int total_chunks = cdiv(M, 64);
-    if (ksplit > total_chunks) ksplit = total_chunks;
-    const int cps = cdiv(total_chunks, ksplit);
-    ksplit = cdiv(total_chunks, cps);
-    dim3 grid(co_tiles, items, ksplit);
-    if (grid.y > 65535 || grid.z > 65535) return SBA_E_ARG;
-    if (!det_begin(ksplit)) return SBA_E_ARG;
-    SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream,
-                                           (const T*)x, (const T*)dy, part ? part : dw, *g, M, cps,
-                                           part ? 2 : (ksplit > 1 ? 1 : 0), dsub, dow, part ? dwn : (int64_t)0));
-    det_end(ksplit);
-    return SBA_CHECK_LAUNCH();
-}
-
-extern "C" int sba_pack_weight(int dtype, const float* w, void* out, int Cout, int KH, int KW, int Cin,
-                               int mode, void* stream) {
-    if (!w || !out || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0 || mode < 0 || mode > 3) return SBA_E_ARG;
-    if (mode == 3 && (KH != 3 || KW != 3)) return SBA_E_ARG;
-    if (mode == 2 && (KH != 4 || KW != 4)) return SBA_E_ARG;
-    if (mode == 1 || mode == 2) {
-        dim3 grid(cdiv(Cin, 32), cdiv(Cout, 32), mode == 1 ? KH * KW : 16);
-        if (grid.y > 65535) return SBA_E_ARG;
-        SBA_DISPATCH(dtype, SBA_LAUNCH((pack_weight_tr_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream,
-                                               w, (T*)out, Cout, KH, KW, Cin, mode));
-        return SBA_CHECK_LAUNCH();
-    }
-    const int64_t n = (int64_t)Cout * (mode == 3 ? 16 : KH * KW) * Cin;
-    const int blocks = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-    SBA_DISPATCH(dtype, SBA_LAUNCH((pack_weight_kernel<T>), dim3(blocks), dim3(256), 0,
-                                           (hipStream_t)stream, w, (T*)out, Cout, KH, KW, Cin, mode));
-    return SBA_CHECK_LAUNCH();
-}
-
-extern "C" int sba_pack_weights_multi(int dtype, const sba_pack_desc* descs, int ndesc, int total_tiles,
-                                      void* stream) {
-    if (!descs || ndesc <= 0 || total_tiles <= 0) return SBA_E_ARG;
-    if (((uintptr_t)descs & 7) != 0) return SBA_E_ARG;
-    SBA_DISPATCH(dtype, SBA_LAUNCH((pack_multi_kernel<T>), dim3(total_tiles), dim3(256), 0,
-                                           (hipStream_t)stream, descs, ndesc));
-    return SBA_CHECK_LAUNCH();
-}
-
-extern "C" int sba_pack_frag_multi(const sba_frag_desc* descs, int ndesc, int total_units, void* stream) {
-    if (!descs || ndesc <= 0 || total_units <= 0 || ((uintptr_t)descs & 7) != 0) return SBA_E_ARG;
-    SBA_LAUNCH(pack_frag_kernel, dim3(cdiv(total_units, 256)), dim3(256), 0, (hipStream_t)stream, descs, ndesc, total_units);
-    return SBA_CHECK_LAUNCH();
-}
-
-extern "C" int sba_pool2x2_sum(int dtype, const void* dup, void* dx, int N, int H, int W, int C, void* stream) {
-    if (!dup || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0) return SBA_E_ARG;
-    const int64_t total = (int64_t)N * H * W * (C / (dtype == SBA_BF16 ? 8 : 4));
-    const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    SBA_DISPATCH(dtype, SBA_LAUNCH((pool2x2_kernel<T>), dim3(blocks), dim3(256), 0,
-                                           (hipStream_t)stream, (const T*)dup, (T*)dx, N, H, W, C));
-    return SBA_CHECK_LAUNCH();
 }
