@@ -624,6 +624,19 @@ int sba_bert_sent_head_bwd(const float* dsent, const float* sent, const float* p
 /* y = cast(x) between f32 and dtype, n elements. */
 int sba_cast(int dtype_dst, void* dst, int dtype_src, const void* src, int64_t n, void* stream);
 
+/* R-precision ranking (evaluation; sbagan/rprecision.py).  For every image b < B: the cosine score
+ * dot / max(|a| |c|, eps) of its global code cnn[b] against true_emb[b] (candidate 0) and against the M rows
+ * pool[idx[b][m]] of the split's sentence-embedding pool, all f32, and
+ *     rank[b] = #{ m : NOT (score_m < score_0) }
+ * -- a tie counts against the image, and so does a NaN on either side.  cnn [B][nef], true_emb [B][nef], pool [P][nef]:
+ * row-major, contiguous, 16-byte aligned; idx [B][M] int32 rows of pool, NOT range-checked on the device (may be NULL
+ * when M == 0); rank [B]; scores [B][M + 1] (column 0 = the true caption) or NULL.  One workgroup per image, candidate
+ * rows gathered by index, no intermediate, no atomics, no workspace; the lane partition and reduction order are fixed
+ * and the true score takes the code path of a candidate's, so byte-identical rows give bit-identical scores (a pool row
+ * equal to true_emb[b] is an exact tie).  SBA_E_ARG unless B >= 1, M >= 0, P >= 1, nef % 4 == 0, 4 <= nef <= 1024. */
+int sba_rprec_rank(const float* cnn, const float* true_emb, const float* pool, const int32_t* idx, float eps,
+                   int32_t* rank, float* scores, int B, int M, int nef, int P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 
     python main.py --cfg cfg/bird_style.yml --gpu 0 --data_dir ../data/birds [--manualSeed N]
 
-cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_example(example_filenames.txt)."""
+cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_example(example_filenames.txt).
+--fused_inference and --r_precision R (sampling also writes r_precision.json) are this project's additions."""
 import os
 import sys
 import time
@@ -75,6 +76,7 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
         from trainer import condGANTrainer as make_trainer
     algo = make_trainer(output_dir, dataloader, dataset.n_words, dataset.ixtoword)
     algo.fused_inference = bool(getattr(args, 'fused_inference', False))
+    algo.r_precision = int(getattr(args, 'r_precision', 0))
     start_t = time.time()
     if training:
         algo.train()

@@ -1,6 +1,6 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
-    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--bert_dir DIR: the BERT entry points]
+    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
 reference's evaluation runs are seeded that way), the given one or a random one in training, and every run gets an
@@ -19,6 +19,13 @@ from .config import cfg, cfg_from_file
 EVAL_SEED = 100
 
 
+def _r_precision(text):
+    r = int(text)
+    if r < 0 or r == 1:
+        raise argparse.ArgumentTypeError('R must be 0 (off) or at least 2 candidates per image')
+    return r
+
+
 def options(what, default_cfg, argv=None, bert=False):
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
@@ -28,6 +35,10 @@ def options(what, default_cfg, argv=None, bert=False):
     ap.add_argument('--fused_inference', dest='fused_inference', action='store_true', default=False,
                     help='sampling / gen_example: run the generator through sbagan.infer.FusedGenerator (BatchNorm '
                          'folded into the convs, GLU in the conv epilogue)')
+    ap.add_argument('--r_precision', dest='r_precision', type=_r_precision, default=0, metavar='R',
+                    help='sampling: also rank every generated image among R candidate captions (its own and R - 1 of '
+                         'other classes) with the DAMSM encoders and write r_precision.json; 0 = off, 100 = the '
+                         'AttnGAN paper\'s setting')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

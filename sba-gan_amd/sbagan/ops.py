@@ -1890,3 +1890,57 @@ class LstmBidirTrainFn(torch.autograd.Function):
         db = dG.sum(1)                                             # [2][4H]
         dx = torch.matmul(dG, w_ih).sum(0).view(B, T, -1) if ctx.needs_input_grad[0] else None
         return dx, None, dw_ih, dw_hh, db, db, None, None, None
+
+
+# ----------------------------------------------------------------------------
+# evaluation: R-precision ranking (sbagan/rprecision.py)
+def rprec_rank(cnn, true_emb, pool, idx, eps=1e-8, want_scores=False):
+    """rank[b] = #{ m : NOT (cos(cnn[b], pool[idx[b, m]]) < cos(cnn[b], true_emb[b])) }, cos = dot / max(|a| |c|, eps) in
+    f32 (sba_rprec_rank): ties and NaNs count against the image.  cnn, true_emb [B][nef] and pool [P][nef]: contiguous
+    f32 device tensors, nef % 4 == 0, 4 <= nef <= 1024.  idx [B][M]: int32 rows of pool, either on the HOST (a numpy
+    array or CPU tensor: range-checked there and uploaded, no device sync) or on the device (range-checked with one
+    sync).  Everything is checked before the launch: TypeError for a dtype, ValueError for a shape, a stride or an index
+    out of range.  Returns rank (int32 [B], device), or (rank, scores [B][M + 1], column 0 = the true caption)."""
+    for t in (cnn, true_emb, pool):
+        _need_gpu(t)
+    for name, t in (('cnn', cnn), ('true_emb', true_emb), ('pool', pool)):
+        if t.dtype != torch.float32:
+            raise TypeError('rprec_rank: %s must be float32 (got %s)' % (name, t.dtype))
+        if t.dim() != 2:
+            raise ValueError('rprec_rank: %s must be 2-D (got %s)' % (name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError('rprec_rank: %s must be contiguous' % name)
+        if t.device != cnn.device:
+            raise ValueError('rprec_rank: %s is on %s, cnn on %s' % (name, t.device, cnn.device))
+    if not torch.is_tensor(idx):
+        idx = torch.as_tensor(idx)
+    if idx.dtype != torch.int32:
+        raise TypeError('rprec_rank: idx must be int32 (got %s)' % idx.dtype)
+    B, nef = cnn.shape
+    P = pool.shape[0]
+    if B < 1 or P < 1:
+        raise ValueError('rprec_rank: needs at least one image and one pool row (B = %d, P = %d)' % (B, P))
+    if nef % 4 or not 4 <= nef <= 1024:
+        raise ValueError('rprec_rank: nef must be a multiple of 4 in [4, 1024] (got %d)' % nef)
+    if tuple(true_emb.shape) != (B, nef) or pool.shape[1] != nef:
+        raise ValueError('rprec_rank: true_emb %s / pool %s do not match cnn %s'
+                         % (tuple(true_emb.shape), tuple(pool.shape), tuple(cnn.shape)))
+    if idx.dim() != 2 or idx.shape[0] != B:
+        raise ValueError('rprec_rank: idx must be [B][M] with B = %d (got %s)' % (B, tuple(idx.shape)))
+    if not idx.is_contiguous():
+        raise ValueError('rprec_rank: idx must be contiguous')
+    M = idx.shape[1]
+    if M > 0:
+        lo, hi = int(idx.min()), int(idx.max())          # (a device idx: the one sync of this call)
+        if lo < 0 or hi >= P:
+            raise ValueError('rprec_rank: idx out of range [0, %d): min %d, max %d' % (P, lo, hi))
+    dev = cnn.device
+    if not idx.is_cuda:
+        idx = idx.pin_memory().to(dev, non_blocking=True) if M > 0 else idx.to(dev)
+    elif idx.device != dev:
+        raise ValueError('rprec_rank: idx is on %s, cnn on %s' % (idx.device, dev))
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty((B, M + 1), dtype=torch.float32, device=dev) if want_scores else None
+    call('sba_rprec_rank', _p(cnn), _p(true_emb), _p(pool), _p(idx) if M > 0 else None, float(eps), _p(rank), _p(scores),
+         B, M, nef, P, _stream())
+    return (rank, scores) if want_scores else rank

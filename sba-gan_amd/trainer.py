@@ -13,6 +13,7 @@ What differs, none of it in results:
     error and fails; pass `allow_random_encoders=True` to train against randomly initialised frozen encoders
     (synthetic-data runs and tests).
 """
+import json
 import os
 import time
 
@@ -266,13 +267,44 @@ class condGANTrainer(object):
         cut = ckpt.rfind('.pth')
         return ckpt[:cut] if cut >= 0 else ckpt
 
-    def _generate(self, netG, text_encoder, captions, cap_lens, noise):
-        """fake images of every stage for one caption batch (noise is refilled in place)"""
+    def _generate(self, netG, text_encoder, captions, cap_lens, noise, with_sent=False):
+        """fake images of every stage for one caption batch (noise is refilled in place); with_sent: and the sentence
+        embeddings they were generated from"""
         words_embs, sent_emb = self._encode(text_encoder, captions, cap_lens)
         noise.normal_(0, 1)
         with torch.no_grad():
             fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs, build_mask(captions, words_embs.size(2)))
-        return fake_imgs
+        return (fake_imgs, sent_emb) if with_sent else fake_imgs
+
+    r_precision = 0             # --r_precision R: sampling() also ranks every image among R candidate captions
+    r_precision_seed = 100      # seed of the evaluator's own index generator and of the pool's caption draws
+    r_precision_result = None   # the result dict of the last sampling() with r_precision != 0
+
+    def _load_image_encoder(self):
+        """the DAMSM image encoder beside cfg.TRAIN.NET_E (as build_models finds it), frozen, in eval mode, behind its
+        HIP forward (as define_optimizers wraps it).  Built with the CPU generator forked: its initialisation must not
+        move the state the data loader's shuffle draws from."""
+        from sbagan.inception_hip import InceptionHIP
+        with torch.random.fork_rng(devices=[]):
+            image_encoder = CNN_ENCODER(cfg.TEXT.EMBEDDING_DIM)
+        if cfg.TRAIN.NET_E != '':
+            img_encoder_path = cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder')
+            image_encoder.load_state_dict(torch.load(img_encoder_path, map_location='cpu'))
+            print('Load image encoder from:', img_encoder_path)
+        elif not self.allow_random_encoders:
+            raise RuntimeError('cfg.TRAIN.NET_E is empty: no image encoder to load')
+        for p in image_encoder.parameters():
+            p.requires_grad = False
+        return InceptionHIP(image_encoder.to(self.device).eval())
+
+    def _r_precision_evaluator(self, text_encoder):
+        """sbagan.rprecision.RPrecision over the sentence embeddings of every caption of the sampled split"""
+        from sbagan.rprecision import RPrecision, encode_pool
+        if self.r_precision < 2:
+            raise ValueError('r_precision must be 0 (off) or >= 2 candidates per image (got %d)' % self.r_precision)
+        pool, pool_class = encode_pool(self.data_loader.dataset, lambda c, n: self._encode(text_encoder, c, n),
+                                       self.batch_size, seed=self.r_precision_seed, device=self.device)
+        return RPrecision(self._load_image_encoder(), pool, pool_class, R=self.r_precision, seed=self.r_precision_seed)
 
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
@@ -282,15 +314,27 @@ class condGANTrainer(object):
         out_dir = os.path.join(root, 'valid' if split_dir == 'test' else split_dir)
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
+        evaluator = self._r_precision_evaluator(text_encoder) if self.r_precision else None
         noise = torch.empty(self._noise_shape(self.batch_size), device=self.device)
         made = set()
         for nbatch, data in enumerate(self.data_loader):
             if nbatch % 100 == 0:
                 print('step: ', nbatch)
-            _, captions, cap_lens, _, keys = prepare_data(data)
-            last = self._generate(netG, text_encoder, captions, cap_lens, noise)[-1]
+            _, captions, cap_lens, class_ids, keys = prepare_data(data)
+            fake_imgs, sent_emb = self._generate(netG, text_encoder, captions, cap_lens, noise, with_sent=True)
+            last = fake_imgs[-1]
+            if evaluator is not None:
+                evaluator.update(last, sent_emb, class_ids)
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
+        if evaluator is not None:
+            self.r_precision_evaluator = evaluator
+            res = self.r_precision_result = evaluator.result()
+            print('R-precision (R = %d, %d images): R@1 %.4f  R@5 %.4f  R@10 %.4f  R@1 over %d splits %.4f +- %.4f'
+                  % (res['R'], res['n'], res['r_at_1'], res['r_at_5'], res['r_at_10'], res['splits'],
+                     res['r_at_1_splits_mean'], res['r_at_1_splits_std']))
+            with open(os.path.join(out_dir, 'r_precision.json'), 'w') as f:
+                json.dump(res, f, indent=1, sort_keys=True)
         return out_dir
 
     def gen_example(self, data_dic):
