@@ -637,6 +637,30 @@ int sba_cast(int dtype_dst, void* dst, int dtype_src, const void* src, int64_t n
 int sba_rprec_rank(const float* cnn, const float* true_emb, const float* pool, const int32_t* idx, float eps,
                    int32_t* rank, float* scores, int B, int M, int nef, int P, void* stream);
 
+/* Attention-map overlays (sbagan/visualize.py).
+ * sba_vis_expand: out[i] = M x'[i] M^T for the n maps x [n][a][a] (f32) of one dump in ONE launch.  M [V][a] (f32, 16-byte
+ * aligned) is the resize-then-blur operator built on the host; M == NULL (only with V == a) copies the maps.
+ * x' = x where thresh == NULL, else x * (x > thresh[i]).  Also per map: mn[i] / mx[i] = min / max of out[i], and
+ * conf[i] = sum of the x[i] above 2 thresh[i] (of all of x[i] where thresh == NULL).  One workgroup per map, sequential
+ * f32 FMA chains of length a per product, no workspace, no atomics, fixed reduction order: two launches are bit-identical.
+ * SBA_E_ARG unless 1 <= n <= 65535, 1 <= a <= 128, a <= V <= 1024.
+ * sba_vis_compose: the uint8 HWC canvas [H][W][3] of an overlay image, everything but the caption text, one thread per
+ * pixel.  The canvas is nS blocks stacked vertically, each a colour band of `band` rows above nr rows of V x V tiles;
+ * horizontally nc cells of V + 2 columns (the tile and 2 black columns; the band's colour band_rgb[s][c] = r | g << 8 |
+ * b << 16 fills the whole cell).  W == nc (V + 2), H == nS (band + nr V).  Cell (s, r, c) is desc[s][r][c] = {kind,
+ * image, map, m} (int32) and par[s][r][c] = {lo, den} (f32):
+ *   kind 0 black;  1 image tile: image `image & 65535` of batch `image >> 16` (img0 [n0][3][S0][S0] or img1
+ *   [n1][3][S1][S1], f32 in [-1, 1]) resized to V x V (bilinear, align_corners), byte = trunc(clamp((v + 1) 127.5, 0, 255));
+ *   2 map tile: gray byte = trunc(clamp(255 (E[map] - lo) / den, 0, 255)), 0 when den <= 0, E [nE][V][V] f32;
+ *   3 the map byte pasted over the image byte with the constant 8-bit mask m: t = map m + img (255 - m) + 128,
+ *   ((t >> 8) + t) >> 8.
+ * A cell whose indices are out of range is left black (callers check them on the host). */
+int sba_vis_expand(const float* x, const float* thresh, const float* M, float* out, float* mn, float* mx, float* conf,
+                   int n, int a, int V, void* stream);
+int sba_vis_compose(uint8_t* canvas, int W, int H, int V, int band, int nS, int nr, int nc, const int32_t* desc,
+                    const float* par, const uint32_t* band_rgb, const float* E, int nE, const float* img0, int n0, int S0,
+                    const float* img1, int n1, int S1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

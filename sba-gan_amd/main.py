@@ -3,7 +3,8 @@
     python main.py --cfg cfg/bird_style.yml --gpu 0 --data_dir ../data/birds [--manualSeed N]
 
 cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_example(example_filenames.txt).
---fused_inference and --r_precision R (sampling also writes r_precision.json) are this project's additions."""
+--fused_inference, --r_precision R (sampling also writes r_precision.json) and --attention_maps (the attention-map
+overlay images, sbagan/visualize.py) are this project's additions."""
 import os
 import sys
 import time
@@ -77,6 +78,7 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo = make_trainer(output_dir, dataloader, dataset.n_words, dataset.ixtoword)
     algo.fused_inference = bool(getattr(args, 'fused_inference', False))
     algo.r_precision = int(getattr(args, 'r_precision', 0))
+    algo.attention_maps = bool(getattr(args, 'attention_maps', False))
     start_t = time.time()
     if training:
         algo.train()

@@ -1,6 +1,6 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
-    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--bert_dir DIR: the BERT entry points]
+    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
 reference's evaluation runs are seeded that way), the given one or a random one in training, and every run gets an
@@ -39,6 +39,10 @@ def options(what, default_cfg, argv=None, bert=False):
                     help='sampling: also rank every generated image among R candidate captions (its own and R - 1 of '
                          'other classes) with the DAMSM encoders and write r_precision.json; 0 = off, 100 = the '
                          'AttnGAN paper\'s setting')
+    ap.add_argument('--attention_maps', dest='attention_maps', action='store_true', default=False,
+                    help='write the attention-map overlays (sbagan.visualize): Image/G_*.png and D_*.png in training, '
+                         '<key>/0_s_<i>_a<k>.png from gen_example, Image/attention_maps<step>.png in DAMSM '
+                         'pre-training')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

@@ -6,8 +6,9 @@ Differences from the reference, none of which change a result:
     .tolist(), losses.py:71), and the per-term log strings (losses.py:184,205, five
     .item() syncs) are replaced by a dict of device scalars;
   * words_loss evaluates all B x B (caption, image) pairs in one launch instead of a Python
-    loop over captions, and does not return the per-caption attention maps (they are only
-    used by the PNG visualiser); the third return value is an empty list;
+    loop over captions, and does not return the per-caption attention maps: the third return
+    value is an empty list (the PNG visualiser, their only reader, computes the maps of its
+    <= 8 samples itself: sbagan.visualize.damsm_attention_maps);
   * the same-class mask is built on the host with numpy exactly like the reference
     (losses.py:24-32,73-76) -- it is integer work on `class_ids`, a host array.
 """

@@ -3,7 +3,8 @@
     python pretrain_DAMSM.py --cfg cfg/DAMSM/bird.yml --gpu 0 [--data_dir ...] [--manualSeed N]
 
 train / evaluate / build_models keep the reference's signatures; the per-batch work is sbagan.damsm.DAMSMStep
-(HIP kernels).  The attention-map PNGs of the reference's logging (build_super_images) are out of scope."""
+(HIP kernels).  --attention_maps: the reference's Image/attention_maps<step>.png (sbagan.visualize.build_super_images)
+wherever the interval log line is printed."""
 import os
 import sys
 import time
@@ -28,7 +29,7 @@ def parse_args(argv=None):
 
 
 def train(dataloader, cnn_model, rnn_model, batch_size, labels, optimizer, epoch, ixtoword, image_dir,
-          max_steps=None):
+          max_steps=None, attention_maps=False):
     """pretrain_DAMSM.py:49-130.  `optimizer` is the sbagan.damsm.DAMSMStep that owns the flat parameter buffers
     and the fused Adam (build it once per run, call .set_lr(lr) per epoch like the reference re-creates Adam)."""
     cnn_model.train()
@@ -49,10 +50,40 @@ def train(dataloader, cnn_model, rnn_model, batch_size, labels, optimizer, epoch
                                                   s0 / UPDATE_INTERVAL, s1 / UPDATE_INTERVAL, w0 / UPDATE_INTERVAL,
                                                   w1 / UPDATE_INTERVAL))
             s0 = s1 = w0 = w1 = 0.0
+            if attention_maps:
+                save_attention_maps(cnn_model, rnn_model, imgs[-1], captions, cap_lens, ixtoword,
+                                    '%s/attention_maps%d.png' % (image_dir, step))
             start_time = time.time()
         if max_steps is not None and step + 1 >= max_steps:
             break
     return count
+
+
+def save_attention_maps(cnn_model, rnn_model, imgs, captions, cap_lens, ixtoword, path):
+    """pretrain_DAMSM.py:108-117: the word-to-region maps of (at most) the first 8 samples over their own images.  Both
+    encoders run in eval mode without gradients (no dropout draw, no running-statistic update) and go back to theirs.
+    Unlike the reference, which draws the maps of the training forward itself, this is a SECOND forward of the logged
+    batch, after the optimizer step: the picture shows the updated weights, and every logged interval pays one more
+    forward of 8 samples (the fused training step keeps no attention maps)."""
+    from PIL import Image
+    from sbagan.visualize import build_super_images, damsm_attention_maps
+    n = min(8, imgs.size(0))
+    modes = cnn_model.training, rnn_model.training
+    cnn_model.eval()
+    rnn_model.eval()
+    try:
+        with torch.no_grad():
+            region_features, _ = cnn_model(imgs[:n])
+            if hasattr(rnn_model, 'init_hidden'):
+                words_emb, _ = rnn_model(captions[:n], cap_lens[:n], rnn_model.init_hidden(n))
+            else:
+                words_emb, _ = rnn_model(captions[:n])
+    finally:
+        cnn_model.train(modes[0])
+        rnn_model.train(modes[1])
+    maps = damsm_attention_maps(region_features, words_emb, cap_lens[:n], cfg.TRAIN.SMOOTH.GAMMA1)
+    img_set, _ = build_super_images(imgs[:n], captions[:n], ixtoword, maps, region_features.size(2))
+    Image.fromarray(img_set).save(path)
 
 
 def evaluate(dataloader, cnn_model, rnn_model, batch_size, damsm=None):
@@ -120,7 +151,7 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
         for epoch in range(start_epoch, cfg.TRAIN.MAX_EPOCH):
             damsm.set_lr(lr)
             train(dataloader, image_encoder, text_encoder, batch_size, labels, damsm, epoch, dataset.ixtoword,
-                  image_dir, max_steps=max_steps)
+                  image_dir, max_steps=max_steps, attention_maps=bool(getattr(args, 'attention_maps', False)))
             print('-' * 89)
             if len(dataloader_val) > 0:
                 s_loss, w_loss = evaluate(dataloader_val, image_encoder, text_encoder, batch_size, damsm)

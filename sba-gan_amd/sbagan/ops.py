@@ -1944,3 +1944,123 @@ def rprec_rank(cnn, true_emb, pool, idx, eps=1e-8, want_scores=False):
     call('sba_rprec_rank', _p(cnn), _p(true_emb), _p(pool), _p(idx) if M > 0 else None, float(eps), _p(rank), _p(scores),
          B, M, nef, P, _stream())
     return (rank, scores) if want_scores else rank
+
+
+# ----------------------------------------------------------------------------
+# attention-map overlays (sbagan/visualize.py)
+def _vis_need(name, t, what, dtype, dim):
+    if not torch.is_tensor(t):
+        raise TypeError('%s: %s must be a tensor' % (name, what))
+    _need_gpu(t)
+    if t.dtype != dtype:
+        raise TypeError('%s: %s must be %s (got %s)' % (name, what, dtype, t.dtype))
+    if t.dim() != dim:
+        raise ValueError('%s: %s must be %d-D (got %s)' % (name, what, dim, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError('%s: %s must be contiguous' % (name, what))
+
+
+def vis_expand(maps, M=None, thresh=None):
+    """out[i] = M maps'[i] M^T in f32, all maps in one launch (sba_vis_expand).  maps [n][a][a] and M [V][a]: contiguous
+    f32 device tensors, 1 <= a <= 128, a <= V <= 1024; M None: the maps themselves (V = a).  thresh (optional, [n] f32):
+    maps' = maps * (maps > thresh[i]).  Everything is checked before the launch: TypeError for a dtype, ValueError for
+    a shape, a stride or a size.  Returns (out [n][V][V], stats [3][n] = per-map min and max of out, and conf = the sum of
+    the map's values above 2 thresh[i] (of all of them without thresh))."""
+    _vis_need('vis_expand', maps, 'maps', torch.float32, 3)
+    n, a, a2 = maps.shape
+    if a != a2 or n < 1 or n > 65535 or not 1 <= a <= 128:
+        raise ValueError('vis_expand: maps must be [n][a][a] with 1 <= n <= 65535, 1 <= a <= 128 (got %s)'
+                         % (tuple(maps.shape),))
+    V = a
+    if M is not None:
+        _vis_need('vis_expand', M, 'M', torch.float32, 2)
+        V = M.shape[0]
+        if M.shape[1] != a or not a <= V <= 1024:
+            raise ValueError('vis_expand: M must be [V][a] with a = %d <= V <= 1024 (got %s)' % (a, tuple(M.shape)))
+        if M.device != maps.device:
+            raise ValueError('vis_expand: M is on %s, maps on %s' % (M.device, maps.device))
+        if M.data_ptr() % 16:
+            raise ValueError('vis_expand: M must be 16-byte aligned')
+    if thresh is not None:
+        _vis_need('vis_expand', thresh, 'thresh', torch.float32, 1)
+        if thresh.shape[0] != n or thresh.device != maps.device:
+            raise ValueError('vis_expand: thresh must be [n] = [%d] on %s (got %s on %s)'
+                             % (n, maps.device, tuple(thresh.shape), thresh.device))
+    out = torch.empty((n, V, V), dtype=torch.float32, device=maps.device)
+    stats = torch.empty((3, n), dtype=torch.float32, device=maps.device)
+    call('sba_vis_expand', _p(maps), _p(thresh), _p(M), _p(out), _p(stats[0]), _p(stats[1]), _p(stats[2]), n, a, V,
+         _stream())
+    return out, stats
+
+
+VIS_BLACK, VIS_IMAGE, VIS_MAP, VIS_BLEND = 0, 1, 2, 3
+
+
+def vis_compose(V, band, desc, par, band_rgb, expanded=None, imgs0=None, imgs1=None):
+    """The uint8 HWC canvas of an overlay image, all but its text, in one launch (sba_vis_compose; the layout is
+    described in include/sbagan_hip.h).  desc [nS][nr][nc][4] int32, par [nS][nr][nc][2] f32 and band_rgb [nS][nc] uint32:
+    HOST arrays (numpy), checked here -- kinds, mask values, image and map indices -- and uploaded; expanded [nE][V][V],
+    imgs0 / imgs1 [n][3][S][S]: contiguous f32 device tensors or None.  TypeError for a dtype, ValueError for a shape, a
+    stride or an index, before any launch.  Returns the canvas, a [nS (band + nr V)][nc (V + 2)][3] uint8 device tensor."""
+    import numpy as np
+    desc, par, band_rgb = np.asarray(desc), np.asarray(par), np.asarray(band_rgb)
+    if desc.dtype != np.int32 or par.dtype != np.float32 or band_rgb.dtype != np.uint32:
+        raise TypeError('vis_compose: desc / par / band_rgb must be int32 / float32 / uint32 (got %s / %s / %s)'
+                        % (desc.dtype, par.dtype, band_rgb.dtype))
+    if desc.ndim != 4 or desc.shape[3] != 4:
+        raise ValueError('vis_compose: desc must be [nS][nr][nc][4] (got %s)' % (desc.shape,))
+    nS, nr, nc = desc.shape[:3]
+    if par.shape != (nS, nr, nc, 2) or band_rgb.shape != (nS, nc):
+        raise ValueError('vis_compose: par %s / band_rgb %s do not match desc %s' % (par.shape, band_rgb.shape, desc.shape))
+    V, band = int(V), int(band)
+    if not (1 <= V <= 1024 and 0 <= band <= 4096 and 1 <= nS <= 64 and 1 <= nr <= 8 and 1 <= nc <= 64):
+        raise ValueError('vis_compose: V %d, band %d or the cell grid %s is out of range' % (V, band, desc.shape[:3]))
+    W, H = nc * (V + 2), nS * (band + nr * V)
+    if H > 65535:
+        raise ValueError('vis_compose: the canvas is %d rows high (at most 65535)' % H)
+    dev = None
+    counts = []
+    for what, t in (('expanded', expanded), ('imgs0', imgs0), ('imgs1', imgs1)):
+        if t is None:
+            counts.append(0)
+            continue
+        _vis_need('vis_compose', t, what, torch.float32, 3 if what == 'expanded' else 4)
+        if dev is not None and t.device != dev:
+            raise ValueError('vis_compose: %s is on %s, not on %s' % (what, t.device, dev))
+        dev = t.device
+        if what == 'expanded':
+            if tuple(t.shape[1:]) != (V, V):
+                raise ValueError('vis_compose: expanded must be [nE][%d][%d] (got %s)' % (V, V, tuple(t.shape)))
+        elif t.shape[1] != 3 or t.shape[2] != t.shape[3] or not 1 <= t.shape[2] <= 4096:
+            raise ValueError('vis_compose: %s must be [n][3][S][S] (got %s)' % (what, tuple(t.shape)))
+        if not 1 <= t.shape[0] <= 65535:
+            raise ValueError('vis_compose: %s holds %d entries' % (what, t.shape[0]))
+        counts.append(t.shape[0])
+    if dev is None:
+        raise ValueError('vis_compose: needs the expanded maps or an image batch')
+    kind, img, mp, m = (desc[..., k] for k in range(4))
+    if kind.min() < 0 or kind.max() > 3:
+        raise ValueError('vis_compose: cell kinds must be 0..3')
+    uses_map, uses_img = kind >= VIS_MAP, (kind == VIS_IMAGE) | (kind == VIS_BLEND)
+    if uses_map.any() and (mp[uses_map].min() < 0 or mp[uses_map].max() >= counts[0]):
+        raise ValueError('vis_compose: a map index is outside [0, %d)' % counts[0])
+    if (kind == VIS_BLEND).any() and (m[kind == VIS_BLEND].min() < 0 or m[kind == VIS_BLEND].max() > 255):
+        raise ValueError('vis_compose: a blend mask is outside [0, 255]')
+    if uses_img.any():
+        which, idx = img[uses_img] >> 16, img[uses_img] & 65535
+        if which.min() < 0 or which.max() > 1:
+            raise ValueError('vis_compose: an image batch is not 0 or 1')
+        for w in (0, 1):
+            if (which == w).any() and idx[which == w].max() >= counts[1 + w]:
+                raise ValueError('vis_compose: an image index of batch %d is outside [0, %d)' % (w, counts[1 + w]))
+    words = np.concatenate([np.ascontiguousarray(desc).view(np.uint32).ravel(),
+                            np.ascontiguousarray(par).view(np.uint32).ravel(),
+                            np.ascontiguousarray(band_rgb).ravel()]).view(np.int32)
+    table = torch.from_numpy(words).to(dev)          # one upload: desc | par | band_rgb
+    nd, npar = desc.size, par.size
+    canvas = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    base = table.data_ptr()
+    call('sba_vis_compose', _p(canvas), W, H, V, band, nS, nr, nc, base, base + 4 * nd, base + 4 * (nd + npar),
+         _p(expanded), counts[0], _p(imgs0), counts[1], imgs0.shape[2] if imgs0 is not None else 0,
+         _p(imgs1), counts[2], imgs1.shape[2] if imgs1 is not None else 0, _stream())
+    return canvas

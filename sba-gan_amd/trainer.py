@@ -6,8 +6,9 @@ What differs, none of it in results:
     `define_optimizers` returns them in the reference's (optimizerG, [optimizerD...]) shape;
   * one training step is GANStep.step (same order as trainer.py:245-299), the per-100-iteration log lines are
     formatted from device scalars outside the step (the reference's five .item() syncs per step are gone);
-  * `save_img_results` writes a plain image grid per scale: the attention-overlay visualiser
-    (miscc/utils.py:53-282, PIL text rendering) is host-side drawing and out of scope (SURVEY.md 2, row 10);
+  * `save_img_results` writes a plain image grid per scale; with `attention_maps` (--attention_maps) it writes the
+    reference's attention overlays instead (G_*.png per attention stage, D_*.png for the DAMSM maps), built on the
+    device by sbagan.visualize from the overlays' contract (DESIGN.md 7c), and gen_example adds the top-5 strips;
   * checkpoints are the reference's files: Model/netG_epoch_N.pth (EMA weights, trainer.py:159-164) and
     Model/netD{i}.pth, loadable by either implementation.  With cfg.TRAIN.NET_E == '' the reference prints an
     error and fails; pass `allow_random_encoders=True` to train against randomly initialised frozen encoders
@@ -141,12 +142,37 @@ class condGANTrainer(object):
 
     def save_img_results(self, netG, noise, sent_emb, words_embs, mask, image_encoder, captions, cap_lens,
                          gen_iterations, name='current'):
-        """trainer.py:177-216 without the attention overlays: one grid (up to 8 samples) per scale."""
+        """trainer.py:177-216.  Without attention_maps: one plain grid (up to 8 samples) per scale.  With it: per
+        attention stage i the overlay grid G_<name>_<it>_<i>.png (stage i + 1's images, stage i's in the first row), and
+        D_<name>_<it>.png: the last stage through the image encoder and its DAMSM word-to-region maps."""
         was = netG.training
         netG.eval()
-        with torch.no_grad():
-            fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs, mask)
-        netG.train(was)
+        if self.attention_maps:
+            stages = [m for m in netG.modules() if hasattr(m, 'return_attention')]
+            flags = [m.return_attention for m in stages]
+            netG.set_return_attention(True)
+        try:
+            with torch.no_grad():
+                fake_imgs, att_maps, _, _ = netG(noise, sent_emb, words_embs, mask)
+        finally:
+            if self.attention_maps:
+                for m, flag in zip(stages, flags):
+                    m.return_attention = flag
+            netG.train(was)
+        if self.attention_maps:
+            from sbagan.visualize import build_super_images, damsm_attention_maps
+            for i, att in enumerate(att_maps):
+                img_set, _ = build_super_images(fake_imgs[i + 1], captions, self.ixtoword, att, att.size(2),
+                                                lr_imgs=fake_imgs[i])
+                Image.fromarray(img_set).save('%s/G_%s_%d_%d.png' % (self.image_dir, name, gen_iterations, i))
+            n = min(8, fake_imgs[-1].size(0))
+            with torch.no_grad():
+                region_features, _ = image_encoder(fake_imgs[-1][:n].detach())
+            maps = damsm_attention_maps(region_features, words_embs[:n], cap_lens[:n], cfg.TRAIN.SMOOTH.GAMMA1)
+            img_set, _ = build_super_images(fake_imgs[-1][:n], captions[:n], self.ixtoword, maps,
+                                            region_features.size(2))
+            Image.fromarray(img_set).save('%s/D_%s_%d.png' % (self.image_dir, name, gen_iterations))
+            return
         for i, f in enumerate(fake_imgs):
             tiles = [_to_uint8(f[j]) for j in range(min(8, f.size(0)))]
             Image.fromarray(np.concatenate(tiles, 1)).save('%s/G_%s_%d_%d.png' % (self.image_dir, name, gen_iterations, i))
@@ -267,14 +293,29 @@ class condGANTrainer(object):
         cut = ckpt.rfind('.pth')
         return ckpt[:cut] if cut >= 0 else ckpt
 
-    def _generate(self, netG, text_encoder, captions, cap_lens, noise, with_sent=False):
+    def _generate(self, netG, text_encoder, captions, cap_lens, noise, with_sent=False, with_att=False):
         """fake images of every stage for one caption batch (noise is refilled in place); with_sent: and the sentence
-        embeddings they were generated from"""
+        embeddings they were generated from; with_att: and the attention maps of every later stage"""
         words_embs, sent_emb = self._encode(text_encoder, captions, cap_lens)
         noise.normal_(0, 1)
         with torch.no_grad():
-            fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs, build_mask(captions, words_embs.size(2)))
+            fake_imgs, att_maps, _, _ = netG(noise, sent_emb, words_embs, build_mask(captions, words_embs.size(2)))
+        if with_att:
+            return fake_imgs, att_maps
         return (fake_imgs, sent_emb) if with_sent else fake_imgs
+
+    attention_maps = False      # --attention_maps: the attention overlays of save_img_results / gen_example
+
+    def _write_top_words(self, stages, att_maps, captions, cap_lens, order, out_dir, suffix=''):
+        """<out_dir>/0_s_<original index>_a<k><suffix>.png: per caption and attention stage k, the top-5 word strip over
+        stage k + 1's image (sbagan.visualize.build_super_images2)"""
+        from sbagan.visualize import build_super_images2
+        lens = [int(v) for v in cap_lens.tolist()]
+        for k, att in enumerate(att_maps):
+            for j, src in enumerate(order):
+                img_set, _ = build_super_images2(stages[k + 1][j], captions[j], lens[j], self.ixtoword, att[j],
+                                                 att.size(2))
+                Image.fromarray(img_set).save(os.path.join(out_dir, '0_s_%d_a%d%s.png' % (int(src), k, suffix)))
 
     r_precision = 0             # --r_precision R: sampling() also ranks every image among R candidate captions
     r_precision_seed = 100      # seed of the evaluator's own index generator and of the pool's caption draws
@@ -339,7 +380,8 @@ class condGANTrainer(object):
 
     def gen_example(self, data_dic):
         """trainer.py:435-518: data_dic[key] = [captions (n x Lmax int64, sorted by length), cap_lens, sorted_indices];
-        every stage's image per caption, named by the caption's ORIGINAL position (attention overlays: out of scope)."""
+        every stage's image per caption, named by the caption's ORIGINAL position; with attention_maps also the
+        top-5 word strips 0_s_<index>_a<k>.png."""
         root = self._output_root()
         if root is None:
             return None
@@ -351,8 +393,10 @@ class condGANTrainer(object):
             captions = torch.from_numpy(np.ascontiguousarray(captions)).to(self.device)
             cap_lens = torch.from_numpy(np.ascontiguousarray(cap_lens)).to(self.device)
             noise = torch.empty(self._noise_shape(captions.shape[0]), device=self.device)
-            stages = self._generate(netG, text_encoder, captions, cap_lens, noise)
+            stages, att_maps = self._generate(netG, text_encoder, captions, cap_lens, noise, with_att=True)
             for stage, batch in enumerate(stages):
                 for img, src in zip(batch, order):
                     self._write_image(img, os.path.join(out_dir, '0_s_%d_g%d.png' % (int(src), stage)))
+            if self.attention_maps:
+                self._write_top_words(stages, att_maps, captions, cap_lens, order, out_dir)
         return root

@@ -46,7 +46,7 @@ class condGANTrainer(trainer.condGANTrainer):
         return words_embs.detach(), sent_emb.detach()
 
     def gen_example(self, data_dic):
-        """trainer_bert.py:440-566 (attention overlays: out of scope)."""
+        """trainer_bert.py:440-566; with attention_maps also the top-5 word strips 0_s_<idx>_a<k>_<set>.png."""
         root = self._output_root()
         if root is None:
             return None
@@ -78,12 +78,15 @@ class condGANTrainer(trainer.condGANTrainer):
             noise.normal_(0, 1)
             swapped = torch.cat([noise[1:], noise[:1]], 0)
             with torch.no_grad():
-                sets = {'AB': netG_mix(noise, sent_emb, words_embs, mask)[0],
-                        'BA': netG_mix(swapped, sent_emb, words_embs, mask)[0],
-                        'A': netG(noise[0], sent_emb, words_embs, mask)[0],
-                        'B': netG(noise[1], sent_emb, words_embs, mask)[0]}
+                outs = {'AB': netG_mix(noise, sent_emb, words_embs, mask)[:2],
+                        'BA': netG_mix(swapped, sent_emb, words_embs, mask)[:2],
+                        'A': netG(noise[0], sent_emb, words_embs, mask)[:2],
+                        'B': netG(noise[1], sent_emb, words_embs, mask)[:2]}
             for tag in ('AB', 'BA', 'A', 'B'):
-                for stage, batch in enumerate(sets[tag]):
+                stages, att_maps = outs[tag]
+                for stage, batch in enumerate(stages):
                     for img, src in zip(batch, order):
                         self._write_image(img, os.path.join(out_dir, '0_s_%d_g%d_%s.png' % (int(src), stage, tag)))
+                if self.attention_maps:
+                    self._write_top_words(stages, att_maps, captions, cap_lens, order, out_dir, suffix='_' + tag)
         return root
