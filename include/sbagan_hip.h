@@ -661,6 +661,21 @@ int sba_vis_compose(uint8_t* canvas, int W, int H, int V, int band, int nS, int 
                     const float* par, const uint32_t* band_rgb, const float* E, int nE, const float* img0, int n0, int S0,
                     const float* img1, int n1, int S1, void* stream);
 
+/* FID statistics (evaluation; sbagan/fid.py), all accumulation in float64.
+ * sba_fid_accumulate: sum[D] += sum_k x[k][:] and gram[D][D] += X^T X over the n f32 feature rows x[k] (row stride ldx
+ * floats), on the f64 matrix instruction; the f32 values are widened in registers (their products are exact in f64, the
+ * only rounding is the f64 accumulation).  ONLY the upper-triangular 64 x 64 tiles of gram (tile row <= tile column) are
+ * updated; the tiles below the diagonal are not touched.  One workgroup per tile pair does one read-modify-write of its
+ * tile; no atomics, no workspace, a fixed summation order: two runs on the same input are bit-identical.  Rows >= n
+ * feed 0.0, so n may be any value >= 1.  SBA_E_ARG before any launch unless n >= 1, D >= 64, D % 64 == 0, ldx >= D,
+ * ldx % 4 == 0, x 16-byte aligned, sum and gram 8-byte aligned.
+ * sba_fid_finalize: mu = sum / n; sigma = (gram - sum sum^T / n) / (n - 1) (the ddof = 1 covariance) as the FULL
+ * symmetric [D][D] matrix, its lower triangle a bitwise copy of the upper; trace[0] = sum_i sigma_ii in a fixed order.
+ * Reads only the upper triangle of gram.  SBA_E_ARG unless n >= 2, D >= 64, D % 64 == 0. */
+int sba_fid_accumulate(const float* x, int n, int D, int ldx, double* sum, double* gram, void* stream);
+int sba_fid_finalize(const double* sum, const double* gram, int64_t n, int D, double* mu, double* sigma, double* trace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,8 +3,9 @@
     python main.py --cfg cfg/bird_style.yml --gpu 0 --data_dir ../data/birds [--manualSeed N]
 
 cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_example(example_filenames.txt).
---fused_inference, --r_precision R (sampling also writes r_precision.json) and --attention_maps (the attention-map
-overlay images, sbagan/visualize.py) are this project's additions."""
+--fused_inference, --r_precision R (sampling also writes r_precision.json), --attention_maps (the attention-map
+overlay images, sbagan/visualize.py) and --fid [--fid_stats PATH] (sampling also writes fid.json, sbagan/fid.py) are this
+project's additions."""
 import os
 import sys
 import time
@@ -79,6 +80,8 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo.fused_inference = bool(getattr(args, 'fused_inference', False))
     algo.r_precision = int(getattr(args, 'r_precision', 0))
     algo.attention_maps = bool(getattr(args, 'attention_maps', False))
+    algo.fid = bool(getattr(args, 'fid', False))
+    algo.fid_stats = getattr(args, 'fid_stats', None)
     start_t = time.time()
     if training:
         algo.train()

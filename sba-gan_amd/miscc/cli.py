@@ -1,6 +1,7 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
-    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--bert_dir DIR: the BERT entry points]
+    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]
+    [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
 reference's evaluation runs are seeded that way), the given one or a random one in training, and every run gets an
@@ -43,6 +44,13 @@ def options(what, default_cfg, argv=None, bert=False):
                     help='write the attention-map overlays (sbagan.visualize): Image/G_*.png and D_*.png in training, '
                          '<key>/0_s_<i>_a<k>.png from gen_example, Image/attention_maps<step>.png in DAMSM '
                          'pre-training')
+    ap.add_argument('--fid', dest='fid', action='store_true', default=False,
+                    help='sampling: also take the Frechet Inception Distance between the real images of the split and '
+                         'the generated ones on the DAMSM image encoder\'s Inception-v3 trunk (sbagan.fid) and write '
+                         'fid.json')
+    ap.add_argument('--fid_stats', dest='fid_stats', type=str, default=None, metavar='PATH',
+                    help='with --fid: an .npz of the real images\' statistics; read instead of the real pass when it '
+                         'exists, written after the run when it does not')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

@@ -140,6 +140,8 @@ SIGNATURES = {
     'sba_rprec_rank': [P, P, P, P, F, P, P, I, I, I, I, P],
     'sba_vis_expand': [P, P, P, P, P, P, P, I, I, I, P],
     'sba_vis_compose': [P, I, I, I, I, I, I, I, P, P, P, P, I, P, I, I, P, I, I, P],
+    'sba_fid_accumulate': [P, I, I, I, P, P, P],
+    'sba_fid_finalize': [P, P, L, I, P, P, P, P],
     'sba_set_deterministic': [I, P, L],
     'sba_set_reduce_scratch': [P, L],
     'sba_det_reset': [],

@@ -146,6 +146,7 @@ class InceptionHIP(object):
         # 120..273-workgroup launch each (hipGraph replay runs the side streams back to back anyway, ROCm 7.2)
         self.group = os.environ.get('SBA_ENC_GROUP', '1') == '1' and self.dtype == torch.bfloat16
         self._thunks = None          # forward: launch closures of the branch being recorded
+        self.last_pooled = None      # the f32 pooled Mixed_7c output [N, 2048] of the last forward
         self._train = False          # trunk_features(train=True): BatchNorm with batch statistics (DAMSM pre-training)
         self._keep = []
         self._pending = None         # implicit-GEMM launches collected for the current level
@@ -705,6 +706,7 @@ class InceptionHIP(object):
         a = nm['Mixed_7c'] = self._E('Mixed_7c', a, dense_out=True)
         pooled = torch.empty((N, 2048), dtype=torch.float32, device=self.device)
         call('sba_global_avgpool', dt, a.t.data_ptr(), pooled.data_ptr(), N, 64, 2048, 0, st)
+        self.last_pooled = pooled       # f32, before the compute-dtype rounding below (sbagan/fid.py reads it)
         pooled_t = _Act(pooled.to(self.dtype).view(N, 1, 1, 2048))
         code = self.conv('emb_cnn_code', pooled_t)                    # [N,1,1,nef_p]
         nef = self.nef
@@ -739,6 +741,19 @@ class InceptionHIP(object):
             pooled = pooled_t.t.view(img.shape[0], -1)[:, :2048].float().contiguous()
         self.tape, self._grads, self._saved, self.named = [], {}, None, {}
         return f768, pooled
+
+    def pooled_features(self, img):
+        """The pooled Mixed_7c output [B, 2048] in f32 as the global average pool wrote it (not rounded to the compute
+        dtype): an eval-mode forward without a tape.  The feature FID is taken on (sbagan/fid.py)."""
+        with torch.no_grad():
+            saved = self._train
+            self._train = False
+            try:
+                self.forward(img)
+            finally:
+                self._train = saved
+        self.tape, self._grads, self._saved, self.named = [], {}, None, {}
+        return self.last_pooled
 
     def backward(self, dfeat, dcode):
         (ishape, x299, a0, f, last, pooled_t, code) = self._saved

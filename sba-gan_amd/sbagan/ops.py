@@ -2064,3 +2064,61 @@ def vis_compose(V, band, desc, par, band_rgb, expanded=None, imgs0=None, imgs1=N
          _p(expanded), counts[0], _p(imgs0), counts[1], imgs0.shape[2] if imgs0 is not None else 0,
          _p(imgs1), counts[2], imgs1.shape[2] if imgs1 is not None else 0, _stream())
     return canvas
+
+
+# ----------------------------------------------------------------------------
+# evaluation: FID statistics (sbagan/fid.py)
+def _fid_need_moments(name, x_device, sum, gram):
+    for what, t, dim in (('sum', sum, 1), ('gram', gram, 2)):
+        _vis_need(name, t, what, torch.float64, dim)
+        if x_device is not None and t.device != x_device:
+            raise ValueError('%s: %s is on %s, x on %s' % (name, what, t.device, x_device))
+    D = sum.shape[0]
+    if D < 64 or D % 64:
+        raise ValueError('%s: D must be a positive multiple of 64 (got %d)' % (name, D))
+    if tuple(gram.shape) != (D, D) or gram.device != sum.device:
+        raise ValueError('%s: gram must be [%d][%d] on %s (got %s on %s)'
+                         % (name, D, D, sum.device, tuple(gram.shape), gram.device))
+    return D
+
+
+def fid_accumulate(x, sum, gram):
+    """sum += x.sum(0) and gram += x^T x in float64, in place (sba_fid_accumulate): x [n][D] f32 rows on the device (unit
+    column stride, row stride >= D and a multiple of 4, 16-byte aligned), sum [D] and gram [D][D] contiguous f64 on the
+    same device, D % 64 == 0, n >= 1.  Only the upper-triangular 64 x 64 tiles of gram are updated.  No atomics, a fixed
+    summation order.  Everything is checked before the launch: TypeError for a dtype, ValueError for a shape, a stride
+    or an alignment."""
+    if not torch.is_tensor(x):
+        raise TypeError('fid_accumulate: x must be a tensor')
+    _need_gpu(x)
+    if x.dtype != torch.float32:
+        raise TypeError('fid_accumulate: x must be float32 (got %s)' % x.dtype)
+    if x.dim() != 2:
+        raise ValueError('fid_accumulate: x must be 2-D (got %s)' % (tuple(x.shape),))
+    D = _fid_need_moments('fid_accumulate', x.device, sum, gram)
+    n, ldx = x.shape[0], x.stride(0)
+    if n < 1 or x.shape[1] != D:
+        raise ValueError('fid_accumulate: x must be [n >= 1][%d] (got %s)' % (D, tuple(x.shape)))
+    if n == 1:
+        ldx = D                     # (a single row has no meaningful row stride)
+    if x.stride(1) != 1 or ldx < D or ldx % 4:
+        raise ValueError('fid_accumulate: x needs unit column stride and a row stride >= D that is a multiple of 4 '
+                         '(got strides %s)' % (tuple(x.stride()),))
+    if x.data_ptr() % 16:
+        raise ValueError('fid_accumulate: x must be 16-byte aligned')
+    call('sba_fid_accumulate', _p(x), n, D, ldx, _p(sum), _p(gram), _stream())
+
+
+def fid_finalize(sum, gram, n):
+    """(mu [D], sigma [D][D], trace [1]), f64 on the device, from fid_accumulate's moments of n >= 2 rows
+    (sba_fid_finalize): mu = sum / n, sigma = (gram - sum sum^T / n) / (n - 1) as the full matrix, its lower triangle a
+    bitwise copy of the upper, trace = sum_i sigma_ii in a fixed order.  Reads the upper triangle of gram only."""
+    D = _fid_need_moments('fid_finalize', None, sum, gram)
+    n = int(n)
+    if n < 2:
+        raise ValueError('fid_finalize: a covariance needs n >= 2 rows (got %d)' % n)
+    mu = torch.empty(D, dtype=torch.float64, device=sum.device)
+    sigma = torch.empty((D, D), dtype=torch.float64, device=sum.device)
+    trace = torch.empty(1, dtype=torch.float64, device=sum.device)
+    call('sba_fid_finalize', _p(sum), _p(gram), n, D, _p(mu), _p(sigma), _p(trace), _stream())
+    return mu, sigma, trace

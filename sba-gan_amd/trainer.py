@@ -347,6 +347,24 @@ class condGANTrainer(object):
                                        self.batch_size, seed=self.r_precision_seed, device=self.device)
         return RPrecision(self._load_image_encoder(), pool, pool_class, R=self.r_precision, seed=self.r_precision_seed)
 
+    fid = False                 # --fid: sampling() also takes the FID between the split's real images and the fakes
+    fid_stats = None            # --fid_stats PATH: the real side's statistics, read when present, written when not
+    fid_result = None           # the result dict of the last sampling() with fid on
+
+    def _fid_evaluator(self, image_encoder, split_dir):
+        """sbagan.fid.FID on the pooled trunk feature of `image_encoder` (an InceptionHIP); the real side comes from
+        fid_stats when that file exists"""
+        from miscc import cli
+        from sbagan import ops
+        from sbagan.fid import FID, stats_key
+        dtype = str(ops.compute_dtype()).replace('torch.', '')
+        key = stats_key(cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder'), dtype, split_dir, cli.image_size())
+        evaluator = FID(image_encoder.pooled_features, D=2048, key=key, dtype=dtype)
+        if self.fid_stats and os.path.exists(self.fid_stats):
+            evaluator.load_real(self.fid_stats)
+            print('Load real FID statistics from:', self.fid_stats)
+        return evaluator
+
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
         root = self._output_root()
@@ -356,16 +374,28 @@ class condGANTrainer(object):
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
         evaluator = self._r_precision_evaluator(text_encoder) if self.r_precision else None
+        fid = fid_real = None
+        if self.fid:            # one image encoder serves both evaluators
+            image_encoder = evaluator.image_encoder if evaluator is not None else self._load_image_encoder()
+            fid = self._fid_evaluator(image_encoder, split_dir)
+            fid_real = not fid.is_loaded('real')
         noise = torch.empty(self._noise_shape(self.batch_size), device=self.device)
         made = set()
         for nbatch, data in enumerate(self.data_loader):
             if nbatch % 100 == 0:
                 print('step: ', nbatch)
-            _, captions, cap_lens, class_ids, keys = prepare_data(data)
+            real_imgs, captions, cap_lens, class_ids, keys = prepare_data(data)
             fake_imgs, sent_emb = self._generate(netG, text_encoder, captions, cap_lens, noise, with_sent=True)
             last = fake_imgs[-1]
             if evaluator is not None:
                 evaluator.update(last, sent_emb, class_ids)
+            if fid is not None:
+                if evaluator is not None:       # R-precision has just run this batch through the trunk
+                    fid.update_features('fake', image_encoder.last_pooled)
+                else:
+                    fid.update('fake', last)
+                if fid_real:
+                    fid.update('real', real_imgs[-1])
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
         if evaluator is not None:
@@ -376,6 +406,17 @@ class condGANTrainer(object):
                      res['r_at_1_splits_mean'], res['r_at_1_splits_std']))
             with open(os.path.join(out_dir, 'r_precision.json'), 'w') as f:
                 json.dump(res, f, indent=1, sort_keys=True)
+        if fid is not None:
+            self.fid_evaluator = fid
+            res = self.fid_result = fid.result()
+            print('FID (%d real, %d generated images, %s trunk): %.6g  (mean term %.6g, tr real %.6g, tr fake %.6g)'
+                  % (res['n_real'], res['n_fake'], res['dtype'], res['fid'], res['mean_term'], res['trace_real'],
+                     res['trace_fake']))
+            with open(os.path.join(out_dir, 'fid.json'), 'w') as f:
+                json.dump(res, f, indent=1, sort_keys=True)
+            if self.fid_stats and fid_real:
+                fid.save_real(self.fid_stats)
+                print('Save real FID statistics to:', self.fid_stats)
         return out_dir
 
     def gen_example(self, data_dic):
