@@ -441,23 +441,9 @@ class _GBase(nn.Module):
                 self._pre = [(st.style_of(w), st.keys_of(word_embs)) for st, w in stages]
         return ws, (main, side)
 
-    image_stream = None      # callable(i) -> the stream image head i runs on, or None for the current one (the trainer names
-    #                          the stream discriminator i is updated on for every image but the last: a head whose image
-    #                          only that discriminator reads leaves the serial chain of the generator's forward pass, and
-    #                          -- autograd replays a node's backward on its forward's stream -- of its backward pass)
-
     def _emit(self, fake_imgs, net, h):
         i = len(fake_imgs)
-        st = self.image_stream(i) if (self.image_stream is not None and h.is_cuda) else None
-        if st is None:
-            img = net(h)
-        else:
-            main = torch.cuda.current_stream()
-            st.wait_stream(main)
-            with torch.cuda.stream(st):
-                # h: produced on `main`, read on `st`; its gradient: produced on `st`, read on `main`
-                img = net(_CrossStream.apply(h, st, main))
-        fake_imgs.append(img)
+        fake_imgs.append(net(h))
         if self.on_image is not None:
             self.on_image(i)
 

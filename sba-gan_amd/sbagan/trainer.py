@@ -19,8 +19,7 @@ import torch.distributed as dist
 
 from miscc.config import cfg
 from miscc.losses import (KL_loss, backward_with_image_grad, backward_with_image_grads, damsm_image_terms,
-                          discriminator_fake_term, discriminator_loss, discriminator_real_term, generator_d_term,
-                          generator_loss)
+                          discriminator_loss, generator_d_term, generator_loss)
 
 from . import ops
 from ._lib import call
@@ -244,13 +243,8 @@ class GANStep(object):
             first = next(getattr(d, name).parameters()) if name else None
             self._bucket_off.append(None if first is None else f.offset_of[id(first)])
         self._real_feats = [None] * len(netsD)
-        self._real_terms = [None] * len(netsD)
-        self._begun = False
         self._g_terms = [None] * len(netsD)
-        self._adam_early = [None] * len(netsD)
-        self._d_zeroed = [False] * len(netsD)
         self._d_frozen = [False] * len(netsD)
-        self._forked_d = False
         self._g_pending = None
         self._d_buckets = {}
 
@@ -273,22 +267,13 @@ class GANStep(object):
     #                                 forwards ahead as their own passes, split backward passes) -- what a rank of the
     #                                 data-parallel step must reproduce bit for bit in the deterministic mode
 
-    # Single GPU: the discriminators' forward passes on the REAL images need nothing of the generator (losses.py:139): as
-    # their own passes (the reference's shape: netD(real), netD(fake) are separate calls) they run at the start of the step,
-    # beside the generator's forward pass -- a serial chain that leaves most of the chip idle -- instead of inside the
-    # crowded stretch between the generator's forward and backward passes (SBA_REAL_FIRST).
-    real_first = os.environ.get('SBA_REAL_FIRST', '0') == '1'
-
+    # The single-GPU step keeps the one grouped [real | fake] discriminator pass.  Measured against it in round 4 and removed:
+    # the two-pass layout with the real-image forwards at the start of the step, 10.15-10.27 -> 10.64 ms, and the same with
+    # the real half's loss terms and backward pass there too, +0.39 ms.
     def _two_pass(self):
-        return (self.distributed and self.overlap_g) or self.force_overlap_layout or self.real_first or self.real_bwd_early
+        return (self.distributed and self.overlap_g) or self.force_overlap_layout
 
-    # Experiment (last hours of round 4): with the two-pass layout, ALSO the real half's loss terms and their backward pass
-    # at the start of the step (they need neither the generator nor the fake images), so that only the fake half's
-    # forward + backward pass is left between the generator's passes.  SBA_REAL_BWD_EARLY=1; see losses.discriminator_real_term
-    # for the one deviation (order of the conditional head's BatchNorm running-statistic updates).
-    real_bwd_early = os.environ.get('SBA_REAL_BWD_EARLY', '0') == '1'
-
-    def phase_pre(self, imgs, streams=None, sent_emb=None):
+    def phase_pre(self, imgs, streams=None):
         """netD_i(real_i) for every discriminator, ahead of the generator's (pending) update; a no-op outside the
         overlapped data-parallel mode.  streams[i]: the stream discriminator i's update will run on -- autograd
         replays a node's backward on the stream of its forward, and the two passes of one network add into the same
@@ -303,19 +288,6 @@ class GANStep(object):
             if st is not main:
                 st.wait_stream(main)
             with torch.cuda.stream(st):
-                if self.real_bwd_early and sent_emb is not None and imgs[i].is_cuda:
-                    if self._d_frozen[i]:
-                        for p in d.parameters():
-                            p.requires_grad_(True)
-                        self._d_frozen[i] = False
-                    d.clear_cuts(record=False)
-                    if not self._d_zeroed[i]:
-                        self.flatD[i].zero_grad()
-                        self._d_zeroed[i] = True
-                    term = discriminator_real_term(d, d(imgs[i]), sent_emb)
-                    term.backward()
-                    self._real_terms[i] = term.detach()
-                    continue
                 d.clear_cuts()
                 self._real_feats[i] = d(imgs[i])
 
@@ -326,12 +298,13 @@ class GANStep(object):
         a host-call node: whether an update is pending is host state, so every replay applies it from the host, here."""
         rec = self.exchange.recorder
         if rec is not None:
-            if self.record_g_update and self.distributed and self.overlap_g:
+            if self.distributed and self.overlap_g:
                 # Only the WAIT for the exchange in flight is a host call (which handle to wait for is host state); the
                 # Adam + EMA launch and the repack of the bf16 weight copies are recorded like any other launch -- as
                 # eager launches issued from the callback they cost 0.38 ms at the head of the generator's forward pass
-                # (profiles/r04_dp_recorded_update.txt).  A replay therefore REQUIRES a pending update: ReplayedStep
-                # runs an eager step instead when there is none (after finish() / restore()).
+                # (10.37 against 10.32 ms per step, profiles/r04_dp_recorded_update.txt; that arm is removed).  A replay
+                # therefore REQUIRES a pending update: ReplayedStep runs an eager step instead when there is none (after
+                # finish() / restore()).
                 rec.host(self._wait_pending_replayed)
                 self.optG.step(1.0 / self.world)
                 if self.flatG.packs is not None:
@@ -341,8 +314,6 @@ class GANStep(object):
                 rec.host(self._finish_replayed)
             return
         self._finish_now()
-
-    record_g_update = os.environ.get('SBA_DP_RECORD_UPDATE', '1') == '1'
 
     def _wait_pending_replayed(self):
         """the host-call node in front of the RECORDED generator update: order the node's stream behind the exchange the
@@ -393,11 +364,8 @@ class GANStep(object):
     # loss, backward, Adam + EMA.  step() composes them with the eager stream forks.
     def phase_a(self, sent_emb, words_embs, mask, noise, eps=None):
         ops.SIDE_WGRAD = self.overlap_wgrad
-        if self._begun:                       # (step() did both ahead of the early real-half backward pass)
-            self._begun = False
-        else:
-            ops.det_reset()                   # deterministic mode: the step's partial sums start at the ring's base
-            ops.ARENA.begin(self.device)      # one memset for all per-layer accumulators of the step
+        ops.det_reset()                   # deterministic mode: the step's partial sums start at the ring's base
+        ops.ARENA.begin(self.device)      # one memset for all per-layer accumulators of the step
         self.netG.ca_net.eps = eps
         fake_imgs, _, mu, logvar = self.netG(noise, sent_emb, words_embs, mask)
         self._ctx = (fake_imgs, mu, logvar)
@@ -423,26 +391,18 @@ class GANStep(object):
                 p.requires_grad_(True)
             self._d_frozen[i] = False
         ops.SIDE_WGRAD = self.overlap_wgrad and self.overlap_wgrad_d
-        if self._d_zeroed[i]:           # cleared at the start of the step, beside the generator's forward pass (step())
-            self._d_zeroed[i] = False
-        else:
-            self.flatD[i].zero_grad()
+        # (clearing the gradients at the start of the step instead, beside the generator's forward pass, measured SLOWER:
+        # 11.7 against 11.0 ms -- the earlier forks change the replayer's stream assignment; removed)
+        self.flatD[i].zero_grad()
         rf = self._real_feats[i]
         self._real_feats[i] = None
-        split = ((self.distributed and self.bucket_d) or self.force_overlap_layout or
-                 (self.bucket_adam and self._forked_d)) and \
+        split = ((self.distributed and self.bucket_d) or self.force_overlap_layout) and \
             self._bucket_off[i] is not None and not ops.SIDE_WGRAD
-        rt = self._real_terms[i]
-        self._real_terms[i] = None
         if rf is None:
             netD.clear_cuts(record=split)
-        if rt is not None:          # the real half, backward pass included, ran at the start of the step (phase_pre)
-            errD = discriminator_fake_term(netD, fake_imgs[i], sent_emb)
-            self._out['errD%d' % i] = rt + errD.detach()
-        else:
-            errD = discriminator_loss(netD, imgs[i], fake_imgs[i], sent_emb, self.real_labels, self.fake_labels,
-                                      real_features=rf)
-            self._out['errD%d' % i] = errD.detach()
+        errD = discriminator_loss(netD, imgs[i], fake_imgs[i], sent_emb, self.real_labels, self.fake_labels,
+                                  real_features=rf)
+        self._out['errD%d' % i] = errD.detach()
         cuts = list(netD._cuts)
         netD.clear_cuts(record=False)
         if split and cuts:
@@ -468,31 +428,15 @@ class GANStep(object):
         bucket by bucket); returns (the stream on which the update must continue -- the weight-gradient companion
         when `forked`, see ops.wgrad_tail_stream --, the exchange handles to wait for)"""
         handles = []
-        self._adam_early[i] = None
         if self.phase_d_bwd_tail(i, imgs, sent_emb):
             if self.distributed:
                 handles.append(self.exchange.start(self.flatD[i].grad[self._bucket_off[i]:]))
-            elif forked and self.bucket_adam:
-                # The backward pass has reached the bucket boundary: the gradients of the tail + heads (D_NET256: 60.6 M of
-                # 71.9 M parameters) are complete.  Their Adam update -- 280 of the 334 us of an HBM-bound launch that
-                # otherwise sits on this discriminator's critical chain -- starts now on a side stream, beside the
-                # large-map trunk's backward pass; the rest of the chain continues on that stream (a one-way edge: ROCm
-                # 7.2's stream capture does not survive a fork that is joined back into a forked stream).
-                side = self._adam_stream(i)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self.optD[i].prepare()
-                    self.optD[i].step_range(self._bucket_off[i], self.flatD[i].n, 1.0 / self.world)
-                self._adam_early[i] = side
             self.phase_d_bwd_rest(i)
             split = True
         else:
             split = False
         if forked:
             tail = ops.wgrad_tail_stream()
-            if self._adam_early[i] is not None:
-                self._adam_early[i].wait_stream(tail)
-                tail = self._adam_early[i]
         else:
             ops.join_wgrads()
             tail = torch.cuda.current_stream()
@@ -508,23 +452,14 @@ class GANStep(object):
         ops.SIDE_WGRAD = self.overlap_wgrad
 
     def phase_d_opt(self, i):
-        """Adam step of discriminator i (its averaged gradient must be in place)."""
-        if self._adam_early[i] is not None:      # the tail bucket was updated beside the backward pass (phase_d_bwd)
-            self.optD[i].step_range(0, self._bucket_off[i], 1.0 / self.world)
-            self.optD[i].done()
-            self._adam_early[i] = None
-            return
+        """Adam step of discriminator i (its averaged gradient must be in place): one launch over the whole flat buffer.
+        (The tail + heads bucket updated on a side stream beside the trunk's backward pass -- FusedAdam.step_range --
+        measured SLOWER, 11.50 against 11.29 ms (round-3 A/B under profiles/): the HBM-bound update competes with the
+        trunk's weight gradients and the split backward pass adds a graph boundary; removed.)"""
         self.optD[i].step(1.0 / self.world)
 
-    def _adam_stream(self, i):
-        if getattr(self, '_adam_streams', None) is None:
-            self._adam_streams = [torch.cuda.Stream(device=self.device) for _ in self.netsD]
-        return self._adam_streams[i]
-
     def phase_d(self, i, imgs, sent_emb, forked):
-        self._forked_d = bool(forked) and not self.distributed
         tail, handles = self.phase_d_bwd(i, imgs, sent_emb, forked)
-        self._forked_d = False
         with torch.cuda.stream(tail):
             for h in handles:
                 self._allreduce_wait(h)
@@ -638,20 +573,7 @@ class GANStep(object):
         main = torch.cuda.current_stream()
         nD = len(self.netsD)
         streams = self._d_streams()[:nD] if self.concurrent_d else [main] * nD
-        if self.early_zero and self.concurrent_d:
-            # the discriminators' gradient buffers (D_NET256: 287 MB, a 57 us fill at the head of the longest chain of the
-            # step) are cleared on their update streams NOW, beside the generator's forward pass
-            for i in range(nD):
-                if streams[i] is not main:
-                    streams[i].wait_stream(main)
-                    with torch.cuda.stream(streams[i]):
-                        self.flatD[i].zero_grad()
-                    self._d_zeroed[i] = True
-        if self.real_bwd_early and self._two_pass():
-            ops.det_reset()
-            ops.ARENA.begin(self.device)
-            self._begun = True
-        self.phase_pre(imgs, streams, sent_emb)         # (data-parallel: beside the generator's pending gradient exchange)
+        self.phase_pre(imgs, streams)         # (data-parallel: beside the generator's pending gradient exchange)
         self.finish()
         # discriminator i reads fake image i only: its update forks from the point where that image has been issued
         # (64 px: after the first stage, 128 px: after the second), not from the end of the generator's forward pass
@@ -662,11 +584,8 @@ class GANStep(object):
                     img_ready[i] = torch.cuda.Event()
                     img_ready[i].record()
             self.netG.on_image = on_image
-            if self.fork_heads:
-                self.netG.image_stream = lambda i: streams[i] if (i < nD - 1 and streams[i] is not main) else None
         self.phase_a(sent_emb, words_embs, mask, noise, eps)
         self.netG.on_image = None
-        self.netG.image_stream = None
         mark('g_forward')
         # The three discriminator updates are independent of each other (different networks, the
         # same detached fakes): each runs on its own HIP stream so that the small launches of the
@@ -711,27 +630,14 @@ class GANStep(object):
             self.phase_events.append((name, e))
 
     concurrent_d = True
-    early_d = os.environ.get('SBA_EARLY_D', '1') == '1'      # fork the 64 / 128 px discriminator updates inside the G forward
-    fork_heads = os.environ.get('SBA_FORK_HEADS', '0') == '1'      # ... and evaluate the 64 / 128 px image heads on those
-    #                                                              discriminators' streams (nets._GBase.image_stream).  Bit-equal
-    #                                                              and audit-clean, but no measurable gain: 9.42 / 9.53 against
-    #                                                              9.52 / 9.39 ms (profiles/r04_ab_fork_heads.txt).  Off.
-    bucket_adam = os.environ.get('SBA_BUCKET_ADAM', '0') == '1'      # D_NET128 / D_NET256: Adam of the tail + heads beside the
-    #                                                                  trunk's backward pass (phase_d_bwd).  Correct (the GPU
-    #                                                                  suite passes with it on) but measured SLOWER: 11.50
-    #                                                                  against 11.29 ms -- the HBM-bound update competes with
-    #                                                                  the trunk's weight gradients, and the split backward
-    #                                                                  pass adds a graph boundary.  Off.
-    early_zero = os.environ.get('SBA_EARLY_ZERO', '0') == '1'      # clear the discriminators' gradients at the start of the step,
-    #                                                              beside the generator's forward pass.  Measured SLOWER (11.7
-    #                                                              against 11.0 ms): the earlier forks change the replayer's
-    #                                                              stream assignment.  Off.
-    early_g_terms = os.environ.get('SBA_EARLY_G_TERMS', '1') == '1'      # each discriminator's generator-loss term right
-    #                                                                  behind its own update (phase_g_term)
+    early_d = True               # fork the 64 / 128 px discriminator updates inside the G forward.  (Also evaluating the 64 /
+    #                              128 px image heads on those discriminators' streams: no gain, 9.42 / 9.53 against 9.52 /
+    #                              9.39 ms (round-4 A/B under profiles/); removed.)
+    early_g_terms = True         # each discriminator's generator-loss term right behind its own update (phase_g_term)
     early_damsm = True           # DAMSM terms + their image gradient beside the discriminator updates (phase_e)
     overlap_wgrad = True
-    overlap_wgrad_d = os.environ.get('SBA_OVERLAP_WGRAD_D', '0') == '1'      # companion streams inside the (already concurrent) discriminator updates cost
-                                 # 1.5 ms under hipGraph replay: ROCm 7.2 runs graph branches nearly serially
+    overlap_wgrad_d = False      # companion streams inside the (already concurrent) discriminator updates cost
+    #                              1.5 ms under hipGraph replay: ROCm 7.2 runs graph branches nearly serially
 
     def _e_stream(self):
         if getattr(self, '_estream', None) is None:
@@ -745,8 +651,8 @@ class GANStep(object):
             # 3.1 + 4.3 ms of slack against the longest path (sba_replay_prioritize's report, profiles/r04_ab_stream_priorities.txt).
             # Three chains beside the image encoder's instead of four: the encoder's ~160 short launches, which gate the
             # generator's backward pass, get a third of the dispatch slots instead of a quarter -- 10.46 -> 10.19..10.39 ms
-            # (profiles/r04_ab_d_merge.txt).  SBA_D_MERGE=0: one stream per discriminator.
-            if os.environ.get('SBA_D_MERGE', '1') == '1' and len(self.netsD) >= 3:
+            # (profiles/r04_ab_d_merge.txt).
+            if len(self.netsD) >= 3:
                 self._streams[0] = self._streams[1]
         return self._streams
 

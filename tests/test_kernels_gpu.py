@@ -1028,6 +1028,100 @@ def test_bce_kl_adam(dev):
     close(ema[0], avg[0], torch.float32, 'ema w'); close(ema[1], avg[1], torch.float32, 'ema b')
 
 
+def test_adam_step_in_pieces_is_bit_equal(dev):
+    """FusedAdam.step() is prepare() + step_range(0, n) + done(); the same update issued as two disjoint ranges -- on two
+    streams, or in the other order on one -- must give the same bits in the parameters, both moments, the EMA shadow and
+    the device state, and a piece must not touch an element outside its range.
+
+    lo = one full pass of the 4096 x 256-thread grid plus 257 vectors (a multiple of 4: piece starts must be 16-byte
+    aligned), so the first piece wraps the grid-stride loop; the second piece, 1027 elements, ends in the 3-element
+    scalar tail that the whole launch also ends in: every element takes the same code path both ways."""
+    from sbagan.trainer import FlatParams, FusedAdam
+    lo = 4 * (4096 * 256) + 4 * 257
+    n = lo + 1027
+
+    class One(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.zeros(n, device=dev))
+
+    flat = FlatParams(One(), with_ema=True)
+    # FlatParams pads its buffers to a multiple of four elements (here n + 1); the update is confined to the parameter's
+    # own n elements, so that the whole launch ends in the scalar tail.  The padding element must then never change.
+    assert flat.n == n + 1 and lo % 4 == 0
+    flat.n = n
+    opt = FusedAdam(flat, 2e-4)
+    opt.step()                                      # a state that is not all zeros (step counter 1)
+    gen = torch.Generator(device='cpu')
+    gen.manual_seed(20260)
+    bufs = {'data': flat.data, 'grad': flat.grad, 'm': flat.m, 'v': flat.v, 'avg': flat.avg}
+    for name, t in bufs.items():
+        src = torch.rand(n + 1, generator=gen) if name == 'v' else torch.randn(n + 1, generator=gen)
+        t.copy_(src.to(dev))
+    snap = {k: t.clone() for k, t in bufs.items()}
+    snap['state'] = opt.state.clone()
+    cur, side = torch.cuda.current_stream(), torch.cuda.Stream(device=dev)
+
+    def restore():
+        for k, t in bufs.items():
+            t.copy_(snap[k])
+        opt.state.copy_(snap['state'])
+
+    def result():
+        torch.cuda.synchronize()
+        r = {k: t.clone() for k, t in bufs.items() if k != 'grad'}
+        r['state'] = opt.state.clone()
+        return r
+
+    def whole():
+        opt.step(0.5)
+
+    def two_streams():
+        opt.prepare()
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            opt.step_range(lo, n, 0.5)
+        opt.step_range(0, lo, 0.5)
+        cur.wait_stream(side)
+        opt.done()
+
+    def other_order():
+        opt.prepare()
+        opt.step_range(lo, n, 0.5)
+        opt.step_range(0, lo, 0.5)
+        opt.done()
+
+    def only(a, b):
+        def f():
+            opt.prepare()
+            opt.step_range(a, b, 0.5)
+        return f
+
+    res = {}
+    for name, fn in (('whole', whole), ('two_streams', two_streams), ('other_order', other_order),
+                     ('upper', only(lo, n)), ('lower', only(0, lo)), ('empty', only(lo, lo)), ('empty0', only(0, 0))):
+        restore()
+        fn()
+        res[name] = result()
+    a = res['whole']
+    for k in ('data', 'm', 'v', 'avg'):
+        assert not torch.equal(a[k][:n], snap[k][:n]), k               # (the update moves every buffer)
+        for name in ('two_streams', 'other_order'):
+            assert torch.equal(res[name][k], a[k]), (name, k)
+        # one piece alone: its own range as in the whole update, everything outside bit-unchanged
+        assert torch.equal(res['upper'][k][:lo], snap[k][:lo]), ('upper piece wrote below lo', k)
+        assert torch.equal(res['upper'][k][lo:n], a[k][lo:n]), ('upper piece', k)
+        assert torch.equal(res['lower'][k][lo:], snap[k][lo:]), ('lower piece wrote at or above lo', k)
+        assert torch.equal(res['lower'][k][:lo], a[k][:lo]), ('lower piece', k)
+        for name in ('empty', 'empty0'):
+            assert torch.equal(res[name][k], snap[k]), ('an empty range changed', name, k)
+        for name in res:
+            assert torch.equal(res[name][k][n:], snap[k][n:]), ('padding element changed', name, k)
+    for name in res:
+        assert torch.equal(res[name]['state'], a['state']), (name, 'state')
+    assert not torch.equal(a['state'], snap['state'])
+
+
 def test_mask_and_sort_bit_exact(dev):
     from sbagan.trainer import build_mask, sort_by_caption_length
     caps, lens = fill.synthetic_captions(6, 20, 18, tag=9)
