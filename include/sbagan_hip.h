@@ -69,9 +69,10 @@ typedef struct sba_conv_geom {
      * (x_cstride = Cin, y_cstride = Cout).  Honoured by sba_conv_igemm only. */
     int32_t x_cstride, x_coff, y_cstride, y_coff;
     int32_t relu;               /* epilogue: y = max(acc + bias, 0) when set (with `bias`) */
-    /* tile configuration of sba_conv_igemm: 0 = the library's rule table; 1..SBA_IGEMM_TILES = a specific one
-     * (measured per layer shape by tools/tune_igemm.py into sbagan/igemm_table.json; bf16 only, an id the
-     * geometry cannot use falls back to the rules).  ksplit: 0 = the library decides, n >= 1 = split K n ways. */
+    /* tile configuration of sba_conv_igemm: 0 = the library's rule table; 1..SBA_IGEMM_TILES = a row of the tile table
+     * (kTiles in csrc/igemm.hip, the only list of the ids; measured per layer shape by tools/tune_igemm.py into
+     * sbagan/igemm_table.json; bf16 only, an id the geometry cannot use falls back to the rules).
+     * ksplit: 0 = the library decides, n >= 1 = split K n ways. */
     int32_t tile, ksplit;
     /* sba_conv_wgrad only: non-zero = the caller knows dw is all zeros (just cleared, nothing accumulated yet):
      * kernel paths whose workgroups own their outputs exclusively then STORE instead of read-modify-write (the
@@ -146,6 +147,8 @@ int sba_conv_igemm_bias(int dtype, const void* x, const void* w, void* y, const 
  * register-weight halo kernel conv3x3_halo3g_kernel -- only with g->w_layout = 1),
  * plan[1] = tile id (families 1 / 2: the ids of sba_conv_geom.tile) or configuration, plan[2] = K splits. */
 int sba_conv_igemm_plan(int dtype, const sba_conv_geom* g, int64_t workspace_bytes, int* plan);
+/* *bm x *bn = the workgroup tile (output pixels x output channels) of tile id 1..SBA_IGEMM_TILES */
+int sba_conv_igemm_tile_shape(int tile, int* bm, int* bn);
 
 /* ---- inference: conv + BatchNorm(eval) + GLU as ONE launch (sbagan/infer.py) ----
  * sba_fold_bn_pack: fold an eval-mode BatchNorm into the layer in front of it and pack the result for the forward
@@ -175,8 +178,8 @@ int sba_conv_igemm_glu_plan(int dtype, const sba_conv_geom* g, int C, int* plan)
  * do not overlap -- as ONE grid (bf16 only, no split-K, no statistics; bias / ReLU (g->relu) / addend /
  * relu_mask per item as in sba_conv_igemm_bias).  For the branches of an Inception block at one depth level (model.py:226-262:
  * the reference runs them one after the other): each alone is 120..273 workgroups of a 64 x 64 tile on 256 CUs.
- * tile: 1 = 64x64, 3 = 96x64, 5 = 128x64, 7 = 128x128 (0 = 1; 7 falls back to 5 when some Cin % 64 != 0).  The item array
- * is HOST memory, read during the call. */
+ * tile: an id whose row of the tile table has a grouped form -- 1, 3, 5, 7 (0 = 1; 7 falls back to 5 when some
+ * Cin % 64 != 0).  The item array is HOST memory, read during the call. */
 #define SBA_GROUP_MAX 8
 typedef struct sba_conv_group_item {
     const void* x; const void* w; void* y; const void* addend; const float* bias; const void* relu_mask;

@@ -268,6 +268,123 @@ __device__ __forceinline__ void tile_epilogue_glu(f32x16_t (&acc)[TM][TN], unsig
     }
 }
 
+// Split-K partial sums: every split adds its partial tile into the zero-filled f32 workspace with device-scope
+// atomics; splitk_finish_kernel then runs the epilogue and leaves the workspace zero.  (The last arriving split finishing
+// its tile inside the GEMM kernel -- one ticket per tile in the workspace tail -- passed the GPU suite but measured no
+// gain on the step, 14.96 vs 14.78 ms with 75 finishing launches fewer: the last arrival's 16 KB device-scope reload +
+// epilogue sits at the tail of every tile, where the finishing launch spreads the same work over the whole chip; removed.)
+template <int TM, int TN>
+__device__ __forceinline__ void splitk_accumulate(float* __restrict__ ws, const f32x16_t (&acc)[TM][TN], const int m0,
+                                                  const int n0, const int lane, const int M, const int Cout) {
+    const int col_s = lane & 31, rsel_s = 4 * (lane >> 5);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int co = n0 + j * 32 + col_s;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel_s;
+                if (m < M && co < Cout) atomicAdd(&ws[(int64_t)m * Cout + co], acc[i][j][r]);
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// What the three GEMM bodies below (igemm_kernel, igemm_dma_body, igemm_dma2_body) share in front of and behind their K
+// loops.  What they still spell out themselves changed a kernel's register counts when it came from a helper: the
+// packing of the tap words in all three, and in igemm_kernel the dead-row test of a_row_origin and gemm_tail.
+// ---------------------------------------------------------------------------
+// tap offsets are packed 4 bits each (offset + 8), 16 to a word, so that the per-step lookup is scalar shifts instead
+// of a dynamically indexed kernarg array: the offsets of tap `tap` out of the packed words
+__device__ __forceinline__ void tap_offsets(const uint64_t (&tyb)[2], const uint64_t (&txb)[2], const int tap, int& ty,
+                                            int& tx) {
+    const int tsel = tap < SBA_MAX_TAPS ? tap : 0;
+    const uint64_t tyw = tsel < 16 ? tyb[0] : tyb[1], txw = tsel < 16 ? txb[0] : txb[1];
+    ty = (int)((tyw >> (4 * (tsel & 15))) & 15) - 8;
+    tx = (int)((txw >> (4 * (tsel & 15))) & 15) - 8;
+}
+
+// GEMM row m = output pixel (oy, ox) of the OHs x OWs sub-grid (sub = OHs * OWs pixels) of image n
+__device__ __forceinline__ void row_pixel(const sba_conv_geom& g, const int sub, const int m, int& n, int& oy, int& ox) {
+    n = m / sub;
+    const int rem = m - n * sub;
+    oy = rem / g.OWs;
+    ox = rem - oy * g.OWs;
+}
+
+// the A row a thread stages (fixed over the K loop): tap (ty, tx) reads input pixel (iy0 + ty, ix0 + tx) of the image
+// that starts at pixel nb; a row that is not `live` (beyond M or the tile) is out of bounds for every tap -> zero rows
+__device__ __forceinline__ void a_row_origin(const sba_conv_geom& g, const int sub, const int m, const bool live,
+                                             int& iy0, int& ix0, int& nb) {
+    if (live) {
+        int n, oy, ox;
+        row_pixel(g, sub, m, n, oy, ox);
+        iy0 = oy * g.sy;
+        ix0 = ox * g.sx;
+        nb = n * g.IH * g.IW;
+    } else {
+        iy0 = -100000;
+        ix0 = 0;
+        nb = 0;
+    }
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16_t (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// LDS-DMA bodies, workgroup L -> tile (mt, nt); false = a padding slot of the grid.  Ids L and L + 8 share an XCD.
+// M-major: the N tiles of an M tile (they share its input rows) take consecutive slots of one XCD, each XCD's L2 fetches
+// the weights once (x read ~once, w up to 8 times); N-major (weight-heavy GEMM-like layers: a few M tiles against
+// megabytes of weights): the M tiles of an N tile on one XCD -- its weight slice is fetched by that XCD only
+__device__ __forceinline__ bool xcd_tile(const int L, const int gx, const int gy, const int nmajor, int& mt, int& nt) {
+    const int xcd = L & 7, q = L >> 3;
+    if (nmajor) {
+        nt = xcd + 8 * (q / gx);
+        mt = q - (q / gx) * gx;
+        return nt < gy;
+    }
+    mt = xcd + 8 * (q / gy);
+    nt = q - (q / gy) * gy;
+    return mt < gx;
+}
+
+// Behind the K loop of the LDS-DMA bodies (it ended with a barrier: the ring is free).  ws != NULL: a split-K partial, the
+// epilogue is splitk_finish_kernel's.  Otherwise the epilogue's row table and statistics accumulators, then the epilogue.
+template <typename T, int BM, int BN, int TM, int TN, int NT, int LDS_BYTES>
+__device__ __forceinline__ void gemm_tail(f32x16_t (&acc)[TM][TN], float* __restrict__ ws, unsigned char* lds, int* rowoff,
+                                          float* s_stat, const int m_base, const int n_base, const int wm0, const int wn0,
+                                          const int lane, const int M, const int ycs, const sba_conv_geom& g,
+                                          T* __restrict__ y, const T* __restrict__ addend, float* __restrict__ stats,
+                                          const EpiX ex, const int slot_id) {
+    if (ws) {
+        splitk_accumulate<TM, TN>(ws, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout);
+        return;
+    }
+    const int sub = g.OHs * g.OWs;
+    for (int r = threadIdx.x; r < BM; r += NT) {
+        const int m = m_base + r;
+        int off = -1;
+        if (m < M) {
+            int n, oy, ox;
+            row_pixel(g, sub, m, n, oy, ox);
+            off = (n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
+        }
+        rowoff[r] = off;
+    }
+    for (int c = threadIdx.x; c < 2 * BN; c += NT) s_stat[c] = 0.f;
+    __syncthreads();
+    tile_epilogue<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, true, lds, rowoff, s_stat, wm0, wn0, lane, n_base, ycs, g, y, addend,
+                                                    stats, ex, slot_id);
+}
+
 // ---------------------------------------------------------------------------
 // forward / data-gradient implicit GEMM
 //   rows  = output pixels of the (OHs x OWs) sub-grid, M = N*OHs*OWs
@@ -319,8 +436,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
     for (int i = 0; i < AI; ++i) {
         const int m = m_base + (tid >> 2) + RP * i;
         if (m < M && (tid >> 2) + RP * i < BM) {
-            const int n = m / sub, rem = m - n * sub;
-            const int oy = rem / g.OWs, ox = rem - oy * g.OWs;
+            int n, oy, ox;
+            row_pixel(g, sub, m, n, oy, ox);
             a_iy0[i] = oy * g.sy;
             a_ix0[i] = ox * g.sx;
             a_nb[i] = n * g.IH * g.IW;
@@ -332,9 +449,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
     }
     const int cpt = g.Cin / KS_CH;            // slabs per tap
     const int nsteps = g.ntaps * cpt;
-    // tap offsets packed 4 bits each (offset + 8) so that the per-step lookup is
-    // scalar shifts instead of a dynamically indexed kernarg array
-    uint64_t tyb[2] = {0, 0}, txb[2] = {0, 0};
+    uint64_t tyb[2] = {0, 0}, txb[2] = {0, 0};     // packed tap offsets: see tap_offsets
 #pragma unroll
     for (int t = 0; t < SBA_MAX_TAPS; ++t) {
         tyb[t >> 4] |= (uint64_t)((g.ty[t] + 8) & 15) << (4 * (t & 15));
@@ -381,10 +496,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
             const bool live = g_step < s_end;
             if (g_tap != cur_tap) {                     // (uniform) new tap: refresh the gather offsets
                 cur_tap = g_tap;
-                const int tsel = g_tap < SBA_MAX_TAPS ? g_tap : 0;
-                const uint64_t tyw = tsel < 16 ? tyb[0] : tyb[1], txw = tsel < 16 ? txb[0] : txb[1];
-                const int ty = (int)((tyw >> (4 * (tsel & 15))) & 15) - 8;
-                const int tx = (int)((txw >> (4 * (tsel & 15))) & 15) - 8;
+                int ty, tx;
+                tap_offsets(tyb, txb, g_tap, ty, tx);
 #pragma unroll
                 for (int i = 0; i < AI; ++i) {
                     int iy = a_iy0[i] + ty, ix = a_ix0[i] + tx;
@@ -429,12 +542,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
     };
 
     f32x16_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int nstages = (s_end - s_begin + KS - 1) / KS;
     gload(rra, rrb);
@@ -452,30 +560,17 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
         __syncthreads();
     }
 
-    if (ws) {
-        // split-K partial: f32 atomics into ws[m][co]; y / addend / stats are done by splitk_finish_kernel
-        const int col_s = lane & 31, rsel_s = 4 * (lane >> 5);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int co = n_base + wn0 + j * 32 + col_s;
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m_base + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel_s;
-                    if (m < M && co < g.Cout) atomicAdd(&ws[(int64_t)m * g.Cout + co], acc[i][j][r]);
-                }
-        }
+    // (as gemm_tail, with the GLU epilogue; the main loop ended with a barrier: the staging buffers are free)
+    if (ws) {           // split-K: splitk_finish_kernel runs the epilogue
+        splitk_accumulate<TM, TN>(ws, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout);
         return;
     }
-
-    // (the main loop ended with a barrier: the staging buffers are free)
     for (int r = threadIdx.x; r < BM; r += NT) {
         const int m = m_base + r;
         int off = -1;
         if (m < M) {
-            const int n = m / sub, rem = m - n * sub;
-            const int oy = rem / g.OWs, ox = rem - oy * g.OWs;
+            int n, oy, ox;
+            row_pixel(g, sub, m, n, oy, ox);
             off = (n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
         }
         rowoff[r] = off;
@@ -509,28 +604,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (sizeof(T) == 2 && BM *
 //   * workgroups are numbered so that the N tiles of one M tile run on one XCD, back to back (shared A rows
 //     are served by that XCD's L2).
 // ---------------------------------------------------------------------------
-
-// Split-K partial sums: every split adds its partial tile into the zero-filled f32 workspace with device-scope
-// atomics; splitk_finish_kernel then runs the epilogue and leaves the workspace zero.  (The last arriving split finishing
-// its tile inside the GEMM kernel -- one ticket per tile in the workspace tail -- passed the GPU suite but measured no
-// gain on the step, 14.96 vs 14.78 ms with 75 finishing launches fewer: the last arrival's 16 KB device-scope reload +
-// epilogue sits at the tail of every tile, where the finishing launch spreads the same work over the whole chip; removed.)
-template <int TM, int TN>
-__device__ __forceinline__ void splitk_accumulate(float* __restrict__ ws, const f32x16_t (&acc)[TM][TN], const int m0,
-                                                  const int n0, const int lane, const int M, const int Cout) {
-    const int col_s = lane & 31, rsel_s = 4 * (lane >> 5);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int co = n0 + j * 32 + col_s;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel_s;
-                if (m < M && co < Cout) atomicAdd(&ws[(int64_t)m * Cout + co], acc[i][j][r]);
-            }
-    }
-}
 
 #ifdef SBA_DMA_TRACE     // tools/trace_dma.py: per-stage s_memtime stamps of wave 0 of the first workgroups
 static unsigned long long* g_dma_trace = nullptr;
@@ -572,21 +645,8 @@ __device__ __forceinline__ void igemm_dma_body(
     int* rowoff = reinterpret_cast<int*>(lds_all + EPI_OFF);
     float* s_stat = reinterpret_cast<float*>(lds_all + EPI_OFF + BM * 4);
 
-    // workgroup -> tile: ids L and L + 8 share an XCD; the N tiles of an M tile take consecutive slots of one XCD
-    // M-major: the N tiles of an M tile (they share its input rows) take consecutive slots of one XCD, each XCD's L2 fetches
-    // the weights once (x read ~once, w up to 8 times); N-major (weight-heavy GEMM-like layers: a few M tiles against
-    // megabytes of weights): the M tiles of an N tile on one XCD -- its weight slice is fetched by that XCD only
-    const int xcd = L & 7, q = L >> 3;
     int mt, nt;
-    if (nmajor) {
-        nt = xcd + 8 * (q / gx);
-        mt = q - (q / gx) * gx;
-        if (nt >= gy) return;
-    } else {
-        mt = xcd + 8 * (q / gy);
-        nt = q - (q / gy) * gy;
-        if (mt >= gx) return;
-    }
+    if (!xcd_tile(L, gx, gy, nmajor, mt, nt)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm0 = (wid / WAVES_N) * WM, wn0 = (wid % WAVES_N) * WN;
@@ -602,21 +662,11 @@ __device__ __forceinline__ void igemm_dma_body(
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
         const int m = m_base + 16 * (wid + NW * i) + rsub;
-        if (m < M) {
-            const int n = m / sub, rem = m - n * sub;
-            const int oy = rem / g.OWs, ox = rem - oy * g.OWs;
-            a_iy0[i] = oy * g.sy;
-            a_ix0[i] = ox * g.sx;
-            a_nb[i] = n * g.IH * g.IW;
-        } else {
-            a_iy0[i] = -100000;
-            a_ix0[i] = 0;
-            a_nb[i] = 0;
-        }
+        a_row_origin(g, sub, m, m < M, a_iy0[i], a_ix0[i], a_nb[i]);
     }
     const int cpt = g.Cin / 32;
     const int nsteps = g.ntaps * cpt;
-    uint64_t tyb[2] = {0, 0}, txb[2] = {0, 0};
+    uint64_t tyb[2] = {0, 0}, txb[2] = {0, 0};     // packed tap offsets: see tap_offsets
 #pragma unroll
     for (int t = 0; t < SBA_MAX_TAPS; ++t) {
         tyb[t >> 4] |= (uint64_t)((g.ty[t] + 8) & 15) << (4 * (t & 15));
@@ -656,10 +706,8 @@ __device__ __forceinline__ void igemm_dma_body(
             if (g_step < s_end) {
                 if (g_tap != cur_tap) {             // (uniform) new tap: per-lane pixel offsets
                     cur_tap = g_tap;
-                    const int tsel = g_tap < SBA_MAX_TAPS ? g_tap : 0;
-                    const uint64_t tyw = tsel < 16 ? tyb[0] : tyb[1], txw = tsel < 16 ? txb[0] : txb[1];
-                    const int ty = (int)((tyw >> (4 * (tsel & 15))) & 15) - 8;
-                    const int tx = (int)((txw >> (4 * (tsel & 15))) & 15) - 8;
+                    int ty, tx;
+                    tap_offsets(tyb, txb, g_tap, ty, tx);
 #pragma unroll
                     for (int i = 0; i < AI; ++i) {
                         int iy = a_iy0[i] + ty, ix = a_ix0[i] + tx;
@@ -687,12 +735,7 @@ __device__ __forceinline__ void igemm_dma_body(
     };
 
     f32x16_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // fragment addressing: lane l reads row (l & 31), logical chunk 2 * kk + (l >> 5), swizzled by its row
     const int fr = lane & 31, fh = lane >> 5, fsw = (fr >> 2) & 3;
@@ -755,24 +798,8 @@ __device__ __forceinline__ void igemm_dma_body(
     wait_vmcnt<0>();        // the dead stages issued past the end still write (zeros) into the ring
     wg_barrier();
 
-    if (ws) {           // split-K: splitk_finish_kernel runs the epilogue
-        splitk_accumulate<TM, TN>(ws, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout);
-        return;
-    }
-    for (int r = threadIdx.x; r < BM; r += NT) {
-        const int m = m_base + r;
-        int off = -1;
-        if (m < M) {
-            const int n = m / sub, rem = m - n * sub;
-            const int oy = rem / g.OWs, ox = rem - oy * g.OWs;
-            off = (n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
-        }
-        rowoff[r] = off;
-    }
-    for (int c = threadIdx.x; c < 2 * BN; c += NT) s_stat[c] = 0.f;
-    __syncthreads();
-    tile_epilogue<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, true, lds_all, rowoff, s_stat, wm0, wn0, lane, n_base, ycs, g, y,
-                                                    addend, stats, ex, mt + bz);
+    gemm_tail<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, ws, lds_all, rowoff, s_stat, m_base, n_base, wm0, wn0, lane, M, ycs, g,
+                                                y, addend, stats, ex, mt + bz);
 }
 
 template <int BM, int BN, int WM, int WN, int KS, int D>
@@ -828,20 +855,8 @@ __device__ __forceinline__ void igemm_dma2_body(
     int* rowoff = reinterpret_cast<int*>(lds_all + EPI_OFF);
     float* s_stat = reinterpret_cast<float*>(lds_all + EPI_OFF + BM * 4);
 
-    // M-major: the N tiles of an M tile (they share its input rows) take consecutive slots of one XCD, each XCD's L2 fetches
-    // the weights once (x read ~once, w up to 8 times); N-major (weight-heavy GEMM-like layers: a few M tiles against
-    // megabytes of weights): the M tiles of an N tile on one XCD -- its weight slice is fetched by that XCD only
-    const int xcd = L & 7, q = L >> 3;
     int mt, nt;
-    if (nmajor) {
-        nt = xcd + 8 * (q / gx);
-        mt = q - (q / gx) * gx;
-        if (nt >= gy) return;
-    } else {
-        mt = xcd + 8 * (q / gy);
-        nt = q - (q / gy) * gy;
-        if (mt >= gx) return;
-    }
+    if (!xcd_tile(L, gx, gy, nmajor, mt, nt)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm0 = (wid / WAVES_N) * WM, wn0 = (wid % WAVES_N) * WN;
@@ -858,21 +873,11 @@ __device__ __forceinline__ void igemm_dma2_body(
     for (int i = 0; i < AI; ++i) {
         const int r = 8 * (wid + NW * i) + rsub, m = m_base + r;
         a_chunk[i] = (uint32_t)(((lane & 7) ^ ((r >> 1) & 7)) * 16);
-        if (m < M) {
-            const int n = m / sub, rem = m - n * sub;
-            const int oy = rem / g.OWs, ox = rem - oy * g.OWs;
-            a_iy0[i] = oy * g.sy;
-            a_ix0[i] = ox * g.sx;
-            a_nb[i] = n * g.IH * g.IW;
-        } else {
-            a_iy0[i] = -100000;
-            a_ix0[i] = 0;
-            a_nb[i] = 0;
-        }
+        a_row_origin(g, sub, m, m < M, a_iy0[i], a_ix0[i], a_nb[i]);
     }
     const int cpt = g.Cin / 64;               // slabs per tap
     const int nsteps = g.ntaps * cpt;
-    uint64_t tyb[2] = {0, 0}, txb[2] = {0, 0};
+    uint64_t tyb[2] = {0, 0}, txb[2] = {0, 0};     // packed tap offsets: see tap_offsets
 #pragma unroll
     for (int t = 0; t < SBA_MAX_TAPS; ++t) {
         tyb[t >> 4] |= (uint64_t)((g.ty[t] + 8) & 15) << (4 * (t & 15));
@@ -909,10 +914,8 @@ __device__ __forceinline__ void igemm_dma2_body(
         if (st_live) {
             if (g_tap != cur_tap) {             // (uniform) new tap: per-lane pixel offsets
                 cur_tap = g_tap;
-                const int tsel = g_tap < SBA_MAX_TAPS ? g_tap : 0;
-                const uint64_t tyw = tsel < 16 ? tyb[0] : tyb[1], txw = tsel < 16 ? txb[0] : txb[1];
-                const int ty = (int)((tyw >> (4 * (tsel & 15))) & 15) - 8;
-                const int tx = (int)((txw >> (4 * (tsel & 15))) & 15) - 8;
+                int ty, tx;
+                tap_offsets(tyb, txb, g_tap, ty, tx);
 #pragma unroll
                 for (int i = 0; i < AI; ++i) {
                     int iy = a_iy0[i] + ty, ix = a_ix0[i] + tx;
@@ -943,12 +946,7 @@ __device__ __forceinline__ void igemm_dma2_body(
     };
 
     f32x16_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // fragment addressing: lane l reads row (l & 31), logical chunk 2 * kk + (l >> 5), swizzled by its row
     const int fr = lane & 31, fh = lane >> 5, fsw = (fr >> 1) & 7;
@@ -1039,24 +1037,8 @@ __device__ __forceinline__ void igemm_dma2_body(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     wg_barrier();
 
-    if (ws) {           // split-K: splitk_finish_kernel runs the epilogue
-        splitk_accumulate<TM, TN>(ws, acc, m_base + wm0, n_base + wn0, lane, M, g.Cout);
-        return;
-    }
-    for (int r = threadIdx.x; r < BM; r += NT) {
-        const int m = m_base + r;
-        int off = -1;
-        if (m < M) {
-            const int n = m / sub, rem = m - n * sub;
-            const int oy = rem / g.OWs, ox = rem - oy * g.OWs;
-            off = (n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
-        }
-        rowoff[r] = off;
-    }
-    for (int c = threadIdx.x; c < 2 * BN; c += NT) s_stat[c] = 0.f;
-    __syncthreads();
-    tile_epilogue<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, true, lds_all, rowoff, s_stat, wm0, wn0, lane, n_base, ycs, g, y,
-                                                    addend, stats, ex, mt + bz);
+    gemm_tail<T, BM, BN, TM, TN, NT, LDS_BYTES>(acc, ws, lds_all, rowoff, s_stat, m_base, n_base, wm0, wn0, lane, M, ycs, g,
+                                                y, addend, stats, ex, mt + bz);
 }
 
 template <int BM, int BN, int WM, int WN, int D>
@@ -1674,22 +1656,50 @@ static const IgemmCfg kCfg[5] = {
     {64, 64, 2, 4, 0.50f, true},    {320, 128, 2, 1, 0.90f, true}};
 constexpr int IGEMM_SPLIT_MAX_M = 2048;     // split-K only pays on the GEMM-like maps: M up to this
 
-template <typename T, int BM, int BN, int WM, int WN, int KS>
-static void launch_cfg(const T* xp, const T* wp, T* yp, const T* ap, float* stats, const sba_conv_geom& g, int M,
-                       int nslabs, int split, float* ws, hipStream_t st, const EpiX ex) {
-    constexpr int NT = (BM / WM) * (BN / WN) * 64;
-    int sps = nslabs;
-    if (split > 1) {
-        sps = cdiv(cdiv(nslabs, split), KS) * KS;
-        split = cdiv(nslabs, sps);
-    }
-    dim3 grid(cdiv(M, BM), cdiv(g.Cout, BN), split);
-    SBA_LAUNCH((igemm_kernel<T, BM, BN, WM, WN, KS>), grid, dim3(NT), 0, st, xp, wp, yp, ap, stats, g, M,
-                       split > 1 ? ws : (float*)nullptr, sps, ex);
-    if (split > 1) {
-        dim3 fgrid(cdiv(g.Cout / 4, 256), cdiv(M, 8));
-        SBA_LAUNCH((splitk_finish_kernel<T>), fgrid, dim3(256), 0, st, ws, yp, ap, stats, g, M, ex);
-    }
+// ---- the tile table ------------------------------------------------------------------------------------------
+// THE table of tile ids (sba_conv_geom.tile, 1..SBA_IGEMM_TILES; row 0 is unused): every dispatch below, the grouped
+// launches and sba_conv_igemm_tile_shape read it, nothing else lists the ids.  BM x BN workgroup tile, one wave per
+// WM x WN sub-tile.
+//   d2        ring depth of the gen-2 form (igemm_dma2_kernel: 64-channel slabs, Cin % 64 == 0 only); 0 = none
+//   ks1, d1   slabs per stage and ring depth of the gen-1 form (igemm_dma_kernel: 32-channel slabs), same tile shape;
+//             d1 = 0: no gen-1 form (ids >= 13 go back to the rules when Cin % 64 != 0)
+//   d2 = d1 = 0 (id 11): the register-staged igemm_kernel with ks1 slabs per stage, whatever Cin is
+//   group     0 = no grouped form.  Otherwise sba_conv_igemm_group* takes the id: the gen-2 form of this row when every
+//             member has Cin % 64 == 0, else the gen-1 form of row `group` (7 falls back to 5: no 128-wide gen-1 group)
+// Even ids 2..10 are the odd id before them with a deeper ring (64..72 KB -> 120..144 KB of LDS: ~100 KB of loads in
+// flight per CU; an L2-hit load takes ~1 us under load, so a workgroup alone on its CU moves bytes_in_flight / 1 us,
+// measured 36-42 GB/s with 48 KB in flight).  13..15 put the WHOLE batch of a 4x4 map (M = 16 B = 320) in one M tile:
+// every weight byte is staged once per M tile, so those weight-streaming layers (4..38 MB of weights against 320..640
+// rows) move 1/3..1/5 of the L2->LDS bytes of the 64- / 96-row tiles; 15 is 14 with a 2-stage ring (60 KB: two
+// workgroups per CU).  16..18: 256x128 with 128x64 or 64x64 wave tiles.
+struct IgemmTile { int bm, bn, wm, wn, d2, ks1, d1, group; };
+constexpr IgemmTile kTiles[SBA_IGEMM_TILES + 1] = {
+    {},
+    {64, 64, 32, 32, 4, 2, 4, 1},       //  1
+    {64, 64, 32, 32, 8, 2, 8, 0},       //  2
+    {96, 64, 32, 64, 3, 2, 3, 3},       //  3
+    {96, 64, 32, 64, 6, 2, 6, 0},       //  4
+    {128, 64, 32, 64, 3, 1, 4, 5},      //  5
+    {128, 64, 32, 64, 6, 2, 6, 0},      //  6
+    {128, 128, 64, 64, 3, 1, 4, 5},     //  7
+    {128, 128, 64, 64, 4, 1, 8, 0},     //  8
+    {256, 64, 64, 64, 3, 1, 3, 0},      //  9
+    {256, 64, 64, 64, 4, 1, 6, 0},      // 10
+    {320, 128, 64, 64, 0, 2, 0, 0},     // 11  register-staged (configuration E)
+    {96, 128, 32, 128, 5, 1, 8, 0},     // 12
+    {320, 64, 64, 64, 3, 0, 0, 0},      // 13  5 waves
+    {160, 64, 32, 64, 4, 0, 0, 0},      // 14  5 waves
+    {160, 64, 32, 64, 2, 0, 0, 0},      // 15
+    {256, 128, 128, 64, 3, 0, 0, 0},    // 16
+    {256, 128, 64, 64, 3, 0, 0, 0},     // 17
+    {256, 128, 128, 64, 2, 0, 0, 0},    // 18
+};
+
+// runtime tile id -> compile-time row: f(std::integral_constant<int, id>) for id in 1..SBA_IGEMM_TILES, else SBA_E_ARG
+template <int I = 1, typename F>
+static int with_tile(int id, F&& f) {
+    if constexpr (I <= SBA_IGEMM_TILES) return id == I ? f(std::integral_constant<int, I>{}) : with_tile<I + 1>(id, f);
+    else return SBA_E_ARG;
 }
 
 // N-major tile numbering (see igemm_dma2_body) when the weights outweigh the input tensor
@@ -1698,44 +1708,49 @@ static int nmajor_for(const sba_conv_geom& g) {
     return wb > xb ? 1 : 0;
 }
 
-template <int BM, int BN, int WM, int WN, int KS, int D>
-static void launch_dma(const bf16_t* xp, const bf16_t* wp, bf16_t* yp, const bf16_t* ap, float* stats,
-                       const sba_conv_geom& g, int M, int nslabs, int split, float* ws, hipStream_t st, const EpiX ex) {
-    constexpr int NT = (BM / WM) * (BN / WN) * 64;
+// What launch_body needs to know of a GEMM body: its kernel and tile, SLAB = channels per K slab, KS = slabs per stage
+// (a K split is a whole number of stages), XCD = the grid is the XCD-aware one-dimensional tile numbering.
+template <typename T, int BM_, int BN_, int WM, int WN, int KS_> struct RegBody {
+    static constexpr int BM = BM_, BN = BN_, NT = (BM / WM) * (BN / WN) * 64, SLAB = 64 / (int)sizeof(T), KS = KS_;
+    static constexpr bool XCD = false;
+    static constexpr auto kernel = igemm_kernel<T, BM, BN, WM, WN, KS>;
+};
+template <int BM_, int BN_, int WM, int WN, int KS_, int D> struct DmaBody {
+    static constexpr int BM = BM_, BN = BN_, NT = (BM / WM) * (BN / WN) * 64, SLAB = 32, KS = KS_;
+    static constexpr bool XCD = true;
+    static constexpr auto kernel = igemm_dma_kernel<BM, BN, WM, WN, KS, D>;
+};
+template <int BM_, int BN_, int WM, int WN, int D> struct Dma2Body {
+    static constexpr int BM = BM_, BN = BN_, NT = (BM / WM) * (BN / WN) * 64, SLAB = 64, KS = 1;
+    static constexpr bool XCD = true;
+    static constexpr auto kernel = igemm_dma2_kernel<BM, BN, WM, WN, D>;
+};
+
+// the one launcher of the three bodies: the GEMM grid, and the finishing pass behind a split-K launch
+template <typename B, typename T>
+static int launch_body(const T* xp, const T* wp, T* yp, const T* ap, float* stats, const sba_conv_geom& g, int M,
+                       int split, float* ws, hipStream_t st, const EpiX ex) {
+    const int nslabs = g.ntaps * (g.Cin / B::SLAB);
     int sps = nslabs;
     if (split > 1) {
-        sps = cdiv(cdiv(nslabs, split), KS) * KS;
+        sps = cdiv(cdiv(nslabs, split), B::KS) * B::KS;
         split = cdiv(nslabs, sps);
     }
-    const int gx = cdiv(M, BM), gy = cdiv(g.Cout, BN);
-    const int nmajor = nmajor_for(g);
-    dim3 grid(nmajor ? 8 * cdiv(gy, 8) * gx : 8 * cdiv(gx, 8) * gy, 1, split);
-    SBA_LAUNCH((igemm_dma_kernel<BM, BN, WM, WN, KS, D>), grid, dim3(NT), 0, st, xp, wp, yp, ap, stats, g, M,
-               split > 1 ? ws : (float*)nullptr, sps, ex, gx, gy, nmajor DMA_TRACE_ARG);
+    float* part = split > 1 ? ws : nullptr;
+    const int gx = cdiv(M, B::BM), gy = cdiv(g.Cout, B::BN);
+    if constexpr (B::XCD) {
+        const int nmajor = nmajor_for(g);
+        dim3 grid(nmajor ? 8 * cdiv(gy, 8) * gx : 8 * cdiv(gx, 8) * gy, 1, split);
+        SBA_LAUNCH(B::kernel, grid, dim3(B::NT), 0, st, xp, wp, yp, ap, stats, g, M, part, sps, ex, gx, gy,
+                   nmajor DMA_TRACE_ARG);
+    } else {
+        SBA_LAUNCH(B::kernel, dim3(gx, gy, split), dim3(B::NT), 0, st, xp, wp, yp, ap, stats, g, M, part, sps, ex);
+    }
     if (split > 1) {
         dim3 fgrid(cdiv(g.Cout / 4, 256), cdiv(M, 8));
-        SBA_LAUNCH((splitk_finish_kernel<bf16_t>), fgrid, dim3(256), 0, st, ws, yp, ap, stats, g, M, ex);
+        SBA_LAUNCH((splitk_finish_kernel<T>), fgrid, dim3(256), 0, st, ws, yp, ap, stats, g, M, ex);
     }
-}
-
-template <int BM, int BN, int WM, int WN, int D>
-static void launch_dma2(const bf16_t* xp, const bf16_t* wp, bf16_t* yp, const bf16_t* ap, float* stats,
-                        const sba_conv_geom& g, int M, int nslabs64, int split, float* ws, hipStream_t st, const EpiX ex) {
-    constexpr int NT = (BM / WM) * (BN / WN) * 64;
-    int sps = nslabs64;
-    if (split > 1) {
-        sps = cdiv(nslabs64, split);
-        split = cdiv(nslabs64, sps);
-    }
-    const int gx = cdiv(M, BM), gy = cdiv(g.Cout, BN);
-    const int nmajor = nmajor_for(g);
-    dim3 grid(nmajor ? 8 * cdiv(gy, 8) * gx : 8 * cdiv(gx, 8) * gy, 1, split);
-    SBA_LAUNCH((igemm_dma2_kernel<BM, BN, WM, WN, D>), grid, dim3(NT), 0, st, xp, wp, yp, ap, stats, g, M,
-               split > 1 ? ws : (float*)nullptr, sps, ex, gx, gy, nmajor DMA_TRACE_ARG);
-    if (split > 1) {
-        dim3 fgrid(cdiv(g.Cout / 4, 256), cdiv(M, 8));
-        SBA_LAUNCH((splitk_finish_kernel<bf16_t>), fgrid, dim3(256), 0, st, ws, yp, ap, stats, g, M, ex);
-    }
+    return SBA_CHECK_LAUNCH();
 }
 
 // ---- halo-tile 3x3 path: which geometries qualify, and its launch
@@ -1862,15 +1877,7 @@ int launch_igemm(const void* x, const void* w, void* y, const void* addend, floa
         // bf16: the LDS-DMA staged kernels, and the register-staged 320x128 tile (configuration E) as tile 11
         const bf16_t* xb = (const bf16_t*)x; const bf16_t* wb = (const bf16_t*)w; bf16_t* yb = (bf16_t*)y;
         const bf16_t* ab = (const bf16_t*)addend;
-        // tile ids (include/sbagan_hip.h: sba_conv_geom.tile): BM x BN, slabs per stage, ring depth
-        //   1/2: 64x64 (64 / 128 KB of LDS)   3/4: 96x64 (72 / 144 KB)   5/6: 128x64 (48 / 144 KB)
-        //   7/8: 128x128 (64 / 128 KB)        9/10: 256x64 (60 / 120 KB) 11: 320x128 register-staged   12: 96x128 (120 KB)
-        //   13: 320x64 (5 waves, 150 KB) / 14: 160x64 (5 waves, 120 KB) / 15: 160x64 with a 2-stage ring (60 KB: two
-        //   workgroups per CU): the WHOLE batch of a 4x4 map (M = 16 B = 320) in one
-        //   M tile -- every weight byte is staged once per M tile, so these weight-streaming layers (4..38 MB of weights
-        //   against 320..640 rows) move 1/3..1/5 of the L2->LDS bytes of the 64- / 96-row tiles; Cin % 64 == 0 only
-        // the deep rings keep ~100 KB of loads in flight per CU: an L2-hit load takes ~1 us under load, so a
-        // workgroup alone on its CU moves bytes_in_flight / 1 us (measured 36-42 GB/s with 48 KB in flight)
+        // g.tile: a row of kTiles; the rules name rows 7 / 9 / 5 / 1 / 11 for configurations A / B / C / D / E
         static const int rule_tile[4] = {7, 9, 5, 1};
         int tile = g.tile;
         int split = best_split;
@@ -1892,55 +1899,35 @@ int launch_igemm(const void* x, const void* w, void* y, const void* addend, floa
             int sp = split;
             if (sp > ns64 / 2) sp = ns64 / 2 > 0 ? ns64 / 2 : 1;
             if (plan) { plan[0] = 1; plan[1] = tile; plan[2] = sp; return SBA_OK; }
-            switch (tile) {
-                case 1: launch_dma2<64, 64, 32, 32, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 2: launch_dma2<64, 64, 32, 32, 8>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 3: launch_dma2<96, 64, 32, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 4: launch_dma2<96, 64, 32, 64, 6>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 5: launch_dma2<128, 64, 32, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 6: launch_dma2<128, 64, 32, 64, 6>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 7: launch_dma2<128, 128, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 8: launch_dma2<128, 128, 64, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 9: launch_dma2<256, 64, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 10: launch_dma2<256, 64, 64, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 13: launch_dma2<320, 64, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 14: launch_dma2<160, 64, 32, 64, 4>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 15: launch_dma2<160, 64, 32, 64, 2>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 16: launch_dma2<256, 128, 128, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 17: launch_dma2<256, 128, 64, 64, 3>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                case 18: launch_dma2<256, 128, 128, 64, 2>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-                default: launch_dma2<96, 128, 32, 128, 5>(xb, wb, yb, ab, stats, g, M, ns64, sp, ws, st, ex); return SBA_CHECK_LAUNCH();
-            }
+            return with_tile(tile, [&](auto id) {
+                constexpr IgemmTile t = kTiles[decltype(id)::value];
+                if constexpr (t.d2 > 0)
+                    return launch_body<Dma2Body<t.bm, t.bn, t.wm, t.wn, t.d2>>(xb, wb, yb, ab, stats, g, M, sp, ws, st, ex);
+                else return SBA_E_ARG;
+            });
         }
-        if (plan && tile != 11) { plan[0] = 2; plan[1] = tile; plan[2] = split; return SBA_OK; }
-        switch (tile) {
-            case 1: launch_dma<64, 64, 32, 32, 2, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 2: launch_dma<64, 64, 32, 32, 2, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 3: launch_dma<96, 64, 32, 64, 2, 3>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 4: launch_dma<96, 64, 32, 64, 2, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 5: launch_dma<128, 64, 32, 64, 1, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 6: launch_dma<128, 64, 32, 64, 2, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 7: launch_dma<128, 128, 64, 64, 1, 4>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 8: launch_dma<128, 128, 64, 64, 1, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 9: launch_dma<256, 64, 64, 64, 1, 3>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 10: launch_dma<256, 64, 64, 64, 1, 6>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            case 12: launch_dma<96, 128, 32, 128, 1, 8>(xb, wb, yb, ab, stats, g, M, nslabs, split, ws, st, ex); return SBA_CHECK_LAUNCH();
-            default: break;
+        if (tile != 11) {       // (ids >= 13 never get here: they went back to the rules above)
+            if (plan) { plan[0] = 2; plan[1] = tile; plan[2] = split; return SBA_OK; }
+            return with_tile(tile, [&](auto id) {
+                constexpr IgemmTile t = kTiles[decltype(id)::value];
+                if constexpr (t.d1 > 0)
+                    return launch_body<DmaBody<t.bm, t.bn, t.wm, t.wn, t.ks1, t.d1>>(xb, wb, yb, ab, stats, g, M, split, ws, st, ex);
+                else return SBA_E_ARG;
+            });
         }
         // tile 11: the register-staged 320x128 tile (configuration E)
         if (plan) { plan[0] = 3; plan[1] = 4; plan[2] = split; return SBA_OK; }
-        launch_cfg<T, 320, 128, 64, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, split, ws, st, ex);
-        return SBA_CHECK_LAUNCH();
+        constexpr IgemmTile e = kTiles[11];
+        return launch_body<RegBody<T, e.bm, e.bn, e.wm, e.wn, e.ks1>>(xp, wp, yp, ap, stats, g, M, split, ws, st, ex);
     } else {
         if (plan) { plan[0] = 3; plan[1] = best; plan[2] = best_split; return SBA_OK; }
         switch (best) {
-            case 0: launch_cfg<T, 128, 128, 64, 64, 1>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-            case 1: launch_cfg<T, 256, 64, 64, 64, 1>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-            case 2: launch_cfg<T, 128, 64, 32, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-            case 3: launch_cfg<T, 64, 64, 32, 32, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
-            default: launch_cfg<T, 320, 128, 64, 64, 2>(xp, wp, yp, ap, stats, g, M, nslabs, best_split, ws, st, ex); break;
+            case 0: return launch_body<RegBody<T, 128, 128, 64, 64, 1>>(xp, wp, yp, ap, stats, g, M, best_split, ws, st, ex);
+            case 1: return launch_body<RegBody<T, 256, 64, 64, 64, 1>>(xp, wp, yp, ap, stats, g, M, best_split, ws, st, ex);
+            case 2: return launch_body<RegBody<T, 128, 64, 32, 64, 2>>(xp, wp, yp, ap, stats, g, M, best_split, ws, st, ex);
+            case 3: return launch_body<RegBody<T, 64, 64, 32, 32, 2>>(xp, wp, yp, ap, stats, g, M, best_split, ws, st, ex);
+            default: return launch_body<RegBody<T, 320, 128, 64, 64, 2>>(xp, wp, yp, ap, stats, g, M, best_split, ws, st, ex);
         }
-        return SBA_CHECK_LAUNCH();
     }
 }
 
@@ -2155,21 +2142,20 @@ static int group_dispatch(int dtype, int n, const sba_conv_group_item* items, in
     if (ksplit > 1 && (!workspace || need > ws_bytes || ((uintptr_t)workspace & 15) || !all64 || sba_det_on())) ksplit = 1;
     if (ksplit < 1) ksplit = 1;
     float* ws = (float*)workspace;
-    if (all64) {        // 64-channel slabs, second-generation body
-        switch (tile) {
-            case 0: case 1: return launch_group<64, 64, 32, 32, 4>(items, n, st, ksplit, ws);
-            case 3: return launch_group<96, 64, 32, 64, 3>(items, n, st, ksplit, ws);
-            case 5: return launch_group<128, 64, 32, 64, 3>(items, n, st, ksplit, ws);
-            case 7: return launch_group<128, 128, 64, 64, 3>(items, n, st, ksplit, ws);
-            default: return SBA_E_ARG;
-        }
-    }
-    switch (tile) {     // some member has Cin % 64 == 32: 32-channel slabs for the whole group
-        case 0: case 1: return launch_group<64, 64, 32, 32, 4, 2>(items, n, st);
-        case 3: return launch_group<96, 64, 32, 64, 3, 2>(items, n, st);
-        case 5: case 7: return launch_group<128, 64, 32, 64, 4, 1>(items, n, st);
-        default: return SBA_E_ARG;
-    }
+    return with_tile(tile ? tile : 1, [&](auto id) {
+        constexpr IgemmTile t = kTiles[decltype(id)::value], m = kTiles[t.group];
+        if constexpr (t.group == 0) return SBA_E_ARG;
+        // 64-channel slabs, second-generation body; some member with Cin % 64 == 32: 32-channel slabs for the whole group
+        else return all64 ? launch_group<t.bm, t.bn, t.wm, t.wn, t.d2>(items, n, st, ksplit, ws)
+                          : launch_group<m.bm, m.bn, m.wm, m.wn, m.d1, m.ks1>(items, n, st);
+    });
+}
+
+extern "C" int sba_conv_igemm_tile_shape(int tile, int* bm, int* bn) {
+    if (tile < 1 || tile > SBA_IGEMM_TILES || !bm || !bn) return SBA_E_ARG;
+    *bm = kTiles[tile].bm;
+    *bn = kTiles[tile].bn;
+    return SBA_OK;
 }
 
 extern "C" int sba_conv_igemm_group(int dtype, int n, const sba_conv_group_item* items, int tile, void* stream) {

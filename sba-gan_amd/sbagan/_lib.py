@@ -55,6 +55,7 @@ SIGNATURES = {
     'sba_conv_igemm': [I, P, P, P, P, P, G, P, L, P],
     'sba_conv_igemm_bias': [I, P, P, P, P, P, P, P, G, P, L, P],
     'sba_conv_igemm_plan': [I, G, L, POINTER(c_int)],
+    'sba_conv_igemm_tile_shape': [I, POINTER(c_int), POINTER(c_int)],
     'sba_fold_bn_pack': [I, P, P, P, P, P, F, P, P, I, I, I, I, P],
     'sba_conv_igemm_glu': [I, P, P, P, P, I, G, P],
     'sba_conv_igemm_glu_plan': [I, G, I, POINTER(c_int)],

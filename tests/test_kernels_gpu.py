@@ -362,7 +362,8 @@ def test_register_weight_halo_kernel_general(dev, geom):
 # sba_conv_geom.tile / .ksplit (include/sbagan_hip.h) pick the kernel instantiation; the measured table only ever uses a
 # few per shape, so each id is forced here on the weight-streaming shapes of the discriminator tails (model.py:560-607:
 # 4x4 maps, M = 16 B rows): one full 320-row tile, a ragged one (B - 1 = 19 images), two M tiles, a ragged 5x5 map.
-SKINNY_CASES = [(20, 4, 128, 192), (19, 4, 64, 72), (40, 4, 128, 64), (7, 5, 192, 136)]
+# The last two have Cin % 64 == 32: ids 1..12 are then the first-generation LDS-DMA kernels (32-channel slabs).
+SKINNY_CASES = [(20, 4, 128, 192), (19, 4, 64, 72), (40, 4, 128, 64), (7, 5, 192, 136), (20, 4, 96, 192), (7, 5, 160, 72)]
 
 
 @pytest.mark.parametrize('case', SKINNY_CASES)

@@ -10,6 +10,7 @@ inputs from oracle/fill.py, and only numeric outputs are written.
     python tools/make_golden.py            # all fixtures
     python tools/make_golden.py units      # just the reduced-size units
     python tools/make_golden.py infer      # the eval-mode generator fixtures (infer_*.npz)
+    SBA_LIB_PATH=<parent build> python tools/make_golden.py igemm_plan     # the kernel-choice recording
 """
 import os
 import sys
@@ -408,10 +409,29 @@ def gen_infer(ref):
         print('%s: %d arrays, %d bytes' % (name, len(S), os.path.getsize(os.path.join(OUT, name))))
 
 
+def gen_igemm_plan():
+    """igemm_plan.npz: the answers of sba_conv_igemm_plan / sba_conv_igemm_glu_plan on the grids of
+    tests/test_igemm_plan_cpu.py.  The recording is only worth something from a library that is NOT the code under
+    test: point SBA_LIB_PATH at a libsbagan_hip.so built from the parent commit."""
+    assert os.environ.get('SBA_LIB_PATH'), 'set SBA_LIB_PATH to a library built from the parent commit'
+    sys.path[:0] = [os.path.join(ROOT, 'sba-gan_amd'), os.path.join(ROOT, 'tests')]
+    import test_igemm_plan_cpu as T
+    from sbagan import _lib
+    S = T.replay(_lib)
+    np.savez_compressed(T.GOLDEN, **S)
+    print('igemm_plan.npz from %s: %s, %d bytes' % (_lib.LIB_PATH, {k: len(v) for k, v in S.items()},
+                                                     os.path.getsize(T.GOLDEN)))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     what = sys.argv[1:] or ['units', 'step_tiny', 'step_full']
     torch.set_num_threads(8)
+    if 'igemm_plan' in what:            # (needs no reference)
+        gen_igemm_plan()
+        what = [w for w in what if w != 'igemm_plan']
+        if not what:
+            return
     ref = load_reference()
     if 'text' in what:
         gen_text(ref)

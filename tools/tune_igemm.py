@@ -14,10 +14,6 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import torch  # noqa: E402
 
-NTILES = 18
-TILE_BM = {1: 64, 2: 64, 3: 96, 4: 96, 5: 128, 6: 128, 7: 128, 8: 128, 9: 256, 10: 256, 11: 320, 12: 96, 13: 320, 14: 160, 15: 160, 16: 256, 17: 256, 18: 256}
-TILE_BN = {1: 64, 2: 64, 3: 64, 4: 64, 5: 64, 6: 64, 7: 128, 8: 128, 9: 64, 10: 64, 11: 128, 12: 128, 13: 64, 14: 64, 15: 64, 16: 128, 17: 128, 18: 128}
-
 
 def main():
     sys.argv += ['--child']
@@ -25,7 +21,7 @@ def main():
     torch.cuda.set_device(0)
     dev = torch.device('cuda:0')
     from sbagan import ops
-    from sbagan._lib import ConvGeom, call
+    from sbagan._lib import IGEMM_TILES, ConvGeom, call
     from sbagan.synth import synthetic_batch
     os.environ['SBA_IGEMM_TABLE'] = '0'
     step = bench.build(args, dev)
@@ -104,8 +100,10 @@ def main():
             return best
         t_rule = timeit(0, 0)
         cands = []
-        for tile in range(1, NTILES + 1):
-            bm, bn = TILE_BM[tile], TILE_BN[tile]
+        c_bm, c_bn = ctypes.c_int(), ctypes.c_int()
+        for tile in range(1, IGEMM_TILES + 1):
+            call('sba_conv_igemm_tile_shape', tile, ctypes.byref(c_bm), ctypes.byref(c_bn))
+            bm, bn = c_bm.value, c_bn.value
             if bm >= 2 * M + 64 or (bn == 128 and g.Cout <= 64) or (tile in (13, 14, 15) and (g.Cin % 64 or M > 4096)) or (tile >= 16 and (g.Cin % 64 or M < 2048)):
                 continue
             tiles = -(-M // bm) * -(-g.Cout // bn)
