@@ -198,6 +198,15 @@ int sba_conv_igemm_group_splitk(int dtype, int n, const sba_conv_group_item* ite
  * ksplit > 1 splits the pixel range over that many workgroups (atomic accumulation). */
 int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* dw, const sba_conv_geom* g,
                    int ksplit, void* stream);
+/* The launch sba_conv_wgrad makes for a geometry (g->first_write included), with the deterministic mode on (det != 0)
+ * or off; nothing is launched, no device is needed.  plan[0] = family: 0 wgrad_row_dma_kernel, 1 wgrad_small_dma_kernel,
+ * 2 wgrad_small_kernel, 3 wgrad_rows_kernel, 4 wgrad_kernel; plan[1..4] = template arguments (family 0: KW, SX, XB, D;
+ * family 1: CT, D; the others: the dtype); plan[5..7] = grid x / y / z (z = pixel splits); plan[8] = threads;
+ * plan[9] = dynamic LDS bytes; plan[10] = pixel chunks (family 3: 64-pixel row segments) per split; plan[11] = epilogue
+ * mode: 0 dw += sum, 1 f32 atomics, 2 store; plan[12] = partial tensors the deterministic mode folds in order (0 = none);
+ * plan[13] = family 0: log2 of the output columns of a 32-pixel chunk. */
+#define SBA_WGRAD_PLAN_INTS 14
+int sba_conv_wgrad_plan(int dtype, const sba_conv_geom* g, int ksplit, int det, int* plan);
 /* weight packing: master f32 [Cout][KH][KW][Cin] (= torch channels_last storage of an OIHW
  * parameter) -> packed `dtype` weights.  mode 0: same order (cast).  mode 1: data-gradient
  * weights of a stride-1 'same' conv: out[ci][KH-1-kh][KW-1-kw][co].  mode 2: data-gradient of

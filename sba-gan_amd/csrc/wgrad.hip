@@ -23,6 +23,77 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
 }
 
 // ---------------------------------------------------------------------------
+// Head and tail shared by the kernels below.  (The tap lookup, the buffer-resource setup and the ring driver of the two
+// LDS-DMA kernels, and the epilogue of wgrad_row_dma_kernel stay written out in their kernels: as helpers they changed
+// the kernels' VGPR / SGPR counts -- profiles/wgrad_plan_refactor.txt.)
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void zero_acc(f32x16_t (&acc)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+template <int N> __device__ __forceinline__ void zero_acc(f32x16_t (&acc)[N][2][2]) {
+#pragma unroll
+    for (int s = 0; s < N; ++s) zero_acc(acc[s]);
+}
+
+// output pixel m -> (n, oy, ox) on a map of `sub` = rows x `ow` pixels per image
+__device__ __forceinline__ void pixel_decode(const int m, const int sub, const int ow, const FastDiv& dsub, const FastDiv& dow,
+                                             int& n, int& oy, int& ox) {
+    n = (int)fdiv(m, dsub);
+    const int rem = m - n * sub;
+    oy = (int)fdiv(rem, dow);
+    ox = rem - oy * ow;
+}
+
+// the input pixel tap (ty, tx) of output pixel (n, oy, ox) reads: false = padding; IHL x IWL = the map the taps walk on
+// (the upsampled one behind a nearest x2 upsample)
+__device__ __forceinline__ bool x_gather(const sba_conv_geom& g, const int IHL, const int IWL, const int n, const int oy, const int ox,
+                                         const int ty, const int tx, int64_t& pix) {
+    int iy = oy * g.sy + ty, ix = ox * g.sx + tx;
+    const bool ok = (iy >= 0) & (iy < IHL) & (ix >= 0) & (ix < IWL);
+    if (g.ups) { iy >>= 1; ix >>= 1; }
+    pix = (int64_t)(n * g.IH + iy) * g.IW + ix;
+    return ok;
+}
+__device__ __forceinline__ int64_t dy_pixel(const sba_conv_geom& g, const int n, const int oy, const int ox) {
+    return (int64_t)(n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
+}
+
+// one element of dw: mode 0 = +=, 1 = f32 atomic (pixel splits), 2 = store (first write of a cleared gradient, or a
+// deterministic-mode partial tensor)
+__device__ __forceinline__ void dw_emit(float* p, const float v, const int mode) {
+    if (mode == 1) atomicAdd(p, v);
+    else if (mode == 2) *p = v;
+    else *p += v;
+}
+// a wave's 64(co) x 64(ci) accumulator tile of tap `tap` -> dwz[co][tap][ci]
+// (OWNER = false: wgrad_rows_kernel, whose waves never own dw -- atomics or store only)
+template <bool OWNER>
+__device__ __forceinline__ void store_tile(const f32x16_t (&acc)[2][2], float* dwz, const sba_conv_geom& g, const int co0,
+                                           const int ci0, const int tap, const int mode, const int lane) {
+    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = co0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
+                const int ci = ci0 + j * 32 + col_l;
+                if (co < g.Cout && ci < g.Cin) {
+                    float* p = dwz + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
+                    if (OWNER) dw_emit(p, acc[i][j][r], mode);
+                    else if (mode == 2) *p = acc[i][j][r];
+                    else atomicAdd(p, acc[i][j][r]);
+                }
+            }
+}
+
+// ---------------------------------------------------------------------------
 // weight gradient: dw[co][tap][ci] += sum_pixels dy[pixel][co] * x[gather(pixel,tap)][ci]
 // Workgroup = one 64(co) x 64(ci) tile of one tap; its 4 waves each walk their
 // own 16-pixel slices of the workgroup's pixel range, then reduce through LDS.
@@ -88,7 +159,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                     float* __restrict__ dw, const sba_conv_geom g,
                                                     const int M, const int chunks_per_split,
-                                                    const int use_atomic, const FastDiv dsub, const FastDiv dow,
+                                                    const int mode, const FastDiv dsub, const FastDiv dow,
                                                     const int64_t zstride) {
     constexpr int ROWS = WgFrag<T>::ROWS;
     constexpr int CH = 16 / (int)sizeof(T);          // elements per 16-byte chunk
@@ -113,12 +184,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ x, con
     unsigned char* sb = sa + SLICE;
 
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int chunk_lo = blockIdx.z * chunks_per_split;
     const int total_chunks = (M + 63) / 64;
@@ -135,21 +201,14 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ x, con
             va[u] = make_uint4(0, 0, 0, 0);
             vb[u] = make_uint4(0, 0, 0, 0);
             if (m < M) {
-                const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
+                int n, oy, ox;
+                pixel_decode(m, sub, g.OWs, dsub, dow, n, oy, ox);
                 const int co = co0 + cc * CH;
-                if (co < g.Cout) {
-                    const int64_t po = (int64_t)(n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
-                    va[u] = *reinterpret_cast<const uint4*>(dy + po * g.Cout + co);
-                }
-                int iy = oy * g.sy + ty, ix = ox * g.sx + tx;
-                const bool ok = (iy >= 0) & (iy < IHL) & (ix >= 0) & (ix < IWL);
-                if (g.ups) { iy >>= 1; ix >>= 1; }
+                if (co < g.Cout) va[u] = *reinterpret_cast<const uint4*>(dy + dy_pixel(g, n, oy, ox) * g.Cout + co);
+                int64_t pi;
+                const bool ok = x_gather(g, IHL, IWL, n, oy, ox, ty, tx, pi);
                 const int ci = ci0 + cc * CH;
-                if (ok && ci < g.Cin) {
-                    const int64_t pi = (int64_t)(n * g.IH + iy) * g.IW + ix;
-                    vb[u] = *reinterpret_cast<const uint4*>(x + pi * g.Cin + ci);
-                }
+                if (ok && ci < g.Cin) vb[u] = *reinterpret_cast<const uint4*>(x + pi * g.Cin + ci);
             }
         }
     };
@@ -192,10 +251,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ x, con
     for (int i = tid; i < 64 * 64; i += 256) {
         const int co = co0 + (i >> 6), ci = ci0 + (i & 63);
         if (co < g.Cout && ci < g.Cin) {
-            float* p = dwz + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-            if (use_atomic == 1) atomicAdd(p, red[i]);
-            else if (use_atomic == 2) *p = red[i];
-            else *p += red[i];
+            dw_emit(dwz + ((int64_t)co * g.ntaps + tap) * g.Cin + ci, red[i], mode);
         }
     }
 }
@@ -211,7 +267,7 @@ template <typename T>
 __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                           float* __restrict__ dw, const sba_conv_geom g,
                                                           const int M, const int chunks_per_split,
-                                                          const int use_atomic, const FastDiv dsub,
+                                                          const int mode, const FastDiv dsub,
                                                           const FastDiv dow, const int64_t zstride) {
     constexpr int ROWS = WgFrag<T>::ROWS;
     constexpr int CH = 16 / (int)sizeof(T);
@@ -239,12 +295,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
     unsigned char* sb = lds + (1 + wid) * SLICE;
 
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int total_chunks = (M + 15) / 16;
     const int chunk_lo = blockIdx.z * chunks_per_split;
@@ -261,10 +312,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
                 const int pix = idx / CPR, cc = idx - pix * CPR;
                 const int m = m0 + pix, co = co0 + cc * CH;
                 if (m < M && co < g.Cout) {
-                    const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                    const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
-                    const int64_t po = (int64_t)(n * g.OH + oy * g.osy + g.ooy) * g.OW + ox * g.osx + g.oox;
-                    va[u] = *reinterpret_cast<const uint4*>(dy + po * g.Cout + co);
+                    int n, oy, ox;
+                    pixel_decode(m, sub, g.OWs, dsub, dow, n, oy, ox);
+                    va[u] = *reinterpret_cast<const uint4*>(dy + dy_pixel(g, n, oy, ox) * g.Cout + co);
                 }
             }
         }
@@ -275,16 +325,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
             const int m = m0 + pix;
             vb[u] = make_uint4(0, 0, 0, 0);
             if (active && m < M) {
-                const int n = (int)fdiv(m, dsub), rem = m - n * sub;
-                const int oy = (int)fdiv(rem, dow), ox = rem - oy * g.OWs;
-                int iy = oy * g.sy + ty, ix = ox * g.sx + tx;
-                const bool ok = (iy >= 0) & (iy < IHL) & (ix >= 0) & (ix < IWL);
-                if (g.ups) { iy >>= 1; ix >>= 1; }
+                int n, oy, ox;
+                pixel_decode(m, sub, g.OWs, dsub, dow, n, oy, ox);
+                int64_t pi;
+                const bool ok = x_gather(g, IHL, IWL, n, oy, ox, ty, tx, pi);
                 const int ci = ci0 + cc * CH;
-                if (ok && ci < g.Cin) {
-                    const int64_t pi = (int64_t)(n * g.IH + iy) * g.IW + ix;
-                    vb[u] = *reinterpret_cast<const uint4*>(x + pi * g.Cin + ci);
-                }
+                if (ok && ci < g.Cin) vb[u] = *reinterpret_cast<const uint4*>(x + pi * g.Cin + ci);
             }
         }
     };
@@ -311,22 +357,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(const T* __restrict
     }
 
     if (!active) return;
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                const int ci = ci0 + j * 32 + col_l;
-                if (co < g.Cout && ci < g.Cin) {
-                    float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-                    if (use_atomic == 1) atomicAdd(p, acc[i][j][r]);
-                    else if (use_atomic == 2) *p = acc[i][j][r];       // first write of a cleared gradient
-                    else *p += acc[i][j][r];
-                }
-            }
+    store_tile<true>(acc, dw + (int64_t)blockIdx.z * zstride, g, co0, ci0, tap, mode, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -362,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_dma_kernel(const bf16_t* _
                                                               const bf16_t* __restrict__ dy,
                                                               float* __restrict__ dw, const sba_conv_geom g,
                                                               const int M, const int chunks_per_split,
-                                                              const int use_atomic, const FastDiv dsub,
+                                                              const int mode, const FastDiv dsub,
                                                               const FastDiv dow, const int64_t zstride) {
     constexpr int SL = 32 * 128;                 // one slice: 32 pixels x 64 channels
     constexpr int STAGE = (CT + 4) * SL;         // [dy slices (shared)] [x slice of wave 0..3]
@@ -438,14 +469,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_dma_kernel(const bf16_t* _
     };
 
     f32x16_t acc[CT][2][2];
-#pragma unroll
-    for (int s = 0; s < CT; ++s)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[s][i][j][r] = 0.f;
+    zero_acc(acc);
 
     int islot = 0;
 #pragma unroll
@@ -482,24 +506,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_dma_kernel(const bf16_t* _
     wg_barrier();
 
     if (!active) return;
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
 #pragma unroll
     for (int s = 0; s < CT; ++s)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + s * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                    const int ci = ci0 + j * 32 + col_l;
-                    if (co < g.Cout && ci < g.Cin) {
-                        float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * g.ntaps + tap) * g.Cin + ci;
-                        if (use_atomic == 1) atomicAdd(p, acc[s][i][j][r]);
-                        else if (use_atomic == 2) *p = acc[s][i][j][r];       // first write of a cleared gradient
-                        else *p += acc[s][i][j][r];
-                    }
-                }
+        store_tile<true>(acc[s], dw + (int64_t)blockIdx.z * zstride, g, co0 + s * 64, ci0, tap, mode, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -645,12 +654,7 @@ __global__ __launch_bounds__(64 * KW, 2) void wgrad_row_dma_kernel(const bf16_t*
     };
 
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     int islot = 0;
 #pragma unroll
@@ -712,7 +716,7 @@ template <typename T>
 __global__ __launch_bounds__(192) void wgrad_rows_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                          float* __restrict__ dw, const sba_conv_geom g,
                                                          const int total_segs, const int segs_per_wg,
-                                                         const int store, const int64_t zstride) {
+                                                         const int mode, const int64_t zstride) {
     constexpr int ROWS = WgFrag<T>::ROWS;
     constexpr int CH = 16 / (int)sizeof(T);
     constexpr int CPR = 64 / CH;                       // 16-byte chunks per 64-channel pixel row
@@ -733,14 +737,7 @@ __global__ __launch_bounds__(192) void wgrad_rows_kernel(const T* __restrict__ x
         *reinterpret_cast<uint4*>(sx + XR * ROWS + i * 16) = make_uint4(0, 0, 0, 0);
 
     f32x16_t acc[3][2][2];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int seg_lo = blockIdx.z * segs_per_wg;
     const int seg_hi = min(seg_lo + segs_per_wg, total_segs);
@@ -813,51 +810,56 @@ __global__ __launch_bounds__(192) void wgrad_rows_kernel(const T* __restrict__ x
         }
     }
 
-    const int col_l = lane & 31, rsel = 4 * (lane >> 5);
+    // (mode 1, f32 atomics: the three waves of a workgroup never own dw; mode 2: deterministic mode, the split's own partial tensor)
 #pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-        const int tap = kh * 3 + kw;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + i * 32 + (r & 3) + 8 * (r >> 2) + rsel;
-                    const int ci = ci0 + j * 32 + col_l;
-                    if (co < g.Cout && ci < g.Cin) {
-                        float* p = dw + (int64_t)blockIdx.z * zstride + ((int64_t)co * 9 + tap) * g.Cin + ci;
-                        if (store) *p = acc[kw][i][j][r];       // deterministic mode: this split's own partial tensor
-                        else atomicAdd(p, acc[kw][i][j][r]);
-                    }
-                }
-    }
+    for (int kw = 0; kw < 3; ++kw)
+        store_tile<false>(acc[kw], dw + (int64_t)blockIdx.z * zstride, g, co0, ci0, kh * 3 + kw, mode, lane);
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------
+// Host side: wgrad_plan decides (pure: no global state, no device), wgrad_launch does what the plan says.
+// ---------------------------------------------------------------------------
+enum WgradFamily { WG_ROW_DMA = 0, WG_SMALL_DMA = 1, WG_SMALL = 2, WG_ROWS = 3, WG_GENERIC = 4 };
 
-extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* dw, const sba_conv_geom* g,
-                              int ksplit, void* stream) {
-    if (!x || !dy || !dw || !geom_ok(g, dtype)) return SBA_E_ARG;
-    if (g->Cin % 8 != 0 || g->Cout % 8 != 0) return SBA_E_ARG;
-    if (g->x_cstride || g->x_coff || g->y_cstride || g->y_coff || g->ntaps > 16) return SBA_E_ARG;
+struct WgradPlan {
+    int family;
+    int v[4];           // template arguments: row-DMA <KW, SX, XB, D>, small-DMA <CT, D>; the other families: the dtype
+    dim3 grid;          // z = pixel splits
+    int block, lds;     // threads, dynamic LDS bytes
+    int per_split;      // chunks (wgrad_rows_kernel: 64-pixel segments) per pixel split
+    int mode;           // epilogue: 0 = +=, 1 = f32 atomics, 2 = store
+    int npart;          // deterministic mode: partial tensors folded in order by sba_det_fold (0 = none)
+    int wclog;          // row-DMA: log2 of the output columns of a 32-pixel chunk
+};
+
+// Pixel splits of a grid of `wgs` workgroups over `chunks` chunks of pixels: fill `target_wgs`, keep >= `min_chunks`
+// behind every split (each split costs a full f32-atomic copy of dW), then even the splits out.
+static int pixel_splits(int target_wgs, int wgs, int chunks, int min_chunks, int* per_split) {
+    int sp = cdiv(target_wgs, wgs);
+    if (sp > chunks / min_chunks) sp = chunks / min_chunks > 0 ? chunks / min_chunks : 1;
+    *per_split = cdiv(chunks, sp);
+    return cdiv(chunks, *per_split);
+}
+
+static bool wgrad_plan(int dtype, const sba_conv_geom* g, int ksplit, bool det_on, WgradPlan* p) {
+    if (!geom_ok(g, dtype)) return false;
+    if (g->Cin % 8 != 0 || g->Cout % 8 != 0) return false;
+    if (g->x_cstride || g->x_coff || g->y_cstride || g->y_coff || g->ntaps > 16) return false;
     const int M = g->N * g->OHs * g->OWs;
     if (ksplit < 1) ksplit = 1;
-    const int fw = g->first_write ? 2 : 0;       // epilogue mode of the exclusive-owner kernels: 0 = +=, 1 = atomic, 2 = store
+    const int fw = g->first_write ? 2 : 0;       // epilogue mode of an unsplit launch of the exclusive-owner kernels
     const int co_tiles = cdiv(g->Cout, 64), items = cdiv(g->Cin, 64) * g->ntaps;
-    const FastDiv dsub = make_fastdiv((uint32_t)(g->OHs * g->OWs), (int64_t)M + 64);
-    const FastDiv dow = make_fastdiv((uint32_t)g->OWs, (int64_t)M + 64);
+    // the LDS-DMA kernels address x and dy with 32-bit byte offsets (x: geom_ok has checked it, x_cstride == 0 here)
+    const bool dma_ok = dtype == SBA_BF16 && (int64_t)g->N * g->OH * g->OW * g->Cout * 2 < (1ll << 32);
     // Deterministic mode: pixel splits do not meet in f32 atomics -- split z STORES its partial gradient into its own
     // tensor of the scratch ring (mode 2, offset z * zstride) and sba_det_fold adds the splits up in order.
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t dwn = (int64_t)g->Cout * g->ntaps * g->Cin;
-    float* part = nullptr;
-    auto det_begin = [&](int nsplit) -> bool {
-        part = nullptr;
-        if (sba_det_on() && nsplit > 1) { part = sba_det_alloc((int64_t)nsplit * dwn); return part != nullptr; }
-        return true;
+    auto fill = [&](int family, int v0, int v1, int v2, int v3, dim3 grid, int block, int lds, int per_split, int unsplit_mode) {
+        *p = WgradPlan{family, {v0, v1, v2, v3}, grid, block, lds, per_split, 0, 0, 0};
+        const int nz = (int)grid.z;
+        p->npart = det_on && (nz > 1 || family == WG_ROWS) ? nz : 0;       // (wgrad_rows_kernel: its three waves never own dw)
+        p->mode = p->npart ? 2 : (nz > 1 ? 1 : unsplit_mode);
+        return grid.y <= 65535 && grid.z <= 65535;
     };
-    auto det_end = [&](int nsplit) { if (part) sba_det_fold(part, 1, nsplit, dwn, dw, 0, fw == 2 ? 1 : 0, st); };
     // Kernel-row decomposition (wgrad_row_dma_kernel): the kw taps of a kernel row share one staged input row segment.
     // 4x4 / stride-2 down blocks, and 3x3 / stride-1 convs on maps of 8 x 8 .. -- also in the all-taps halo-row kernel's
     // range and behind the nearest x2 upsample (G upsample1..4 73 / 92 / 102 / 80 -> 41 / 56 / 55 / 53 us, upBlock -> 128 px
@@ -867,76 +869,49 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
     // 38.1 -> 27.3, 512->1024 4x4/s2 35.8 -> 27.9.
     {
         const int kwn = g->ntaps == 16 ? 4 : (g->ntaps == 9 ? 3 : 0), sxy = g->sx;
-        bool ok = dtype == SBA_BF16 && kwn && g->sy == sxy && (!g->ups || kwn == 3) && g->osy == 1 && g->osx == 1 && g->ooy == 0 &&
+        bool ok = dma_ok && kwn && g->sy == sxy && (!g->ups || kwn == 3) && g->osy == 1 && g->osx == 1 && g->ooy == 0 &&
                   g->oox == 0 && g->OHs == g->OH && g->OWs == g->OW && g->Cin % 64 == 0 && g->Cout % 64 == 0 &&
                   g->OW >= 4 && (g->OW & (g->OW - 1)) == 0 && !(g->OW == 4 && (g->ups || g->OH != 4)) && M % 32 == 0 &&
                   ((g->OH * g->OW) % 32 == 0 || g->OW == 4);
         ok = ok && ((kwn == 4 && sxy == 2) || (kwn == 3 && sxy == 1));
         for (int t = 0; t < g->ntaps && ok; ++t)
             ok = g->ty[t] == g->ty[(t / kwn) * kwn] && g->tx[t] == g->tx[(t / kwn) * kwn] + (t % kwn);
-        const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
-        if (ok && xb < (1ll << 32) && db < (1ll << 32)) {
+        if (ok) {
             const int wc = g->OW < 32 ? g->OW : 32;
             int wclog = 0;
             while ((1 << wclog) < wc) ++wclog;
             const int wgs = co_tiles * kwn * (g->Cin / 64);
-            const int tc32 = M / 32;
             // pixel splits: each one adds a full f32-atomic copy of dW (~1.3 TB/s chip-wide): fill the chip about twice,
             // keep >= 12 chunks behind a copy
             // (tools/bench_wgrad.py, B = 40: 128->256 @64 71 us at 512 workgroups, 78 at 384, 94 at 256; the 64->128 layers,
             // 8 workgroups per split: @128 89 / 86 / 94, @64 42 / 37 / 36)
             constexpr int ROW_WGS = 512;
-            int sp = cdiv(wgs <= 8 ? (ROW_WGS * 3) / 4 : ROW_WGS, wgs);
-            if (sp > tc32 / 12) sp = tc32 / 12 > 0 ? tc32 / 12 : 1;
-            const int cps32 = cdiv(tc32, sp);
-            sp = cdiv(tc32, cps32);
-            dim3 gd(co_tiles, kwn * (g->Cin / 64), sp);
-            if (gd.y <= 65535 && gd.z <= 65535) {
-                if (!det_begin(sp)) return SBA_E_ARG;
-                float* dwa = part ? part : dw;
-                const int md = part ? 2 : (sp > 1 ? 1 : fw);
-                const int64_t zs = part ? dwn : 0;
-                // (ring depth: 3 and 4 measure the same, 6 is 30-60 % slower -- occupancy: profiles/r04_wgrad_s2_rows.txt)
-                if (kwn == 4) {         // x segment: <= 72 rows (OW >= 8), 80 rows (two 4 x 4 maps)
-                    constexpr int LDS = 4 * WgRowCfg<4, 10>::STAGE;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<4, 2, 10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_row_dma_kernel<4, 2, 10, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
-                } else if (g->OW == 4) {       // 8 rows x 6 = 48 rows
-                    constexpr int LDS = 4 * WgRowCfg<3, 6>::STAGE;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<3, 1, 6, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_row_dma_kernel<3, 1, 6, 4>), gd, dim3(192), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
-                } else {                       // <= 40 rows
-                    constexpr int LDS = 4 * WgRowCfg<3, 5>::STAGE;
-                    static bool once = false;
-                    if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_row_dma_kernel<3, 1, 5, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                    SBA_LAUNCH((wgrad_row_dma_kernel<3, 1, 5, 4>), gd, dim3(192), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs, wclog);
-                }
-                det_end(sp);
-                return SBA_CHECK_LAUNCH();
+            int cps32;
+            const int sp = pixel_splits(wgs <= 8 ? (ROW_WGS * 3) / 4 : ROW_WGS, wgs, M / 32, 12, &cps32);
+            // x segment of a stage: <= 72 rows (4x4 / stride 2, OW >= 8) or 80 rows (two 4 x 4 maps): XB = 10; 3x3 on a
+            // 4 x 4 map: 8 rows x 6 = 48 rows: XB = 6; 3x3 otherwise <= 40 rows: XB = 5
+            // (ring depth: 3 and 4 measure the same, 6 is 30-60 % slower -- occupancy: profiles/r04_wgrad_s2_rows.txt)
+            const int xb = kwn == 4 ? 10 : (g->OW == 4 ? 6 : 5);
+            const int stage = kwn == 4 ? WgRowCfg<4, 10>::STAGE : (g->OW == 4 ? WgRowCfg<3, 6>::STAGE : WgRowCfg<3, 5>::STAGE);
+            if (fill(WG_ROW_DMA, kwn, sxy, xb, 4, dim3(co_tiles, kwn * (g->Cin / 64), sp), 64 * kwn, 4 * stage, cps32, fw)) {
+                p->wclog = wclog;
+                return true;
             }
         }
     }
     constexpr int SMALL_M = 12000;      // small-pixel-count decomposition: output pixels up to this
     if (M <= SMALL_M && co_tiles * items >= 256) {
         // GEMM-like layer: one tile per wave, all pixels (ksplit re-derived for this decomposition)
-        const int total_chunks = cdiv(M, 16);
         const int wgs = co_tiles * cdiv(items, 4);
         // pixel splits: each one adds a full f32-atomic copy of every 64x64 tile (the atomics run at ~1.3 TB/s),
         // so split only up to ~3 workgroups per CU and keep >= 24 chunks (384 pixels) of MFMA work behind a copy
         // (measured on the discriminator shapes: joint conv 68 -> 44 us, s64_2 68 -> 46, c4 166 -> 133)
         constexpr int SMALL_WGS = 768, SMALL_MINC = 24;
-        int split = wgs >= SMALL_WGS / 2 ? 1 : cdiv(SMALL_WGS, wgs);
-        if (split > total_chunks / SMALL_MINC) split = total_chunks / SMALL_MINC > 0 ? total_chunks / SMALL_MINC : 1;
-        const int cps = cdiv(total_chunks, split);
-        split = cdiv(total_chunks, cps);
-        dim3 grid(co_tiles, cdiv(items, 4), split);
-        if (grid.y > 65535 || grid.z > 65535) return SBA_E_ARG;
-        const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
+        const int target = wgs >= SMALL_WGS / 2 ? wgs : SMALL_WGS;         // (half the target is there already: no split)
+        int cps;
+        const int split = pixel_splits(target, wgs, cdiv(M, 16), SMALL_MINC, &cps);
+        const dim3 grid(co_tiles, cdiv(items, 4), split);
+        if (grid.y > 65535 || grid.z > 65535) return false;
         // LDS-DMA ring of depth 4 (tools/bench_wgrad.py, B = 20): 15-25 % faster than the register-staged kernel up to ~512
         // workgroups (joint conv 29 -> 25 us, D s32 61 -> 50, s32_1 49 -> 37); beyond that the launches are bound by
         // the L2 traffic of the operand slices either way and the 80 KB ring costs occupancy (s64 145 -> 175 us)
@@ -944,44 +919,17 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
         // beyond DMA_WGS: the DMA kernel with TWO co tiles per wave (0.375 KB of operands per MFMA) -- pays once the
         // epilogue is a plain store (first write: D256 s64 119 -> 95 us, s64_1 89 -> 79, G upsample1 84 -> 72); with the
         // read-modify-write epilogue it is no faster than the register-staged kernel (148 vs 146 us).
-        if (fw == 2 && wgs > DMA_WGS && g->Cout % 128 == 0 && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
-            const int tc32 = cdiv(M, 32);
-            dim3 gd(co_tiles / 2, cdiv(items, 4), 1);
-            constexpr int LDS = 3 * 6 * 32 * 128;
-            static bool once = false;
-            if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-            SBA_LAUNCH((wgrad_small_dma_kernel<2, 3>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)dy, dw, *g, M, tc32, fw, dsub, dow, (int64_t)0);
-            return SBA_CHECK_LAUNCH();
+        if (fw == 2 && wgs > DMA_WGS && g->Cout % 128 == 0 && dma_ok) {
+            fill(WG_SMALL_DMA, 2, 3, 0, 0, dim3(co_tiles / 2, cdiv(items, 4), 1), 256, 3 * 6 * 32 * 128, cdiv(M, 32), fw);
+            return true;
         }
-        if (wgs <= DMA_WGS && dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
+        if (wgs <= DMA_WGS && dma_ok) {
             // stages of 32 pixels; the same split rule restated in 32-pixel chunks
-            const int tc32 = cdiv(M, 32);
-            int sp = wgs >= SMALL_WGS / 2 ? 1 : cdiv(SMALL_WGS, wgs);
-            constexpr int mc = SMALL_MINC / 2;
-            if (sp > tc32 / mc) sp = tc32 / mc > 0 ? tc32 / mc : 1;
-            const int cps32 = cdiv(tc32, sp);
-            sp = cdiv(tc32, cps32);
-            dim3 gd(co_tiles, cdiv(items, 4), sp);
-            if (gd.z > 65535) return SBA_E_ARG;
-            if (!det_begin(sp)) return SBA_E_ARG;
-            float* dwa = part ? part : dw;
-            const int md = part ? 2 : (sp > 1 ? 1 : fw);
-            const int64_t zs = part ? dwn : 0;
-            constexpr int LDS = 4 * 5 * 32 * 128;
-            static bool once = false;
-            if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-            SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-            det_end(sp);
-            return SBA_CHECK_LAUNCH();
+            int cps32;
+            const int sp = pixel_splits(target, wgs, cdiv(M, 32), SMALL_MINC / 2, &cps32);
+            return fill(WG_SMALL_DMA, 1, 4, 0, 0, dim3(co_tiles, cdiv(items, 4), sp), 256, 4 * 5 * 32 * 128, cps32, fw);
         }
-        if (!det_begin(split)) return SBA_E_ARG;
-        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_small_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream,
-                                               (const T*)x, (const T*)dy, part ? part : dw, *g, M, cps,
-                                               part ? 2 : (split > 1 ? 1 : fw), dsub, dow, part ? dwn : (int64_t)0));
-        det_end(split);
-        return SBA_CHECK_LAUNCH();
+        return fill(WG_SMALL, dtype, 0, 0, 0, grid, 256, 0, cps, fw);
     }
     // generator-style 3x3 stride-1 conv on a wide map: all nine taps per workgroup from halo tiles.  From 128x128 maps
     // up (B = 20: M >= 327 k) it beats the LDS-DMA decomposition below (upBlock -> 256 px 189 vs 349 us); at 64x64
@@ -991,68 +939,92 @@ extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* d
                    g->oox == 0 && g->OHs == g->OH && g->OWs == g->OW && g->OW % 64 == 0 && M >= ROWS_M;
     for (int t = 0; t < 9 && rows_ok; ++t) rows_ok = g->ty[t] == t / 3 - 1 && g->tx[t] == t % 3 - 1;
     if (rows_ok) {
-        const int total_segs = g->N * g->OH * (g->OW / 64);
         const int ci_t = cdiv(g->Cin, 64);
         // every pixel split adds a full copy of the tile's 9 x 64 x 64 outputs to the f32 atomics
         // (~1.3 TB/s chip-wide), so use few, fat workgroups: ~1 per CU and >= 16 segments each
-        int nz = cdiv(256, co_tiles * ci_t);
-        if (nz > total_segs / 16) nz = total_segs / 16;
-        if (nz < 1) nz = 1;
-        const int spw = cdiv(total_segs, nz);
-        nz = cdiv(total_segs, spw);
-        dim3 grid(co_tiles, ci_t, nz);
-        if (grid.z > 65535) return SBA_E_ARG;
+        int spw;
+        const int nz = pixel_splits(256, co_tiles * ci_t, g->N * g->OH * (g->OW / 64), 16, &spw);
         // (deterministic mode: also for nz == 1 -- every workgroup's three waves store, nothing adds)
-        part = nullptr;
-        if (sba_det_on()) { part = sba_det_alloc((int64_t)nz * dwn); if (!part) return SBA_E_ARG; }
-        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_rows_kernel<T>), grid, dim3(192), 0, (hipStream_t)stream,
-                                               (const T*)x, (const T*)dy, part ? part : dw, *g, total_segs, spw,
-                                               part ? 1 : 0, part ? dwn : (int64_t)0));
-        det_end(nz);
-        return SBA_CHECK_LAUNCH();
+        return fill(WG_ROWS, dtype, 0, 0, 0, dim3(co_tiles, ci_t, nz), 192, 0, spw, 1);
     }
-    {
-        // Big-M layers that are not 3x3 / OW % 64 == 0 (the discriminators' 4x4/s2 down blocks at 32..128 px): the
-        // register-staged kernel below shares nothing between its waves (1 KB of operands per MFMA from L2 = the
-        // 300 TFLOP/s on-chip-bandwidth roofline of a 64x64 tile); the small-pixel-count decomposition shares the dy
-        // slices between the four (tap, ci tile) items of a workgroup (0.625 KB per MFMA) and walks its pixel split
-        // through the LDS-DMA ring.  Measured (tools/bench_wgrad.py, B = 20): D256 down 64->128 @128 px 200 -> 110 us,
-        // 128->256 @64 193 -> 107, D128 down @64 99 -> 48, D64 down @32 43 -> 24; two co tiles per wave are no better.
-        const int64_t xb = (int64_t)g->N * g->IH * g->IW * g->Cin * 2, db = (int64_t)g->N * g->OH * g->OW * g->Cout * 2;
-        if (dtype == SBA_BF16 && xb < (1ll << 32) && db < (1ll << 32)) {
-            constexpr int GEN_WGS = 512;
-            const int wgs = co_tiles * cdiv(items, 4);
-            const int tc32 = cdiv(M, 32);
-            int sp = cdiv(GEN_WGS, wgs);
-            if (sp > tc32 / 12) sp = tc32 / 12 > 0 ? tc32 / 12 : 1;
-            const int cps32 = cdiv(tc32, sp);
-            sp = cdiv(tc32, cps32);
-            dim3 gd(co_tiles, cdiv(items, 4), sp);
-            if (gd.y <= 65535 && gd.z <= 65535) {
-                if (!det_begin(sp)) return SBA_E_ARG;
-                float* dwa = part ? part : dw;
-                const int md = part ? 2 : (sp > 1 ? 1 : fw);
-                const int64_t zs = part ? dwn : 0;
-                constexpr int LDS = 4 * 5 * 32 * 128;
-                static bool once = false;
-                if (!once) { (void)hipFuncSetAttribute((const void*)wgrad_small_dma_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); once = true; }
-                SBA_LAUNCH((wgrad_small_dma_kernel<1, 4>), gd, dim3(256), LDS, (hipStream_t)stream, (const bf16_t*)x,
-                           (const bf16_t*)dy, dwa, *g, M, cps32, md, dsub, dow, zs);
-                det_end(sp);
-                return SBA_CHECK_LAUNCH();
-            }
-        }
+    // Big-M layers that are not 3x3 / OW % 64 == 0 (the discriminators' 4x4/s2 down blocks at 32..128 px): the
+    // register-staged kernel below shares nothing between its waves (1 KB of operands per MFMA from L2 = the
+    // 300 TFLOP/s on-chip-bandwidth roofline of a 64x64 tile); the small-pixel-count decomposition shares the dy
+    // slices between the four (tap, ci tile) items of a workgroup (0.625 KB per MFMA) and walks its pixel split
+    // through the LDS-DMA ring.  Measured (tools/bench_wgrad.py, B = 20): D256 down 64->128 @128 px 200 -> 110 us,
+    // 128->256 @64 193 -> 107, D128 down @64 99 -> 48, D64 down @32 43 -> 24; two co tiles per wave are no better.
+    if (dma_ok) {
+        constexpr int GEN_WGS = 512;
+        int cps32;
+        const int sp = pixel_splits(GEN_WGS, co_tiles * cdiv(items, 4), cdiv(M, 32), 12, &cps32);
+        if (fill(WG_SMALL_DMA, 1, 4, 0, 0, dim3(co_tiles, cdiv(items, 4), sp), 256, 4 * 5 * 32 * 128, cps32, fw)) return true;
     }
     const int total_chunks = cdiv(M, 64);
     if (ksplit > total_chunks) ksplit = total_chunks;
     const int cps = cdiv(total_chunks, ksplit);
-    ksplit = cdiv(total_chunks, cps);
-    dim3 grid(co_tiles, items, ksplit);
-    if (grid.y > 65535 || grid.z > 65535) return SBA_E_ARG;
-    if (!det_begin(ksplit)) return SBA_E_ARG;
-    SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream,
-                                           (const T*)x, (const T*)dy, part ? part : dw, *g, M, cps,
-                                           part ? 2 : (ksplit > 1 ? 1 : 0), dsub, dow, part ? dwn : (int64_t)0));
-    det_end(ksplit);
+    return fill(WG_GENERIC, dtype, 0, 0, 0, dim3(co_tiles, items, cdiv(total_chunks, cps)), 256, 0, cps, 0);
+}
+
+// One launch of a dynamic-LDS kernel; its LDS limit is raised once per kernel symbol.
+template <auto Kernel, typename... Args>
+static void launch_dyn_lds(const WgradPlan& p, hipStream_t st, Args... args) {
+    static bool once = false;
+    if (!once) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds); once = true; }
+    SBA_LAUNCH(Kernel, p.grid, dim3(p.block), p.lds, st, args...);
+}
+
+static int wgrad_launch(const WgradPlan& p, int dtype, const void* x, const void* dy, float* dw, const sba_conv_geom* g,
+                        hipStream_t st) {
+    const int M = g->N * g->OHs * g->OWs;
+    const FastDiv dsub = make_fastdiv((uint32_t)(g->OHs * g->OWs), (int64_t)M + 64);
+    const FastDiv dow = make_fastdiv((uint32_t)g->OWs, (int64_t)M + 64);
+    const int64_t dwn = (int64_t)g->Cout * g->ntaps * g->Cin;
+    float* part = nullptr;
+    if (p.npart) { part = sba_det_alloc((int64_t)p.npart * dwn); if (!part) return SBA_E_ARG; }
+    float* dwa = part ? part : dw;
+    const int64_t zs = part ? dwn : 0;
+    const bf16_t* xh = (const bf16_t*)x;
+    const bf16_t* dyh = (const bf16_t*)dy;
+    switch (p.family) {
+    case WG_ROW_DMA:
+        if (p.v[0] == 4) launch_dyn_lds<wgrad_row_dma_kernel<4, 2, 10, 4>>(p, st, xh, dyh, dwa, *g, M, p.per_split, p.mode, dsub, dow, zs, p.wclog);
+        else if (p.v[2] == 6) launch_dyn_lds<wgrad_row_dma_kernel<3, 1, 6, 4>>(p, st, xh, dyh, dwa, *g, M, p.per_split, p.mode, dsub, dow, zs, p.wclog);
+        else launch_dyn_lds<wgrad_row_dma_kernel<3, 1, 5, 4>>(p, st, xh, dyh, dwa, *g, M, p.per_split, p.mode, dsub, dow, zs, p.wclog);
+        break;
+    case WG_SMALL_DMA:
+        if (p.v[0] == 2) launch_dyn_lds<wgrad_small_dma_kernel<2, 3>>(p, st, xh, dyh, dwa, *g, M, p.per_split, p.mode, dsub, dow, zs);
+        else launch_dyn_lds<wgrad_small_dma_kernel<1, 4>>(p, st, xh, dyh, dwa, *g, M, p.per_split, p.mode, dsub, dow, zs);
+        break;
+    case WG_SMALL:
+        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_small_kernel<T>), p.grid, dim3(p.block), 0, st, (const T*)x, (const T*)dy, dwa, *g, M,
+                                       p.per_split, p.mode, dsub, dow, zs));
+        break;
+    case WG_ROWS:
+        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_rows_kernel<T>), p.grid, dim3(p.block), 0, st, (const T*)x, (const T*)dy, dwa, *g,
+                                       g->N * g->OH * (g->OW / 64), p.per_split, p.mode, zs));
+        break;
+    default:
+        SBA_DISPATCH(dtype, SBA_LAUNCH((wgrad_kernel<T>), p.grid, dim3(p.block), 0, st, (const T*)x, (const T*)dy, dwa, *g, M,
+                                       p.per_split, p.mode, dsub, dow, zs));
+    }
+    if (part) sba_det_fold(part, 1, p.npart, dwn, dw, 0, g->first_write ? 1 : 0, st);
     return SBA_CHECK_LAUNCH();
+}
+
+}  // namespace
+
+extern "C" int sba_conv_wgrad_plan(int dtype, const sba_conv_geom* g, int ksplit, int det, int* plan) {
+    WgradPlan p;
+    if (!plan || !wgrad_plan(dtype, g, ksplit, det != 0, &p)) return SBA_E_ARG;
+    const int out[SBA_WGRAD_PLAN_INTS] = {p.family, p.v[0], p.v[1], p.v[2], p.v[3], (int)p.grid.x, (int)p.grid.y, (int)p.grid.z,
+                                          p.block, p.lds, p.per_split, p.mode, p.npart, p.wclog};
+    for (int i = 0; i < SBA_WGRAD_PLAN_INTS; ++i) plan[i] = out[i];
+    return SBA_OK;
+}
+
+extern "C" int sba_conv_wgrad(int dtype, const void* x, const void* dy, float* dw, const sba_conv_geom* g,
+                              int ksplit, void* stream) {
+    WgradPlan p;
+    if (!x || !dy || !dw || !wgrad_plan(dtype, g, ksplit, sba_det_on(), &p)) return SBA_E_ARG;
+    return wgrad_launch(p, dtype, x, dy, dw, g, (hipStream_t)stream);
 }

@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get('SBA_LIB_PATH') or os.path.join(os.path.dirname(_HERE)
 
 SBA_F32, SBA_BF16, SBA_BF16_YH = 0, 1, 2
 IGEMM_TILES = 18          # SBA_IGEMM_TILES of include/sbagan_hip.h
+WGRAD_PLAN_INTS = 14      # SBA_WGRAD_PLAN_INTS
+WGRAD_FAMILIES = ('row_dma', 'small_dma', 'small', 'rows', 'generic')       # sba_conv_wgrad_plan: plan[0]
 ACT_NONE, ACT_GLU, ACT_LRELU, ACT_RELU = 0, 1, 2, 3
 MAX_TAPS = 32
 
@@ -62,6 +64,7 @@ SIGNATURES = {
     'sba_conv_igemm_group': [I, I, POINTER(ConvGroupItem), I, P],
     'sba_conv_igemm_group_splitk': [I, I, POINTER(ConvGroupItem), I, I, P, L, P],
     'sba_conv_wgrad': [I, P, P, P, G, I, P],
+    'sba_conv_wgrad_plan': [I, G, I, I, POINTER(c_int)],
     'sba_pack_weight': [I, P, P, I, I, I, I, I, P],
     'sba_pack_frag_multi': [P, I, I, P],
     'sba_pack_weights_multi': [I, P, I, I, P],
@@ -185,6 +188,22 @@ def call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise RuntimeError('%s failed: %s' % (name, _ERR.get(rc, rc)))
+
+
+def wgrad_plan(dtype, g, ksplit, det=None):
+    """sba_conv_wgrad_plan: the 14 integers of the launch sba_conv_wgrad would make for geometry `g` (needs no device);
+    det = None: the current deterministic-mode flag"""
+    plan = (c_int * WGRAD_PLAN_INTS)()
+    det = lib.sba_get_deterministic() if det is None else int(det)
+    call('sba_conv_wgrad_plan', dtype, byref(g), ksplit, det, plan)
+    return list(plan)
+
+
+def wgrad_plan_name(plan):
+    """'row_dma<3,1,5,4> x2': kernel family, template arguments and pixel splits of a wgrad_plan"""
+    fam, nargs = WGRAD_FAMILIES[plan[0]], (4, 2, 0, 0, 0)[plan[0]]
+    args = ','.join(str(v) for v in plan[1:1 + nargs]) if nargs else ('f32', 'bf16')[plan[1]]
+    return '%s<%s> x%d' % (fam, args, plan[7])
 
 
 def version():

@@ -278,6 +278,42 @@ def test_small_batch_discriminator_gradients_are_reproducible(dev, det):
             assert torch.equal(a, b0), rel_l2(a, b0)
 
 
+def test_weight_gradients_are_bit_reproducible_in_every_kernel_family(dev, det):
+    """ops.conv_wgrad twice in the deterministic mode gives identical bytes, one shape per family of sba_conv_wgrad_plan
+    (with pixel splits wherever the family has them: partial tensors + the ordered fold instead of f32 atomics),
+    first write and accumulate"""
+    from sbagan import _lib, ops
+    import test_kernels_gpu as K
+    import test_wgrad_plan_cpu as T
+    seen = set()
+    for dt, case in ((torch.bfloat16, ('4x4s2', 3, 128, 64, 32, 32)), (torch.bfloat16, ('3x3', 12, 224, 544, 8, 8)),
+                     (torch.float32, ('3x3', 16, 256, 512, 8, 8)), (torch.bfloat16, ('3x3', 2, 32, 64, 256, 256)),
+                     (torch.float32, ('3x3', 1, 64, 64, 96, 96))):
+        kind, N, Cin, Cout, H, W = case
+        g = T.geom(_lib, kind, N, H, W, Cin, Cout)
+        tiles = ((Cout + 63) // 64) * ((Cin + 63) // 64) * g.ntaps
+        plan = _lib.wgrad_plan(ops._dt(torch.empty(0, dtype=dt)), g, ops._ksplit(tiles, N * g.OH * g.OW), 1)
+        assert plan[12] > 1, (case, plan)           # deterministic partials: the ordered path is what runs
+        seen.add(plan[0])
+        xa = K.act(fill.unit((N, Cin, H, W), 1), dt, dev)
+        dya = K.act(fill.unit((N, Cout, g.OH, g.OW), 3), dt, dev)
+        runs = []
+        for _ in range(2):
+            ops.det_reset()
+            wq = torch.nn.Parameter(torch.zeros((Cout, Cin, 3 if kind != '4x4s2' else 4, 3 if kind != '4x4s2' else 4),
+                                                device=dev).contiguous(memory_format=torch.channels_last))
+            wq.grad = torch.zeros_like(wq)
+            wq._sba_gepoch = [1]
+            ops.conv_wgrad(xa, dya, wq, kind)            # first write
+            first = wq.grad.clone()
+            ops.conv_wgrad(xa, dya, wq, kind)            # accumulate
+            torch.cuda.synchronize()
+            runs.append((first, wq.grad.clone()))
+        assert float(runs[0][0].abs().max()) > 0
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1]), case
+    assert seen == set(range(5))
+
+
 @pytest.mark.parametrize('dt', DTYPES)
 def test_deterministic_kernels_match_the_oracle(dev, det, dt):
     """The ordered-reduction code paths (scratch-ring slots + fold, wave-by-wave LDS accumulation, no split-K,

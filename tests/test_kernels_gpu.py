@@ -73,26 +73,53 @@ CONV_CASES = [
     ('4x4s2', 3, 128, 64, 8, 8),
     ('3x3', 1, 64, 64, 96, 96),       # M = 9216 -> 256-row tiles
     ('3x3', 1, 64, 128, 72, 64),      # M = 4608 -> 128x128 tiles
-    ('4x4s2', 2, 512, 256, 8, 8),     # M = 32, K = 8192: split-K path + small-M wgrad
+    ('4x4s2', 2, 512, 256, 8, 8),     # M = 32, K = 8192: split-K path + small-M wgrad (f32; bf16: kernel-row wgrad, OW = 4)
     ('3x3', 4, 256, 512, 4, 4),       # M = 64, K = 2304: split-K with a ragged last split
     ('3x3up', 2, 512, 512, 4, 4),     # generator stage-1 shape
-    ('3x3', 2, 64, 64, 128, 128),     # M = 32768, OW % 64 == 0: all-taps halo-tile wgrad
+    ('3x3', 2, 64, 64, 128, 128),     # M = 32768: kernel-row wgrad with 79 pixel splits in bf16, generic wgrad_kernel x21 in f32
     ('3x3up', 2, 64, 128, 64, 64),    # same with the fused nearest x2 (output 128 x 128)
     ('3x3', 1, 128, 64, 128, 256),    # two ci tiles, non-square map
-    ('3x3', 8, 64, 64, 128, 128),     # 512 8 x 32 tiles: register-weight halo-tile kernel (conv3x3_halo3_kernel)
+    ('3x3', 8, 64, 64, 128, 128),     # 512 8 x 32 tiles: halo-tile forward kernel; M = 131072: f32 all-taps halo-row wgrad (wgrad_rows_kernel)
     ('3x3', 5, 64, 128, 128, 128),    # ... two 64-channel blocks of Cout, 320 tiles per block
     ('3x3up', 9, 64, 64, 64, 64),     # ... behind the nearest x2 upsample (576 tiles, LDS-weight conv3x3_halo_kernel)
     ('3x3up', 2, 128, 128, 64, 64),   # halo-tile kernel walking TWO 64-channel chunks of Cin = 128, behind the nearest x2 upsample
     ('3x3', 8, 128, 64, 64, 64),      # ... plain 3x3 (the shape of the data gradient of the ResBlocks' 64 -> 128 conv)
-    ('3x3', 20, 768, 512, 4, 4),      # D_GET_LOGITS.jointConv at B = 20 (M = 320): LDS-DMA small-pixel-count wgrad, 10 stages
-    ('3x3', 3, 224, 544, 4, 4),       # ... ragged: last ci / co tiles 32 channels wide, M = 48 (half-empty second stage)
-    ('3x3', 16, 256, 512, 8, 8),      # ... M = 1024: two pixel splits, f32 atomics
-    ('3x3', 2, 1024, 1024, 4, 4),     # ... 576 workgroups: register-staged kernel when accumulating, two co tiles per wave (CT = 2) on a first write
-    ('4x4s2', 2, 64, 128, 64, 64),    # wgrad_s2_dma_kernel (the four kw taps of a kernel row share one staged input row): OW = 32
+    ('3x3', 20, 768, 512, 4, 4),      # D_GET_LOGITS.jointConv at B = 20 (M = 320): kernel-row wgrad on 4 x 4 maps (two images per chunk), 10 stages
+    ('3x3', 3, 224, 544, 4, 4),       # LDS-DMA small-pixel-count wgrad, ragged: last ci / co tiles 32 channels wide, M = 48 (half-empty second stage)
+    ('3x3', 16, 256, 512, 8, 8),      # M = 1024: two pixel splits, f32 atomics (bf16: kernel-row wgrad, f32: wgrad_small_kernel)
+    ('3x3', 2, 1024, 1024, 4, 4),     # 576 workgroups of the small-pixel-count kernels in f32; bf16: kernel-row wgrad, one 32-pixel chunk of two 4 x 4 maps
+    ('4x4s2', 2, 64, 128, 64, 64),    # wgrad_row_dma_kernel<4, 2, 10, 4> (the four kw taps of a kernel row share one staged input row): OW = 32
     ('4x4s2', 3, 128, 64, 32, 32),    # ... OW = 16 (two output rows per 32-pixel chunk), two ci tiles
     ('4x4s2', 2, 64, 64, 256, 128),   # ... OW = 64 (two chunks per output row), non-square, pixel splits
     ('4x4s2', 5, 192, 128, 16, 16),   # ... OW = 8 (four output rows per chunk), three ci tiles
+    ('3x3', 2, 1056, 1024, 4, 4),     # Cin % 64 = 32: not kernel-row; M = 32, 624 workgroups: bf16 first write wgrad_small_dma_kernel<2, 3> (one
+                                      # 32-pixel stage in a depth-3 ring, half-empty last ci tile), bf16 accumulate / f32: wgrad_small_kernel
+    ('3x3', 12, 224, 544, 8, 8),      # M = 768, 81 workgroups: wgrad_small_dma_kernel<1, 4> with two pixel splits, ragged last co and ci tiles
+    ('3x3', 2, 32, 64, 256, 256),     # M = 131072, Cin = 32: wgrad_rows_kernel in bf16 too (Cin % 64 != 0 keeps the kernel-row kernel away)
 ]
+
+# The weight-gradient kernel a case is there for: case -> {(dtype, first_write): sba_conv_wgrad_plan as
+# _lib.wgrad_plan_name, 'family<template arguments> x pixel splits'}.  Checked without a device by
+# tests/test_wgrad_plan_cpu.py::test_conv_cases_take_the_kernels_they_name; between them the cases reach every kernel.
+WGRAD_KERNELS = {
+    ('3x3', 2, 64, 64, 16, 16): {('f32', 0): 'generic<f32> x1', ('bf16', 0): 'row_dma<3,1,5,4> x1'},
+    ('3x3', 1, 64, 64, 96, 96): {('f32', 0): 'generic<f32> x6', ('bf16', 0): 'small_dma<1,4> x24'},
+    ('4x4s2', 2, 512, 256, 8, 8): {('f32', 0): 'small<f32> x1', ('bf16', 0): 'row_dma<4,2,10,4> x1'},
+    ('3x3', 2, 64, 64, 128, 128): {('f32', 0): 'generic<f32> x21', ('bf16', 0): 'row_dma<3,1,5,4> x79'},
+    ('3x3', 8, 64, 64, 128, 128): {('f32', 0): 'rows<f32> x128', ('bf16', 0): 'row_dma<3,1,5,4> x128'},
+    ('3x3up', 9, 64, 64, 64, 64): {('f32', 1): 'rows<f32> x144', ('bf16', 1): 'row_dma<3,1,5,4> x128'},
+    ('3x3', 20, 768, 512, 4, 4): {('f32', 0): 'small<f32> x1', ('bf16', 0): 'row_dma<3,1,6,4> x1', ('bf16', 1): 'row_dma<3,1,6,4> x1'},
+    ('3x3', 3, 224, 544, 4, 4): {('bf16', 0): 'small_dma<1,4> x1', ('bf16', 1): 'small_dma<1,4> x1'},
+    ('3x3', 16, 256, 512, 8, 8): {('f32', 0): 'small<f32> x2', ('bf16', 0): 'row_dma<3,1,5,4> x2'},
+    ('3x3', 2, 1024, 1024, 4, 4): {('f32', 1): 'small<f32> x1', ('bf16', 0): 'row_dma<3,1,6,4> x1', ('bf16', 1): 'row_dma<3,1,6,4> x1'},
+    ('4x4s2', 2, 64, 128, 64, 64): {('bf16', 0): 'row_dma<4,2,10,4> x5'},
+    ('4x4s2', 3, 128, 64, 32, 32): {('bf16', 0): 'row_dma<4,2,10,4> x2'},
+    ('4x4s2', 2, 64, 64, 256, 128): {('bf16', 0): 'row_dma<4,2,10,4> x40'},
+    ('4x4s2', 5, 192, 128, 16, 16): {('bf16', 0): 'row_dma<4,2,10,4> x1'},
+    ('3x3', 2, 1056, 1024, 4, 4): {('f32', 0): 'small<f32> x1', ('bf16', 0): 'small<bf16> x1', ('bf16', 1): 'small_dma<2,3> x1'},
+    ('3x3', 12, 224, 544, 8, 8): {('bf16', 0): 'small_dma<1,4> x2', ('bf16', 1): 'small_dma<1,4> x2'},
+    ('3x3', 2, 32, 64, 256, 256): {('f32', 0): 'rows<f32> x128', ('bf16', 0): 'rows<bf16> x128', ('bf16', 1): 'rows<bf16> x128'},
+}
 
 
 def torch_conv(x, w, kind):

@@ -74,8 +74,13 @@ def main():
         us = e0.elapsed_time(e1) / n * 1e3
         M = N * OH * OW
         fl = 2.0 * M * Cout * Cin * k * k
-        print('%-36s %-6s M=%-6d %5dx%-5d  %8.1f us  %6.1f TFLOP/s  dW %6.1f MB' %
-              (name, kind, M, Cin, Cout, us, fl / us * 1e-6, Cout * Cin * k * k * 4 / 1e6))
+        # the launch behind the number (sba_conv_wgrad_plan: kernel family, template arguments, pixel splits)
+        g = ops._geom((kind, N, H, W, Cin, Cout, None))
+        g.first_write = 1 if os.environ.get('BENCH_FIRST_WRITE', '0') == '1' else 0
+        tiles = ((Cout + 63) // 64) * ((Cin + 63) // 64) * g.ntaps
+        plan = ops._lib.wgrad_plan_name(ops._lib.wgrad_plan(ops._lib.SBA_BF16, g, ops._ksplit(tiles, M)))
+        print('%-36s %-6s M=%-6d %5dx%-5d  %8.1f us  %6.1f TFLOP/s  dW %6.1f MB  %s' %
+              (name, kind, M, Cin, Cout, us, fl / us * 1e-6, Cout * Cin * k * k * 4 / 1e6, plan))
 
 
 if __name__ == '__main__':

@@ -11,6 +11,7 @@ inputs from oracle/fill.py, and only numeric outputs are written.
     python tools/make_golden.py units      # just the reduced-size units
     python tools/make_golden.py infer      # the eval-mode generator fixtures (infer_*.npz)
     SBA_LIB_PATH=<parent build> python tools/make_golden.py igemm_plan     # the kernel-choice recording
+    SBA_LIB_PATH=<recorder build> python tools/make_golden.py wgrad_plan   # ... of the weight gradient
 """
 import os
 import sys
@@ -423,6 +424,20 @@ def gen_igemm_plan():
                                                      os.path.getsize(T.GOLDEN)))
 
 
+def gen_wgrad_plan():
+    """wgrad_plan.npz: the answers of sba_conv_wgrad_plan on the grid of tests/test_wgrad_plan_cpu.py, from a library that
+    is NOT the code under test: SBA_LIB_PATH = a libsbagan_hip.so of the commit before the query existed, built with
+    the recorder unit of profiles/wgrad_plan_refactor.txt (that commit's own dispatch, its launches recorded)."""
+    assert os.environ.get('SBA_LIB_PATH'), 'set SBA_LIB_PATH to the recorder build of the parent commit'
+    sys.path[:0] = [os.path.join(ROOT, 'sba-gan_amd'), os.path.join(ROOT, 'tests')]
+    import test_wgrad_plan_cpu as T
+    from sbagan import _lib
+    S = T.replay(_lib)
+    np.savez_compressed(T.GOLDEN, **S)
+    print('wgrad_plan.npz from %s: %s, %d bytes' % (_lib.LIB_PATH, {k: len(v) for k, v in S.items()},
+                                                     os.path.getsize(T.GOLDEN)))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     what = sys.argv[1:] or ['units', 'step_tiny', 'step_full']
@@ -430,6 +445,11 @@ def main():
     if 'igemm_plan' in what:            # (needs no reference)
         gen_igemm_plan()
         what = [w for w in what if w != 'igemm_plan']
+        if not what:
+            return
+    if 'wgrad_plan' in what:
+        gen_wgrad_plan()
+        what = [w for w in what if w != 'wgrad_plan']
         if not what:
             return
     ref = load_reference()
