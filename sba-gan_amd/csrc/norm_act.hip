@@ -10,23 +10,150 @@ namespace {
 
 constexpr float LRELU_SLOPE = 0.2f;
 
-// per-channel (scale, shift, mean, rstd) of one BatchNorm batch from its (sum, sumsq)
+// ---- the arithmetic every kernel below shares.  All helpers are forced inline: a kernel that uses one compiles to
+// the floating-point operations, in the order, that it had with the expression written out in place ----
+
+// forward element: BatchNorm output n = y * scale + shift of the value channel (and gp of its gate channel under GLU)
+// -> activated value.  The residual add stays with the caller.  (sigmoidf_, IEEE division: see common.h)
+template <int ACT>
+__device__ __forceinline__ float bn_act_elem(float ya, float sca, float sha, float yg, float scg, float shg) {
+    const float n = ya * sca + sha;
+    if (ACT == SBA_ACT_GLU) return n * sigmoidf_(yg * scg + shg);
+    if (ACT == SBA_ACT_LRELU) return n > 0.f ? n : LRELU_SLOPE * n;
+    if (ACT == SBA_ACT_RELU) return fmaxf(n, 0.f);
+    return n;
+}
+
+// backward element: dz = d loss / d (BatchNorm output) and xhat of the value channel (index 0) and, under GLU, of its
+// gate channel (index 1) from y, dout and the channels' (scale, shift, mean, rstd); without GLU kg = ka.  The LeakyReLU branch is taken from
+// the recomputed forward value; the gate is recomputed with sigmoid_bwd_ (v_rcp_f32: see common.h)
+struct ChCoef { float scale, shift, mean, rstd; };
+// (loaded in the order the backward math uses them: scale and shift of both channels for the forward value, then mean and
+// rstd for xhat -- the load order decides a VGPR or two, and with them a wave of occupancy of bn_bwd_apply_kernel)
+__device__ __forceinline__ void ch_coef_pair(const float* __restrict__ scale, const float* __restrict__ shift,
+                                             const float* __restrict__ mean, const float* __restrict__ rstd, int ca, int cg,
+                                             ChCoef& ka, ChCoef& kg) {
+    ka.scale = scale[ca]; ka.shift = shift[ca]; kg.scale = scale[cg]; kg.shift = shift[cg];
+    ka.mean = mean[ca]; ka.rstd = rstd[ca]; kg.mean = mean[cg]; kg.rstd = rstd[cg];
+}
+template <int ACT>
+__device__ __forceinline__ void bn_bwd_elem(float ya, float yg, float dd, const ChCoef& ka, const ChCoef& kg,
+                                            float (&dz)[2], float (&xh)[2]) {
+    if (ACT == SBA_ACT_GLU) {
+        const float n = ya * ka.scale + ka.shift;
+        const float gp = yg * kg.scale + kg.shift;
+        const float s = sigmoid_bwd_(gp);
+        dz[0] = dd * s;
+        dz[1] = dd * n * s * (1.f - s);
+    } else {
+        dz[0] = dd;
+        if (ACT == SBA_ACT_LRELU) {
+            const float n = ya * ka.scale + ka.shift;
+            dz[0] = n > 0.f ? dd : LRELU_SLOPE * dd;
+        }
+    }
+    xh[0] = (ya - ka.mean) * ka.rstd;
+    if (ACT == SBA_ACT_GLU) xh[1] = (yg - kg.mean) * kg.rstd;
+}
+
+// (sum, sumsq) of `count` values -> mean, biased variance, rstd; with gamma and beta -> scale and shift
+struct Moments { float mean, var, rstd; };
+__device__ __forceinline__ Moments moments_of(float sum, float sumsq, float count, float eps) {
+    Moments m;
+    m.mean = sum / count;
+    m.var = fmaxf(sumsq / count - m.mean * m.mean, 0.f);
+    m.rstd = rsqrtf(m.var + eps);
+    return m;
+}
 struct BnCoef { float scale, shift, mean, rstd, var; };
+__device__ __forceinline__ BnCoef bn_affine(float mean, float var, float rstd, float gamma, float beta) {
+    BnCoef k;
+    k.mean = mean; k.var = var; k.rstd = rstd;
+    k.scale = gamma * rstd;
+    k.shift = beta - mean * k.scale;
+    return k;
+}
+// aux[4][C] = scale, shift, mean, rstd: what the forward leaves for the backward kernels
+__device__ __forceinline__ void store_aux(float* __restrict__ aux, int C, int c, const BnCoef& k) {
+    aux[c] = k.scale; aux[C + c] = k.shift; aux[2 * C + c] = k.mean; aux[3 * C + c] = k.rstd;
+}
+// running statistics after one more batch: momentum, unbiased variance
+__device__ __forceinline__ void running_update(float& rm, float& rv, float mean, float var, float count, float momentum) {
+    const float unb = count > 1.f ? var * count / (count - 1.f) : var;
+    rm = (1.f - momentum) * rm + momentum * mean;
+    rv = (1.f - momentum) * rv + momentum * unb;
+}
+// per-channel coefficients of one BatchNorm batch from its replicated (sum, sumsq) statistics
 __device__ __forceinline__ BnCoef bn_coef(const float* __restrict__ stats, const float* __restrict__ gamma,
                                           const float* __restrict__ beta, int C, int c, float count, float eps) {
-    BnCoef k;
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int sl = 0; sl < SBA_BN_STAT_SLOTS; ++sl) {            // add the replicas up
         s0 += stats[sl * 2 * C + c];
         s1 += stats[sl * 2 * C + C + c];
     }
-    k.mean = s0 / count;
-    k.var = fmaxf(s1 / count - k.mean * k.mean, 0.f);
-    k.rstd = rsqrtf(k.var + eps);
-    k.scale = gamma[c] * k.rstd;
-    k.shift = beta[c] - k.mean * k.scale;
-    return k;
+    const Moments m = moments_of(s0, s1, count, eps);
+    return bn_affine(m.mean, m.var, m.rstd, gamma[c], beta[c]);
+}
+
+// The channel-sum tail of the reduction kernels: per-thread partial sums of 2C per-channel values (two halves of C) meet
+// in LDS, then go to their destination.  Default mode: acc[2*C], cleared, LDS atomics.  Deterministic mode: one private
+// row acc[tr][2*C] per row-group (plain stores, no clearing), the row-groups added in order.  dst(i, v) receives the
+// workgroup's sum v of value i < 2C.
+struct ChannelSum {
+    float* acc;
+    int C;
+    bool det;
+    __device__ __forceinline__ void clear() const {
+        if (det) return;
+        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) acc[i] = 0.f;
+        __syncthreads();
+    }
+    // row-group tr adds V consecutive channels from c on: s0 into the first half, s1 into the second
+    template <int V>
+    __device__ __forceinline__ void add(int tr, int c, const float (&s0)[V], const float (&s1)[V]) const {
+        float* row = acc + (det ? tr * 2 * C : 0);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            if (det) {
+                row[c + k] = s0[k];
+                row[C + c + k] = s1[k];
+            } else {
+                atomicAdd(&row[c + k], s0[k]);
+                atomicAdd(&row[C + c + k], s1[k]);
+            }
+        }
+    }
+    template <typename Dst>
+    __device__ __forceinline__ void finish(int rpi, Dst dst) const {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
+            float v = det ? 0.f : acc[i];
+            if (det)
+                for (int r = 0; r < rpi; ++r) v += acc[r * 2 * C + i];
+            dst(i, v);
+        }
+    }
+};
+
+// Cross-wave sum of the N (sum, sumsq) pairs a 256-thread workgroup owns: lane 0 of each of the four waves stores its
+// wave's sums, interleaved, into s_red[wave]; after a barrier four_wave_sum adds the waves as ((w0 + w1) + w2) + w3.
+template <int NV, int V>
+__device__ __forceinline__ void wave_sums_to_lds(const float (&s0)[NV][V], const float (&s1)[NV][V],
+                                                 float (&s_red)[4][2 * NV * V]) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int h = 0; h < NV; ++h)
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const float a0 = wave_sum(s0[h][k]), a1 = wave_sum(s1[h][k]);
+            if (lane == 0) { s_red[wid][(h * V + k) * 2] = a0; s_red[wid][(h * V + k) * 2 + 1] = a1; }
+        }
+    __syncthreads();
+}
+template <int W>
+__device__ __forceinline__ float four_wave_sum(const float (&s_red)[4][W], int i) {
+    return s_red[0][i] + s_red[1][i] + s_red[2][i] + s_red[3][i];
 }
 
 // ---- batch statistics of an NHWC tensor (used when the conv epilogue cannot provide them:
@@ -39,10 +166,8 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ y_a
     float* stats = stats_all + ((int64_t)blockIdx.y * SBA_BN_STAT_SLOTS + (blockIdx.x & (SBA_BN_STAT_SLOTS - 1))) * 2 * C;
     const int cv = C / V;
     extern __shared__ float s_acc[];                        // [2*C]; deterministic mode: [rows per iteration][2*C]
-    if (!det_part) {
-        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) s_acc[i] = 0.f;
-        __syncthreads();
-    }
+    const ChannelSum cs{s_acc, C, det_part != nullptr};
+    cs.clear();
     const int tpr = cv < (int)blockDim.x ? cv : (int)blockDim.x;
     const int rpi = blockDim.x / tpr;           // (cv not a power of two: the last blockDim.x % tpr threads idle)
     const int tc = threadIdx.x % tpr, tr = threadIdx.x / tpr;
@@ -56,31 +181,14 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ y_a
 #pragma unroll
             for (int k = 0; k < V; ++k) { const float v = a.get(k); s0[k] += v; s1[k] += v * v; }
         }
-        if (det_part) {                                     // private LDS row per row-group: no atomics
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                s_acc[tr * 2 * C + c + k] = s0[k];
-                s_acc[tr * 2 * C + C + c + k] = s1[k];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                atomicAdd(&s_acc[c + k], s0[k]);
-                atomicAdd(&s_acc[C + c + k], s1[k]);
-            }
-        }
+        cs.add(tr, c, s0, s1);
     }
-    __syncthreads();
-    if (det_part) {         // this workgroup's partial sums, row-groups added in order; sba_det_fold adds the workgroups
-        float* part = det_part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C;
-        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-            float v = 0.f;
-            for (int r = 0; r < rpi; ++r) v += s_acc[r * 2 * C + i];
-            part[i] = v;
-        }
-        return;
-    }
-    for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) atomicAdd(&stats[i], s_acc[i]);
+    // deterministic mode: this workgroup's partial sums go to its own slot; sba_det_fold adds the workgroups
+    float* part = det_part ? det_part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C : nullptr;
+    cs.finish(rpi, [&](int i, float v) {
+        if (det_part) part[i] = v;
+        else atomicAdd(&stats[i], v);
+    });
 }
 
 // ---- forward: finalize + out = act(y*scale+shift) (+residual) in one launch; blockIdx.y = group.
@@ -106,23 +214,16 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const YT* __restrict__ 
         if (training) {
             k = bn_coef(stats_all + (int64_t)g * SBA_BN_STAT_SLOTS * 2 * C, gamma, beta, C, c, count, eps);
         } else {                                            // inference: running statistics
-            k.mean = rmean[c];
-            k.rstd = rsqrtf(rvar[c] + eps);
-            k.scale = gamma[c] * k.rstd;
-            k.shift = beta[c] - k.mean * k.scale;
+            k = bn_affine(rmean[c], rvar[c], rsqrtf(rvar[c] + eps), gamma[c], beta[c]);
         }
         s_co[c] = k.scale;
         s_co[C + c] = k.shift;
-        if (blockIdx.x == 0) {
-            aux[c] = k.scale; aux[C + c] = k.shift; aux[2 * C + c] = k.mean; aux[3 * C + c] = k.rstd;
-        }
+        if (blockIdx.x == 0) store_aux(aux, C, c, k);
         if (blockIdx.x == 0 && g == 0 && training && rmean) {
             float rm = rmean[c], rv = rvar[c];
             for (int gg = 0; gg < (int)gridDim.y; ++gg) {
                 const BnCoef q = bn_coef(stats_all + (int64_t)gg * SBA_BN_STAT_SLOTS * 2 * C, gamma, beta, C, c, count, eps);
-                const float unb = count > 1.f ? q.var * count / (count - 1.f) : q.var;
-                rm = (1.f - momentum) * rm + momentum * q.mean;
-                rv = (1.f - momentum) * rv + momentum * unb;
+                running_update(rm, rv, q.mean, q.var, count, momentum);
             }
             rmean[c] = rm;
             rvar[c] = rv;
@@ -133,7 +234,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const YT* __restrict__ 
     const float* scale = s_co;
     const float* shift = s_co + C;
     const YT* y = y_all + (int64_t)g * rows * C;
-    const T* residual = residual_all ? residual_all + (int64_t)g * rows * Co : nullptr;
+    // (GLU takes no residual: the entry point refuses it)
+    const T* residual = ACT != SBA_ACT_GLU && residual_all ? residual_all + (int64_t)g * rows * Co : nullptr;
     T* out = out_all + (int64_t)g * rows * out_cstride;
     const int cv = Co / V;
     const int64_t total = rows * cv;
@@ -142,32 +244,23 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const YT* __restrict__ 
         const int64_t row = i / cv;
         const int c = (int)(i - row * cv) * V;
         Vec16<YT> a = ld16(y + row * C + c);
-        Vec16<T> o;
-        if (ACT == SBA_ACT_GLU) {
-            Vec16<YT> gt = ld16(y + row * C + Co + c);
+        Vec16<YT> gt = ACT == SBA_ACT_GLU ? ld16(y + row * C + Co + c) : a;     // the gate channels (GLU only)
+        Vec16<T> r, o;
+        if (residual) r = ld16(residual + row * Co + c);
 #pragma unroll
-            for (int k = 0; k < V; ++k) {
-                const float n = a.get(k) * scale[c + k] + shift[c + k];
-                const float gp = gt.get(k) * scale[Co + c + k] + shift[Co + c + k];
-                o.set(k, n * sigmoidf_(gp));
-            }
-        } else {
-            Vec16<T> r;
-            if (residual) r = ld16(residual + row * Co + c);
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                float n = a.get(k) * scale[c + k] + shift[c + k];
-                if (ACT == SBA_ACT_LRELU) n = n > 0.f ? n : LRELU_SLOPE * n;
-                if (ACT == SBA_ACT_RELU) n = fmaxf(n, 0.f);
-                if (residual) n += r.get(k);
-                o.set(k, n);
-            }
+        for (int k = 0; k < V; ++k) {
+            const int ca = c + k, cg = ACT == SBA_ACT_GLU ? Co + ca : ca;
+            float n = bn_act_elem<ACT>(a.get(k), scale[ca], shift[ca], gt.get(k), scale[cg], shift[cg]);
+            if (residual) n += r.get(k);
+            o.set(k, n);
         }
         st16(out + row * out_cstride + out_coff + c, o);
     }
 }
 
 // ---- backward pass 1: per-channel sum(dz), sum(dz*xhat); blockIdx.y = group ----
+// (This kernel keeps its element math and its LDS tail written out: with bn_bwd_elem the bf16 LeakyReLU variant took 116
+// instead of 112 VGPRs, and with ChannelSum alone its 32x32 row still measured 0.1-0.2 us above the hand-written tail.)
 // thread mapping: each thread keeps a fixed set of channel vectors and strides over rows
 template <typename T, typename YT, int ACT>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const YT* __restrict__ y_all, const T* __restrict__ dout_all,
@@ -326,17 +419,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const YT* __restrict_
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 const int ca = c + k, cg = Co + c + k;
-                const float n = a.get(k) * scale[ca] + shift[ca];
-                const float gp = gt.get(k) * scale[cg] + shift[cg];
-                const float s = sigmoid_bwd_(gp), dd = d.get(k);
-                const float dza = dd * s, dzg = dd * n * s * (1.f - s);
-                const float xa = (a.get(k) - mean[ca]) * rstd[ca];
-                const float xg = (gt.get(k) - mean[cg]) * rstd[cg];
-                o.set(k, scale[ca] * (dza - P[ca] - xa * Q[ca]));
-                og.set(k, scale[cg] * (dzg - P[cg] - xg * Q[cg]));
+                float dz[2], xh[2];
+                ChCoef ka, kg;
+                ch_coef_pair(scale, shift, mean, rstd, ca, cg, ka, kg);
+                bn_bwd_elem<ACT>(a.get(k), gt.get(k), d.get(k), ka, kg, dz, xh);
+                o.set(k, scale[ca] * (dz[0] - P[ca] - xh[0] * Q[ca]));
+                og.set(k, scale[cg] * (dz[1] - P[cg] - xh[1] * Q[cg]));
             }
             st16(dy + row * C + Co + c, og);
         } else {
+            // (written out: through bn_bwd_elem the bf16 kernel without activation takes one more VGPR and its 128x128 row
+            // measured 0.2-0.3 us above the parent's)
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 const int ca = c + k;
@@ -368,7 +461,7 @@ __global__ __launch_bounds__(256) void bn_fwd_fused_kernel(const YT* __restrict_
     constexpr int NV = ACT == SBA_ACT_GLU ? 2 : 1;
     __shared__ float s_red[4][2 * NV * V];
     __shared__ float s_co[2 * NV * V];                      // scale, shift per owned channel
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     const int Co = ACT == SBA_ACT_GLU ? C / 2 : C;
     const int c = blockIdx.x * V;
     const float count = (float)rows;
@@ -390,50 +483,25 @@ __global__ __launch_bounds__(256) void bn_fwd_fused_kernel(const YT* __restrict_
                 for (int k = 0; k < V; ++k) { const float v = a.get(k); s0[h][k] += v; s1[h][k] += v * v; }
             }
         }
-#pragma unroll
-        for (int h = 0; h < NV; ++h)
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                const float a0 = wave_sum(s0[h][k]), a1 = wave_sum(s1[h][k]);
-                if (lane == 0) { s_red[wid][(h * V + k) * 2] = a0; s_red[wid][(h * V + k) * 2 + 1] = a1; }
-            }
-        __syncthreads();
+        wave_sums_to_lds(s0, s1, s_red);
         if (tid < NV * V) {
             const int h = tid / V, k = tid - h * V, ch = c + h * Co + k;
-            const float t0 = s_red[0][tid * 2] + s_red[1][tid * 2] + s_red[2][tid * 2] + s_red[3][tid * 2];
-            const float t1 = s_red[0][tid * 2 + 1] + s_red[1][tid * 2 + 1] + s_red[2][tid * 2 + 1] + s_red[3][tid * 2 + 1];
-            const float mean = t0 / count;
-            const float var = fmaxf(t1 / count - mean * mean, 0.f);
-            const float rstd = rsqrtf(var + eps);
-            const float scale = gamma[ch] * rstd, shift = beta[ch] - mean * scale;
-            s_co[tid * 2] = scale;
-            s_co[tid * 2 + 1] = shift;
-            aux[ch] = scale; aux[C + ch] = shift; aux[2 * C + ch] = mean; aux[3 * C + ch] = rstd;
-            if (rmean) {
-                const float unb = count > 1.f ? var * count / (count - 1.f) : var;
-                rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * mean;
-                rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * unb;
-            }
+            const Moments m = moments_of(four_wave_sum(s_red, tid * 2), four_wave_sum(s_red, tid * 2 + 1), count, eps);
+            const BnCoef q = bn_affine(m.mean, m.var, m.rstd, gamma[ch], beta[ch]);
+            s_co[tid * 2] = q.scale;
+            s_co[tid * 2 + 1] = q.shift;
+            store_aux(aux, C, ch, q);
+            if (rmean) running_update(rmean[ch], rvar[ch], q.mean, q.var, count, momentum);
         }
         __syncthreads();
         for (int64_t row = tid; row < rows; row += 256) {
             Vec16<YT> a = ld16(y + row * C + c);
+            Vec16<YT> gt = ACT == SBA_ACT_GLU ? ld16(y + row * C + Co + c) : a;     // the gate channels (GLU only)
             Vec16<T> o;
-            if (ACT == SBA_ACT_GLU) {
-                Vec16<YT> gt = ld16(y + row * C + Co + c);
 #pragma unroll
-                for (int k = 0; k < V; ++k) {
-                    const float n = a.get(k) * s_co[k * 2] + s_co[k * 2 + 1];
-                    const float gp = gt.get(k) * s_co[(V + k) * 2] + s_co[(V + k) * 2 + 1];
-                    o.set(k, n * sigmoidf_(gp));
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < V; ++k) {
-                    float n = a.get(k) * s_co[k * 2] + s_co[k * 2 + 1];
-                    if (ACT == SBA_ACT_LRELU) n = n > 0.f ? n : LRELU_SLOPE * n;
-                    o.set(k, n);
-                }
+            for (int k = 0; k < V; ++k) {
+                const int kg = (NV - 1) * V + k;
+                o.set(k, bn_act_elem<ACT>(a.get(k), s_co[k * 2], s_co[k * 2 + 1], gt.get(k), s_co[kg * 2], s_co[kg * 2 + 1]));
             }
             st16(out + row * out_cstride + out_coff + c, o);
         }
@@ -454,21 +522,17 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const YT* __restrict_
     constexpr int NV = ACT == SBA_ACT_GLU ? 2 : 1;          // channel vectors owned (value [+ gate])
     __shared__ float s_red[4][2 * NV * V];
     __shared__ float s_tot[2 * NV * V];
-    const int g = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = blockIdx.y, tid = threadIdx.x;
     const int Co = ACT == SBA_ACT_GLU ? C / 2 : C;
     const int c = blockIdx.x * V;                           // first owned (value) channel
     const YT* y = y_all + (int64_t)g * rows * C;
     const T* dout = dout_all + (int64_t)g * rows * dcs;
     T* dy = dy_all + (int64_t)g * rows * C;
     const float* aux = aux_all + (int64_t)g * 4 * C;
-    float sc[NV][V], sh[NV][V], mn[NV][V], rs[NV][V];
+    ChCoef kc[NV][V];
 #pragma unroll
-    for (int h = 0; h < NV; ++h)
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const int ch = c + h * Co + k;
-            sc[h][k] = aux[ch]; sh[h][k] = aux[C + ch]; mn[h][k] = aux[2 * C + ch]; rs[h][k] = aux[3 * C + ch];
-        }
+    for (int k = 0; k < V; ++k)
+        ch_coef_pair(aux, aux + C, aux + 2 * C, aux + 3 * C, c + k, c + (NV - 1) * Co + k, kc[0][k], kc[NV - 1][k]);
     float s0[NV][V], s1[NV][V];
 #pragma unroll
     for (int h = 0; h < NV; ++h)
@@ -478,29 +542,13 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const YT* __restrict_
     auto dz_row = [&](int64_t row, float (&dz)[NV][V], float (&xh)[NV][V]) {
         Vec16<YT> a = ld16(y + row * C + c);
         Vec16<T> d = ld16(dout + row * dcs + dco + c);
-        if (ACT == SBA_ACT_GLU) {
-            Vec16<YT> gt = ld16(y + row * C + Co + c);
+        Vec16<YT> gt = ACT == SBA_ACT_GLU ? ld16(y + row * C + Co + c) : a;     // the gate channels (GLU only)
 #pragma unroll
-            for (int k = 0; k < V; ++k) {
-                const float n = a.get(k) * sc[0][k] + sh[0][k];
-                const float gp = gt.get(k) * sc[NV - 1][k] + sh[NV - 1][k];
-                const float sg = sigmoid_bwd_(gp), dd = d.get(k);
-                dz[0][k] = dd * sg;
-                dz[NV - 1][k] = dd * n * sg * (1.f - sg);
-                xh[0][k] = (a.get(k) - mn[0][k]) * rs[0][k];
-                xh[NV - 1][k] = (gt.get(k) - mn[NV - 1][k]) * rs[NV - 1][k];
-            }
-        } else {
+        for (int k = 0; k < V; ++k) {
+            float z[2], x[2];
+            bn_bwd_elem<ACT>(a.get(k), gt.get(k), d.get(k), kc[0][k], kc[NV - 1][k], z, x);
 #pragma unroll
-            for (int k = 0; k < V; ++k) {
-                float z = d.get(k);
-                if (ACT == SBA_ACT_LRELU) {
-                    const float n = a.get(k) * sc[0][k] + sh[0][k];
-                    z = n > 0.f ? z : LRELU_SLOPE * z;
-                }
-                dz[0][k] = z;
-                xh[0][k] = (a.get(k) - mn[0][k]) * rs[0][k];
-            }
+            for (int h = 0; h < NV; ++h) { dz[h][k] = z[h]; xh[h][k] = x[h]; }
         }
     };
     for (int64_t row = tid; row < rows; row += 256) {
@@ -511,15 +559,8 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const YT* __restrict_
 #pragma unroll
             for (int k = 0; k < V; ++k) { s0[h][k] += dz[h][k]; s1[h][k] += dz[h][k] * xh[h][k]; }
     }
-#pragma unroll
-    for (int h = 0; h < NV; ++h)
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const float a0 = wave_sum(s0[h][k]), a1 = wave_sum(s1[h][k]);
-            if (lane == 0) { s_red[wid][(h * V + k) * 2] = a0; s_red[wid][(h * V + k) * 2 + 1] = a1; }
-        }
-    __syncthreads();
-    if (tid < 2 * NV * V) s_tot[tid] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
+    wave_sums_to_lds(s0, s1, s_red);
+    if (tid < 2 * NV * V) s_tot[tid] = four_wave_sum(s_red, tid);
     __syncthreads();
     if (tid < NV * V && dgamma) {                           // groups accumulate into the same parameter
         const int h = tid / V, k = tid - h * V;
@@ -535,7 +576,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const YT* __restrict_
             Vec16<T> o;
 #pragma unroll
             for (int k = 0; k < V; ++k)
-                o.set(k, sc[h][k] * (dz[h][k] - s_tot[(h * V + k) * 2] * inv - xh[h][k] * s_tot[(h * V + k) * 2 + 1] * inv));
+                o.set(k, kc[h][k].scale * (dz[h][k] - s_tot[(h * V + k) * 2] * inv - xh[h][k] * s_tot[(h * V + k) * 2 + 1] * inv));
             st16(dy + row * C + c + h * Co, o);
         }
     }
@@ -543,73 +584,123 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const YT* __restrict_
 
 // ---- BatchNorm1d + GLU on [B][F] f32 with the NCHW->NHWC view permutation ----
 // feature f' in [0,F/2) pairs with gate f'+F/2; view(B, F/2/16, 4, 4): f' = c*16 + s
+// B <= BN1D_BM (the training batch): the B values of a column are loaded ONCE into registers, all loads in flight together
+// (three passes of dependent loads took 27 us for 20 x 16384 values at the head of the generator's forward pass); a larger
+// batch reads global memory at every use.  Same sums in the same order either way: each kernel's body is written once,
+// over sample_at and BN1D_EACH_SAMPLE.  (Plain loops, and the cache filled in the body, on purpose: a lambda that captures
+// the register cache, or a helper that fills it, costs bn1d_glu_bwd_kernel 31 VGPRs and a wave of occupancy.)
+constexpr int BN1D_BM = 32;
+// sample b of a column of p[B][stride]: from the register cache, or p[b * stride + col]
+template <bool CACHED, typename T, int N>
+__device__ __forceinline__ float sample_at(const float (&cache)[N], const T* __restrict__ p, int stride, int col, int b) {
+    if constexpr (CACHED) return cache[b];
+    else return to_f<T>(p[(int64_t)b * stride + col]);
+}
+// for every sample b < B: fully unrolled over the register cache (CACHED, a compile-time constant of the body), one
+// iteration at a time otherwise -- `unroll 1` pins the uncached loop, which the compiler was free to unroll before
+#define BN1D_EACH_SAMPLE(b, B, CACHED) \
+    _Pragma("unroll CACHED ? BN1D_BM : 1") for (int b = 0; b < (CACHED ? BN1D_BM : B); ++b) if (b < B)
+
+template <typename T, bool CACHED>
+__device__ __forceinline__ void bn1d_glu_fwd_body(const float* __restrict__ y, const float* __restrict__ gamma,
+                                                  const float* __restrict__ beta, float* __restrict__ rmean,
+                                                  float* __restrict__ rvar, float* __restrict__ mean_o,
+                                                  float* __restrict__ rstd_o, T* __restrict__ out, int B, int F, int f,
+                                                  float eps, float momentum) {
+    const int fh = F / 2, Cg = fh / 16;
+    float yv[2][CACHED ? BN1D_BM : 1];
+    if constexpr (CACHED) {
+#pragma unroll
+        for (int b = 0; b < BN1D_BM; ++b) {
+            yv[0][b] = b < B ? y[(int64_t)b * F + f] : 0.f;
+            yv[1][b] = b < B ? y[(int64_t)b * F + f + fh] : 0.f;
+        }
+    }
+    float sc[2], sh[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int ff = f + h * fh;
+        float s = 0.f, q = 0.f;
+        BN1D_EACH_SAMPLE(b, B, CACHED) s += sample_at<CACHED>(yv[h], y, F, ff, b);
+        const float mean = s / B;
+        BN1D_EACH_SAMPLE(b, B, CACHED) { const float v = sample_at<CACHED>(yv[h], y, F, ff, b) - mean; q += v * v; }    // centred: two passes
+        const float var = q / B, r = rsqrtf(var + eps);
+        // (y * scale + shift: the form the step's forward values were validated with.  The backward kernel recomputes the
+        // pre-activation as (y - mean) * scale + beta, which does not cancel at a tiny batch variance; see there)
+        sc[h] = gamma[ff] * r; sh[h] = beta[ff] - mean * sc[h];
+        mean_o[ff] = mean; rstd_o[ff] = r;
+        if (rmean) running_update(rmean[ff], rvar[ff], mean, var, (float)B, momentum);
+    }
+    const int c = f / 16, s16 = f % 16;
+    BN1D_EACH_SAMPLE(b, B, CACHED) {
+        const float ya = sample_at<CACHED>(yv[0], y, F, f, b), yg = sample_at<CACHED>(yv[1], y, F, f + fh, b);
+        // (fmaf: the contraction the compiler made of y * scale + shift while the expression stood here alone; through
+        // bn_act_elem the vectoriser pairs the add with one of __expf's and leaves it unfused -- other bits in `out`)
+        const float n = fmaf(ya, sc[0], sh[0]), gp = fmaf(yg, sc[1], sh[1]);
+        out[((int64_t)b * 16 + s16) * Cg + c] = from_f<T>(n * sigmoidf_(gp));
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn1d_glu_fwd_kernel(const float* __restrict__ y, const float* __restrict__ gamma,
                                     const float* __restrict__ beta, float* __restrict__ rmean,
                                     float* __restrict__ rvar, int64_t* __restrict__ nbt,
                                     float* __restrict__ mean_o, float* __restrict__ rstd_o,
                                     T* __restrict__ out, int B, int F, float eps, float momentum) {
-    const int fh = F / 2, Cg = fh / 16;
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f == 0 && nbt) *nbt += 1;
-    if (f >= fh) return;
-    float m[2], r[2], sc[2], sh[2];
-    // B <= 32 (the training batch): the 2 B values of this feature pair are loaded ONCE, all loads in flight together (three
-    // passes of dependent loads took 27 us for 20 x 16384 values at the head of the generator's forward pass); same sums in
-    // the same order
-    constexpr int BM = 32;
-    float yv[2][BM];
-    const bool cached = B <= BM;
-    if (cached) {
+    if (f >= F / 2) return;
+    if (B <= BN1D_BM) bn1d_glu_fwd_body<T, true>(y, gamma, beta, rmean, rvar, mean_o, rstd_o, out, B, F, f, eps, momentum);
+    else bn1d_glu_fwd_body<T, false>(y, gamma, beta, rmean, rvar, mean_o, rstd_o, out, B, F, f, eps, momentum);
+}
+
+// dz of one sample's value and gate feature.  The pre-activations are recomputed as (y - mean) * scale + beta, not
+// y * scale + shift: with a tiny batch variance (B = 2, two nearly equal samples: rstd up to 316) y * scale and shift are
+// two large numbers that cancel, and the gate's rounding error (4e-5) reaches dgamma / dbeta
+struct Bn1dCoef { float scale, beta, mean, rstd; };
+__device__ __forceinline__ void bn1d_glu_dz(float ya, float yg, float dd, const Bn1dCoef& ka, const Bn1dCoef& kg,
+                                            float& dza, float& dzg) {
+    const float n = (ya - ka.mean) * ka.scale + ka.beta, gp = (yg - kg.mean) * kg.scale + kg.beta, s = sigmoidf_(gp);
+    dza = dd * s;
+    dzg = dd * n * s * (1.f - s);
+}
+
+template <typename T, bool CACHED>
+__device__ __forceinline__ void bn1d_glu_bwd_body(const float* __restrict__ y, const T* __restrict__ dout,
+                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                  float* __restrict__ dy, float* __restrict__ dgamma,
+                                                  float* __restrict__ dbeta, int B, int F, int f) {
+    const int fh = F / 2, Cg = fh / 16;
+    const int fa = f, fg = f + fh, dcol = (f % 16) * Cg + f / 16;       // dout[b][s16][c]: column s16 * Cg + c of 16 * Cg
+    const Bn1dCoef ka{gamma[fa] * rstd[fa], beta[fa], mean[fa], rstd[fa]}, kg{gamma[fg] * rstd[fg], beta[fg], mean[fg], rstd[fg]};
+    constexpr int NB = CACHED ? BN1D_BM : 1;
+    float ya_[NB], yg_[NB], dd_[NB];
+    if constexpr (CACHED) {
 #pragma unroll
-        for (int b = 0; b < BM; ++b) {
-            yv[0][b] = b < B ? y[(int64_t)b * F + f] : 0.f;
-            yv[1][b] = b < B ? y[(int64_t)b * F + f + fh] : 0.f;
+        for (int b = 0; b < BN1D_BM; ++b) {
+            ya_[b] = b < B ? y[(int64_t)b * F + fa] : 0.f;
+            yg_[b] = b < B ? y[(int64_t)b * F + fg] : 0.f;
+            dd_[b] = b < B ? to_f<T>(dout[(int64_t)b * (16 * Cg) + dcol]) : 0.f;
         }
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int ff = f + h * fh;
-        float s = 0.f, q = 0.f;
-        if (cached) {
-#pragma unroll
-            for (int b = 0; b < BM; ++b) if (b < B) s += yv[h][b];
-        } else {
-            for (int b = 0; b < B; ++b) { const float v = y[(int64_t)b * F + ff]; s += v; }
-        }
-        const float mean = s / B;
-        if (cached) {
-#pragma unroll
-            for (int b = 0; b < BM; ++b) if (b < B) { const float v = yv[h][b] - mean; q += v * v; }
-        } else {
-            for (int b = 0; b < B; ++b) { const float v = y[(int64_t)b * F + ff] - mean; q += v * v; }
-        }
-        const float var = q / B;
-        m[h] = mean; r[h] = rsqrtf(var + eps);
-        // (y * scale + shift: the form the step's forward values were validated with.  The backward kernel recomputes the
-        // pre-activation as (y - mean) * scale + beta, which does not cancel at a tiny batch variance; see there)
-        sc[h] = gamma[ff] * r[h]; sh[h] = beta[ff] - mean * sc[h];
-        mean_o[ff] = mean; rstd_o[ff] = r[h];
-        if (rmean) {
-            const float unb = B > 1 ? var * B / (B - 1.f) : var;
-            rmean[ff] = (1.f - momentum) * rmean[ff] + momentum * mean;
-            rvar[ff] = (1.f - momentum) * rvar[ff] + momentum * unb;
-        }
+    float a0 = 0.f, a1 = 0.f, g0 = 0.f, g1 = 0.f;
+    BN1D_EACH_SAMPLE(b, B, CACHED) {
+        const float ya = sample_at<CACHED>(ya_, y, F, fa, b), yg = sample_at<CACHED>(yg_, y, F, fg, b);
+        float dza, dzg;
+        bn1d_glu_dz(ya, yg, sample_at<CACHED>(dd_, dout, 16 * Cg, dcol, b), ka, kg, dza, dzg);
+        a0 += dza; a1 += dza * (ya - ka.mean) * ka.rstd;
+        g0 += dzg; g1 += dzg * (yg - kg.mean) * kg.rstd;
     }
-    const int c = f / 16, s16 = f % 16;
-    if (cached) {
-#pragma unroll
-        for (int b = 0; b < BM; ++b)
-            if (b < B) {
-                const float n = yv[0][b] * sc[0] + sh[0], gp = yv[1][b] * sc[1] + sh[1];
-                out[((int64_t)b * 16 + s16) * Cg + c] = from_f<T>(n * sigmoidf_(gp));
-            }
-        return;
-    }
-    for (int b = 0; b < B; ++b) {
-        const float n = y[(int64_t)b * F + f] * sc[0] + sh[0];
-        const float gp = y[(int64_t)b * F + f + fh] * sc[1] + sh[1];
-        out[((int64_t)b * 16 + s16) * Cg + c] = from_f<T>(n * sigmoidf_(gp));
+    dgamma[fa] += a1; dbeta[fa] += a0;
+    dgamma[fg] += g1; dbeta[fg] += g0;
+    const float inv = 1.f / B;
+    BN1D_EACH_SAMPLE(b, B, CACHED) {
+        const float ya = sample_at<CACHED>(ya_, y, F, fa, b), yg = sample_at<CACHED>(yg_, y, F, fg, b);
+        float dza, dzg;
+        bn1d_glu_dz(ya, yg, sample_at<CACHED>(dd_, dout, 16 * Cg, dcol, b), ka, kg, dza, dzg);
+        dy[(int64_t)b * F + fa] = ka.scale * (dza - a0 * inv - (ya - ka.mean) * ka.rstd * a1 * inv);
+        dy[(int64_t)b * F + fg] = kg.scale * (dzg - g0 * inv - (yg - kg.mean) * kg.rstd * g1 * inv);
     }
 }
 
@@ -619,67 +710,10 @@ __global__ __launch_bounds__(256) void bn1d_glu_bwd_kernel(const float* __restri
                                     const float* __restrict__ mean, const float* __restrict__ rstd,
                                     float* __restrict__ dy, float* __restrict__ dgamma,
                                     float* __restrict__ dbeta, int B, int F) {
-    const int fh = F / 2, Cg = fh / 16;
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= fh) return;
-    const int c = f / 16, s16 = f % 16;
-    const int fa = f, fg = f + fh;
-    // the pre-activations are recomputed as (y - mean) * scale + beta, not y * scale + shift: with a tiny batch variance
-    // (B = 2, two nearly equal samples: rstd up to 316) y * scale and shift are two large numbers that cancel, and the
-    // gate's rounding error (4e-5) reaches dgamma / dbeta
-    const float sca = gamma[fa] * rstd[fa], ba = beta[fa], ma = mean[fa];
-    const float scg = gamma[fg] * rstd[fg], bg = beta[fg], mg = mean[fg];
-    float a0 = 0.f, a1 = 0.f, g0 = 0.f, g1 = 0.f;
-    constexpr int BM = 32;
-    if (B <= BM) {          // one pass of loads, all in flight together (see bn1d_glu_fwd_kernel); same sums, same order
-        float ya_[BM], yg_[BM], dd_[BM];
-        const float ra = rstd[fa], rg = rstd[fg];
-#pragma unroll
-        for (int b = 0; b < BM; ++b) {
-            ya_[b] = b < B ? y[(int64_t)b * F + fa] : 0.f;
-            yg_[b] = b < B ? y[(int64_t)b * F + fg] : 0.f;
-            dd_[b] = b < B ? to_f<T>(dout[((int64_t)b * 16 + s16) * Cg + c]) : 0.f;
-        }
-#pragma unroll
-        for (int b = 0; b < BM; ++b)
-            if (b < B) {
-                const float n = (ya_[b] - ma) * sca + ba, gp = (yg_[b] - mg) * scg + bg, s = sigmoidf_(gp);
-                const float dza = dd_[b] * s, dzg = dd_[b] * n * s * (1.f - s);
-                a0 += dza; a1 += dza * (ya_[b] - ma) * ra;
-                g0 += dzg; g1 += dzg * (yg_[b] - mg) * rg;
-            }
-        dgamma[fa] += a1; dbeta[fa] += a0;
-        dgamma[fg] += g1; dbeta[fg] += g0;
-        const float inv = 1.f / B;
-#pragma unroll
-        for (int b = 0; b < BM; ++b)
-            if (b < B) {
-                const float n = (ya_[b] - ma) * sca + ba, gp = (yg_[b] - mg) * scg + bg, s = sigmoidf_(gp);
-                const float dza = dd_[b] * s, dzg = dd_[b] * n * s * (1.f - s);
-                dy[(int64_t)b * F + fa] = sca * (dza - a0 * inv - (ya_[b] - ma) * ra * a1 * inv);
-                dy[(int64_t)b * F + fg] = scg * (dzg - g0 * inv - (yg_[b] - mg) * rg * g1 * inv);
-            }
-        return;
-    }
-    for (int b = 0; b < B; ++b) {
-        const float ya = y[(int64_t)b * F + fa], yg = y[(int64_t)b * F + fg];
-        const float n = (ya - ma) * sca + ba, gp = (yg - mg) * scg + bg, s = sigmoidf_(gp);
-        const float dd = to_f<T>(dout[((int64_t)b * 16 + s16) * Cg + c]);
-        const float dza = dd * s, dzg = dd * n * s * (1.f - s);
-        a0 += dza; a1 += dza * (ya - mean[fa]) * rstd[fa];
-        g0 += dzg; g1 += dzg * (yg - mean[fg]) * rstd[fg];
-    }
-    dgamma[fa] += a1; dbeta[fa] += a0;
-    dgamma[fg] += g1; dbeta[fg] += g0;
-    const float inv = 1.f / B;
-    for (int b = 0; b < B; ++b) {
-        const float ya = y[(int64_t)b * F + fa], yg = y[(int64_t)b * F + fg];
-        const float n = (ya - ma) * sca + ba, gp = (yg - mg) * scg + bg, s = sigmoidf_(gp);
-        const float dd = to_f<T>(dout[((int64_t)b * 16 + s16) * Cg + c]);
-        const float dza = dd * s, dzg = dd * n * s * (1.f - s);
-        dy[(int64_t)b * F + fa] = sca * (dza - a0 * inv - (ya - mean[fa]) * rstd[fa] * a1 * inv);
-        dy[(int64_t)b * F + fg] = scg * (dzg - g0 * inv - (yg - mean[fg]) * rstd[fg] * g1 * inv);
-    }
+    if (f >= F / 2) return;
+    if (B <= BN1D_BM) bn1d_glu_bwd_body<T, true>(y, dout, gamma, beta, mean, rstd, dy, dgamma, dbeta, B, F, f);
+    else bn1d_glu_bwd_body<T, false>(y, dout, gamma, beta, mean, rstd, dy, dgamma, dbeta, B, F, f);
 }
 
 // ---- InstanceNorm statistics / AdaIN ----
@@ -692,10 +726,8 @@ __global__ __launch_bounds__(256) void instnorm_accum_kernel(const T* __restrict
     const int rpi = blockDim.x / cv;
     const int tc = threadIdx.x % cv, tr = threadIdx.x / cv;
     extern __shared__ float s_acc[];   // [2*C]; deterministic mode (one workgroup per image): [rpi][2*C]
-    if (!det) {
-        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) s_acc[i] = 0.f;
-        __syncthreads();
-    }
+    const ChannelSum cs{s_acc, C, det != 0};
+    cs.clear();
     float s0[V], s1[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) s0[k] = s1[k] = 0.f;
@@ -705,30 +737,14 @@ __global__ __launch_bounds__(256) void instnorm_accum_kernel(const T* __restrict
 #pragma unroll
             for (int k = 0; k < V; ++k) { const float v = a.get(k); s0[k] += v; s1[k] += v * v; }
         }
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            if (det) {
-                s_acc[tr * 2 * C + tc * V + k] = s0[k];
-                s_acc[tr * 2 * C + C + tc * V + k] = s1[k];
-            } else {
-                atomicAdd(&s_acc[tc * V + k], s0[k]);
-                atomicAdd(&s_acc[C + tc * V + k], s1[k]);
-            }
-        }
+        cs.add(tr, tc * V, s0, s1);
     }
-    __syncthreads();
-    if (det) {              // gridDim.y == 1: this workgroup owns image n; row-groups added in order, plain stores
-        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-            float v = 0.f;
-            for (int r = 0; r < rpi; ++r) v += s_acc[r * 2 * C + i];
-            if (i < C) sum[n * C + i] = v; else sumsq[n * C + i - C] = v;
-        }
-        return;
-    }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) {
-        atomicAdd(&sum[n * C + i], s_acc[i]);
-        atomicAdd(&sumsq[n * C + i], s_acc[C + i]);
-    }
+    // (deterministic mode, gridDim.y == 1: this workgroup owns image n -- plain stores)
+    cs.finish(rpi, [&](int i, float v) {
+        float* dst = i < C ? &sum[n * C + i] : &sumsq[n * C + i - C];
+        if (det) *dst = v;
+        else atomicAdd(dst, v);
+    });
 }
 
 // The same statistics in ONE launch, no atomics, no clearing, no finalize pass: workgroup (n, tc) owns 16-byte channel vector tc
@@ -763,19 +779,16 @@ __global__ __launch_bounds__(256) void instnorm_stats_fused_kernel(const T* __re
     __shared__ float s_part[4][2 * V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-        float a = s0[k], b = s1[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        const float a = wave_sum(s0[k]), b = wave_sum(s1[k]);
         if ((tid & 63) == 0) { s_part[tid >> 6][k] = a; s_part[tid >> 6][V + k] = b; }
     }
     __syncthreads();
     if (tid < V) {
         const float sm = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
         const float sq = (s_part[0][V + tid] + s_part[1][V + tid]) + (s_part[2][V + tid] + s_part[3][V + tid]);
-        const float m = sm / (float)HW;
-        const float var = fmaxf(sq / (float)HW - m * m, 0.f);
-        mean[n * C + tc * V + tid] = m;
-        rstd[n * C + tc * V + tid] = rsqrtf(var + eps);
+        const Moments m = moments_of(sm, sq, (float)HW, eps);
+        mean[n * C + tc * V + tid] = m.mean;
+        rstd[n * C + tc * V + tid] = m.rstd;
     }
 }
 
@@ -783,10 +796,9 @@ __global__ __launch_bounds__(256) void instnorm_finalize_kernel(float* __restric
                                          float HW, float eps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= NC) return;
-    const float m = mean[i] / HW;
-    const float var = fmaxf(rstd[i] / HW - m * m, 0.f);
-    mean[i] = m;
-    rstd[i] = rsqrtf(var + eps);
+    const Moments m = moments_of(mean[i], rstd[i], HW, eps);
+    mean[i] = m.mean;
+    rstd[i] = m.rstd;
 }
 
 template <typename T>
@@ -821,10 +833,8 @@ __global__ __launch_bounds__(256) void adain_bwd_reduce_kernel(const T* __restri
     const int rpi = blockDim.x / cv;
     const int tc = threadIdx.x % cv, tr = threadIdx.x / cv;
     extern __shared__ float s_acc[];   // [2*C]; deterministic mode (one workgroup per image): [rpi][2*C]
-    if (!det) {
-        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) s_acc[i] = 0.f;
-        __syncthreads();
-    }
+    const ChannelSum cs{s_acc, C, det != 0};
+    cs.clear();
     float s0[V], s1[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) s0[k] = s1[k] = 0.f;
@@ -841,30 +851,13 @@ __global__ __launch_bounds__(256) void adain_bwd_reduce_kernel(const T* __restri
                 s1[k] += d.get(k);
             }
         }
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            if (det) {
-                s_acc[tr * 2 * C + tc * V + k] = s0[k];
-                s_acc[tr * 2 * C + C + tc * V + k] = s1[k];
-            } else {
-                atomicAdd(&s_acc[tc * V + k], s0[k]);
-                atomicAdd(&s_acc[C + tc * V + k], s1[k]);
-            }
-        }
+        cs.add(tr, tc * V, s0, s1);
     }
-    __syncthreads();
-    if (det) {
-        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-            float v = 0.f;
-            for (int r = 0; r < rpi; ++r) v += s_acc[r * 2 * C + i];
-            if (i < C) red[(n * C + i) * 2 + 0] += v; else red[(n * C + i - C) * 2 + 1] += v;
-        }
-        return;
-    }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) {
-        atomicAdd(&red[(n * C + i) * 2 + 0], s_acc[i]);
-        atomicAdd(&red[(n * C + i) * 2 + 1], s_acc[C + i]);
-    }
+    cs.finish(rpi, [&](int i, float v) {
+        float* dst = i < C ? &red[(n * C + i) * 2 + 0] : &red[(n * C + i - C) * 2 + 1];
+        if (det) *dst += v;
+        else atomicAdd(dst, v);
+    });
 }
 
 template <typename T>
@@ -913,49 +906,93 @@ inline int grid_for(int64_t items, int cap = 4096) {
 }
 inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
+inline int vec_width(int dtype) { return dtype != SBA_F32 ? 8 : 4; }       // elements per 16-byte vector
+inline int64_t elem_size(int dtype) { return dtype != SBA_F32 ? 2 : 4; }
+// a `width` channel slice at `offset` of rows `stride` channels apart, all three in whole vectors
+inline bool slice_ok(int stride, int offset, int width, int V) {
+    return stride >= width + offset && stride % V == 0 && offset % V == 0;
+}
+inline int act_width(int C, int act) { return act == SBA_ACT_GLU ? C / 2 : C; }  // channels after the activation
+
+// Grid of the two channel-sum passes (bn_stats_kernel, bn_bwd_reduce_kernel): rpi rows per iteration of a workgroup.
+// Every workgroup ends with 2C same-address f32 atomics per replica: measured (tools/bench_bn.py) 85 -> 63 us at
+// 256x256 and 64 -> 43 us at 128x128 going from 1024 to 512 workgroups in total (two per CU)
+constexpr int BN_RED_WORKGROUPS = 512;                      // over all groups ...
+constexpr int BN_RED_WORKGROUPS_PER_GROUP = 64;             // ... but at least this many for each
+struct ReduceGrid { int rpi, blocks; };
+inline ReduceGrid reduce_grid(int64_t rows, int cv, int groups) {
+    ReduceGrid r;
+    r.rpi = cv < 256 ? 256 / cv : 1;
+    r.blocks = cdiv(rows, (int64_t)r.rpi * 8);
+    const int cap = BN_RED_WORKGROUPS / groups > BN_RED_WORKGROUPS_PER_GROUP ? BN_RED_WORKGROUPS / groups
+                                                                              : BN_RED_WORKGROUPS_PER_GROUP;
+    if (r.blocks > cap) r.blocks = cap;
+    if (r.blocks < 1) r.blocks = 1;
+    return r;
+}
+// One channel-sum pass into dst[groups][SBA_BN_STAT_SLOTS][2*C]: launch(lds_bytes, part) starts the kernel.  Deterministic
+// mode: each workgroup gets a slot of scratch (`part`) and one LDS row per row-group, and the workgroups' partial sums are
+// added in workgroup order into replica 0 (the others stay zero).
+template <typename Launch>
+int reduce_pass(int groups, ReduceGrid rg, int C, float* dst, hipStream_t st, Launch launch) {
+    float* part = nullptr;
+    size_t sh = 2 * (size_t)C * sizeof(float);
+    if (sba_det_on()) {
+        part = sba_det_alloc((int64_t)groups * rg.blocks * 2 * C);
+        if (!part) return SBA_E_ARG;
+        sh *= rg.rpi;
+    }
+    const int rc = launch(sh, part);
+    if (rc != SBA_OK) return rc;
+    if (part) sba_det_fold(part, groups, rg.blocks, 2 * C, dst, (int64_t)SBA_BN_STAT_SLOTS * 2 * C, 0, st);
+    return SBA_CHECK_LAUNCH();
+}
+// A backward launch whose groups add into the same dgamma / dbeta: launch(g0, ng) covers groups [g0, g0 + ng).  All
+// groups at once, or in deterministic mode one launch per group, in group order.
+template <typename Launch>
+int param_grad_pass(int groups, bool param_grads, Launch launch) {
+    const int step = sba_det_on() && groups > 1 && param_grads ? 1 : groups;
+    for (int g = 0; g < groups; g += step) {
+        const int rc = launch(g, step);
+        if (rc != SBA_OK) return rc;
+    }
+    return SBA_CHECK_LAUNCH();
+}
+// workgroups per image of the two InstanceNorm channel-sum passes (deterministic mode: one, row-groups added in order)
+inline int instnorm_splits(int HW, int rpi, bool det) {
+    const int splits = cdiv(HW, rpi * 16);
+    return det ? 1 : splits > 256 ? 256 : splits;
+}
+
 }  // namespace
 
 extern "C" int sba_bn_stats(int dtype, const void* y, float* stats, int64_t rows, int groups, int C,
                             void* stream) {
-    const int V = dtype != SBA_F32 ? 8 : 4;
+    const int V = vec_width(dtype);
     if (!y || !stats || rows <= 0 || groups <= 0 || groups > 65535 || C <= 0 || C % V || C > 4096)
         return SBA_E_ARG;
-    const int cv = C / V;
-    const int rpi = cv < 256 ? 256 / cv : 1;
-    int blocks = cdiv(rows, (int64_t)rpi * 8);
-    // every workgroup ends with 2C same-address f32 atomics per replica: measured (tools/bench_bn.py) 85 -> 63 us at
-    // 256x256 and 64 -> 43 us at 128x128 going from 1024 to 512 workgroups in total (two per CU)
-    static int cap = -1;
-    if (cap < 0) { const char* e = getenv("SBA_BN_RED_BLOCKS"); cap = e ? atoi(e) : 512; }
-    const int cap_g = cap / groups > 64 ? cap / groups : 64;
-    if (blocks > cap_g) blocks = cap_g;
-    if (blocks < 1) blocks = 1;
-    float* part = nullptr;
-    size_t sh = 2 * (size_t)C * sizeof(float);
-    if (sba_det_on()) {
-        part = sba_det_alloc((int64_t)groups * blocks * 2 * C);
-        if (!part) return SBA_E_ARG;
-        sh *= rpi;
-    }
-    SBA_DISPATCH_Y(dtype, SBA_LAUNCH((bn_stats_kernel<YT>), dim3(blocks, groups), dim3(256), sh, (hipStream_t)stream,
-                                     (const YT*)y, stats, rows, C, part));
-    // deterministic mode: the workgroups' partial sums are added in workgroup order into replica 0 (the others stay zero)
-    if (part) sba_det_fold(part, groups, blocks, 2 * C, stats, (int64_t)SBA_BN_STAT_SLOTS * 2 * C, 0, (hipStream_t)stream);
-    return SBA_CHECK_LAUNCH();
+    const ReduceGrid rg = reduce_grid(rows, C / V, groups);
+    return reduce_pass(groups, rg, C, stats, (hipStream_t)stream, [&](size_t sh, float* part) -> int {
+        SBA_DISPATCH_Y(dtype, SBA_LAUNCH((bn_stats_kernel<YT>), dim3(rg.blocks, groups), dim3(256), sh, (hipStream_t)stream,
+                                         (const YT*)y, stats, rows, C, part));
+        return SBA_OK;
+    });
 }
 
-#define ACT_SWITCH(act, CALL)                                                   \
-    switch (act) {                                                              \
-        case SBA_ACT_NONE: { constexpr int ACT = SBA_ACT_NONE; CALL; } break;   \
-        case SBA_ACT_GLU: { constexpr int ACT = SBA_ACT_GLU; CALL; } break;     \
-        case SBA_ACT_LRELU: { constexpr int ACT = SBA_ACT_LRELU; CALL; } break; \
-        default: return SBA_E_ARG;                                              \
+// ACT_SWITCH: the activations that have a backward; ACT_SWITCH_FWD adds ReLU (sba_bn_act_fwd only: the Inception trunk)
+#define ACT_CASE(A, ...) case A: { constexpr int ACT = A; __VA_ARGS__; } break;
+#define ACT_SWITCH_(act, EXTRA_CASE, ...)                                                                       \
+    switch (act) {                                                                                               \
+        ACT_CASE(SBA_ACT_NONE, __VA_ARGS__) ACT_CASE(SBA_ACT_GLU, __VA_ARGS__) ACT_CASE(SBA_ACT_LRELU, __VA_ARGS__) \
+        EXTRA_CASE                                                                                               \
+        default: return SBA_E_ARG;                                                                               \
     }
+#define ACT_SWITCH(act, ...) ACT_SWITCH_(act, , __VA_ARGS__)
+#define ACT_SWITCH_FWD(act, ...) ACT_SWITCH_(act, ACT_CASE(SBA_ACT_RELU, __VA_ARGS__), __VA_ARGS__)
 
 static bool bn_shape_ok(int dtype, int64_t rows, int groups, int C, int act) {
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    const int Co = act == SBA_ACT_GLU ? C / 2 : C;
-    return rows > 0 && groups > 0 && groups <= 65535 && C > 0 && pow2(C) && Co % V == 0 && C <= 4096;
+    return rows > 0 && groups > 0 && groups <= 65535 && C > 0 && pow2(C) && act_width(C, act) % vec_width(dtype) == 0 &&
+           C <= 4096;
 }
 
 extern "C" int sba_bn_act_fwd(int dtype, const void* y, const float* stats, const float* gamma,
@@ -965,62 +1002,37 @@ extern "C" int sba_bn_act_fwd(int dtype, const void* y, const float* stats, cons
                               float momentum, int training, void* stream) {
     // (the forward kernel indexes channels generically: any C that is a multiple of the vector width -- the Inception
     // trunk's 80 / 96 / 160 / 192 / 320 / 448 ... channel BatchNorms in the DAMSM pre-training loop)
-    const int Vw = dtype != SBA_F32 ? 8 : 4;
+    const int V = vec_width(dtype), Co = act_width(C, act);
     const bool shape_ok = rows > 0 && groups > 0 && groups <= 65535 && C > 0 && C <= 4096 &&
-                          (act == SBA_ACT_GLU ? (C / 2) % Vw == 0 && C % 2 == 0 : C % Vw == 0);
+                          (act == SBA_ACT_GLU ? Co % V == 0 && C % 2 == 0 : C % V == 0);
     if (!y || !gamma || !beta || !aux || !out || !shape_ok) return SBA_E_ARG;
     if (training ? !stats : (!running_mean || !running_var)) return SBA_E_ARG;
     if ((running_mean == nullptr) != (running_var == nullptr)) return SBA_E_ARG;
     if (act == SBA_ACT_GLU && residual) return SBA_E_ARG;
-    const int Co = act == SBA_ACT_GLU ? C / 2 : C;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (out_cstride < Co + out_coff || out_cstride % V || out_coff % V) return SBA_E_ARG;
+    if (!slice_ok(out_cstride, out_coff, Co, V)) return SBA_E_ARG;
     const int blocks = grid_for(rows * (Co / V));
     const size_t sh = 2 * (size_t)C * sizeof(float);
-    if (act == SBA_ACT_RELU) {
-        SBA_DISPATCH_Y(dtype, SBA_LAUNCH((bn_act_fwd_kernel<T, YT, SBA_ACT_RELU>), dim3(blocks, groups), dim3(256), sh,
-                                         (hipStream_t)stream, (const YT*)y, stats, gamma, beta, running_mean, running_var,
-                                         num_batches_tracked, aux, (const T*)residual, (T*)out, rows, C, out_cstride,
-                                         out_coff, eps, momentum, training));
-        return SBA_CHECK_LAUNCH();
-    }
-    SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_act_fwd_kernel<T, YT, ACT>), dim3(blocks, groups),
-                                                           dim3(256), sh, (hipStream_t)stream, (const YT*)y, stats,
-                                                           gamma, beta, running_mean, running_var,
-                                                           num_batches_tracked, aux, (const T*)residual, (T*)out,
-                                                           rows, C, out_cstride, out_coff, eps, momentum,
-                                                           training)));
+    SBA_DISPATCH_Y(dtype, ACT_SWITCH_FWD(act, SBA_LAUNCH((bn_act_fwd_kernel<T, YT, ACT>), dim3(blocks, groups),
+                                                               dim3(256), sh, (hipStream_t)stream, (const YT*)y, stats,
+                                                               gamma, beta, running_mean, running_var,
+                                                               num_batches_tracked, aux, (const T*)residual, (T*)out,
+                                                               rows, C, out_cstride, out_coff, eps, momentum,
+                                                               training)));
     return SBA_CHECK_LAUNCH();
 }
 
 extern "C" int sba_bn_act_bwd_reduce(int dtype, const void* y, const void* dout, const float* aux, float* red,
                                      int64_t rows, int groups, int C, int act, int dcs, int dco, void* stream) {
     if (!y || !dout || !aux || !red || !bn_shape_ok(dtype, rows, groups, C, act)) return SBA_E_ARG;
-    const int Co = act == SBA_ACT_GLU ? C / 2 : C;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (dcs < Co + dco || dcs % V || dco % V) return SBA_E_ARG;
-    const int cv = Co / V;
-    const int rpi = cv < 256 ? 256 / cv : 1;
-    int blocks = cdiv(rows, (int64_t)rpi * 8);
-    // every workgroup ends with 2C same-address f32 atomics per replica: measured (tools/bench_bn.py) 85 -> 63 us at
-    // 256x256 and 64 -> 43 us at 128x128 going from 1024 to 512 workgroups in total (two per CU)
-    static int cap = -1;
-    if (cap < 0) { const char* e = getenv("SBA_BN_RED_BLOCKS"); cap = e ? atoi(e) : 512; }
-    const int cap_g = cap / groups > 64 ? cap / groups : 64;
-    if (blocks > cap_g) blocks = cap_g;
-    if (blocks < 1) blocks = 1;
-    size_t sh = 2 * (size_t)C * sizeof(float);
-    float* part = nullptr;
-    if (sba_det_on()) {
-        part = sba_det_alloc((int64_t)groups * blocks * 2 * C);
-        if (!part) return SBA_E_ARG;
-        sh *= rpi;
-    }
-    SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_reduce_kernel<T, YT, ACT>), dim3(blocks, groups),
-                                                           dim3(256), sh, (hipStream_t)stream, (const YT*)y,
-                                                           (const T*)dout, aux, red, rows, C, dcs, dco, part)));
-    if (part) sba_det_fold(part, groups, blocks, 2 * C, red, (int64_t)SBA_BN_STAT_SLOTS * 2 * C, 0, (hipStream_t)stream);
-    return SBA_CHECK_LAUNCH();
+    const int V = vec_width(dtype), Co = act_width(C, act);
+    if (!slice_ok(dcs, dco, Co, V)) return SBA_E_ARG;
+    const ReduceGrid rg = reduce_grid(rows, Co / V, groups);
+    return reduce_pass(groups, rg, C, red, (hipStream_t)stream, [&](size_t sh, float* part) -> int {
+        SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_reduce_kernel<T, YT, ACT>), dim3(rg.blocks, groups),
+                                                               dim3(256), sh, (hipStream_t)stream, (const YT*)y,
+                                                               (const T*)dout, aux, red, rows, C, dcs, dco, part)));
+        return SBA_OK;
+    });
 }
 
 extern "C" int sba_bn_act_bwd_apply(int dtype, const void* y, const void* dout, const float* aux,
@@ -1028,31 +1040,22 @@ extern "C" int sba_bn_act_bwd_apply(int dtype, const void* y, const void* dout, 
                                     int groups, int C, int act, int dcs, int dco, void* stream) {
     if (!y || !dout || !aux || !red || !dy || !bn_shape_ok(dtype, rows, groups, C, act)) return SBA_E_ARG;
     if ((dgamma == nullptr) != (dbeta == nullptr)) return SBA_E_ARG;
-    const int Co = act == SBA_ACT_GLU ? C / 2 : C;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (dcs < Co + dco || dcs % V || dco % V) return SBA_E_ARG;
+    const int V = vec_width(dtype), Co = act_width(C, act);
+    if (!slice_ok(dcs, dco, Co, V)) return SBA_E_ARG;
     const int blocks = grid_for(rows * (Co / V));
     const size_t sh = 6 * (size_t)C * sizeof(float);
-    if (sba_det_on() && groups > 1 && dgamma) {
-        // the groups add into the same dgamma / dbeta: one launch per group, in group order
-        const int64_t esz = dtype != SBA_F32 ? 2 : 4;
-        for (int g = 0; g < groups; ++g) {
-            const char* yg = (const char*)y + (int64_t)g * rows * C * esz;
-            const char* dg = (const char*)dout + (int64_t)g * rows * dcs * esz;
-            char* dyg = (char*)dy + (int64_t)g * rows * C * esz;
-            const float* auxg = aux + (int64_t)g * 4 * C;
-            const float* redg = red + (int64_t)g * SBA_BN_STAT_SLOTS * 2 * C;
-            SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_apply_kernel<T, YT, ACT>), dim3(blocks, 1), dim3(256), sh,
-                                                           (hipStream_t)stream, (const YT*)yg, (const T*)dg, auxg, redg,
-                                                           (T*)dyg, dgamma, dbeta, rows, C, dcs, dco)));
-        }
-        return SBA_CHECK_LAUNCH();
-    }
-    SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_apply_kernel<T, YT, ACT>), dim3(blocks, groups),
-                                                           dim3(256), sh, (hipStream_t)stream, (const YT*)y,
-                                                           (const T*)dout, aux, red, (T*)dy, dgamma, dbeta, rows, C,
-                                                           dcs, dco)));
-    return SBA_CHECK_LAUNCH();
+    const int64_t esz = elem_size(dtype);
+    return param_grad_pass(groups, dgamma != nullptr, [&](int g, int ng) -> int {
+        const char* yg = (const char*)y + (int64_t)g * rows * C * esz;
+        const char* dg = (const char*)dout + (int64_t)g * rows * dcs * esz;
+        char* dyg = (char*)dy + (int64_t)g * rows * C * esz;
+        const float* auxg = aux + (int64_t)g * 4 * C;
+        const float* redg = red + (int64_t)g * SBA_BN_STAT_SLOTS * 2 * C;
+        SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_apply_kernel<T, YT, ACT>), dim3(blocks, ng), dim3(256), sh,
+                                                               (hipStream_t)stream, (const YT*)yg, (const T*)dg, auxg, redg,
+                                                               (T*)dyg, dgamma, dbeta, rows, C, dcs, dco)));
+        return SBA_OK;
+    });
 }
 
 extern "C" int sba_bn_act_fwd_fused(int dtype, const void* y, const float* gamma, const float* beta,
@@ -1061,9 +1064,8 @@ extern "C" int sba_bn_act_fwd_fused(int dtype, const void* y, const float* gamma
                                     int out_cstride, int out_coff, float eps, float momentum, void* stream) {
     if (!y || !gamma || !beta || !aux || !out || !bn_shape_ok(dtype, rows, groups, C, act)) return SBA_E_ARG;
     if ((running_mean == nullptr) != (running_var == nullptr)) return SBA_E_ARG;
-    const int Co = act == SBA_ACT_GLU ? C / 2 : C;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (out_cstride < Co + out_coff || out_cstride % V || out_coff % V) return SBA_E_ARG;
+    const int V = vec_width(dtype), Co = act_width(C, act);
+    if (!slice_ok(out_cstride, out_coff, Co, V)) return SBA_E_ARG;
     SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_fwd_fused_kernel<T, YT, ACT>), dim3(Co / V), dim3(256), 0,
                                                            (hipStream_t)stream, (const YT*)y, gamma, beta,
                                                            running_mean, running_var, num_batches_tracked, aux,
@@ -1077,27 +1079,19 @@ extern "C" int sba_bn_act_bwd_fused(int dtype, const void* y, const void* dout, 
                                     int dco, void* stream) {
     if (!y || !dout || !aux || !dy || !bn_shape_ok(dtype, rows, groups, C, act)) return SBA_E_ARG;
     if ((dgamma == nullptr) != (dbeta == nullptr)) return SBA_E_ARG;
-    const int Co = act == SBA_ACT_GLU ? C / 2 : C;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (dcs < Co + dco || dcs % V || dco % V) return SBA_E_ARG;
-    if (sba_det_on() && groups > 1 && dgamma) {
-        const int64_t esz = dtype != SBA_F32 ? 2 : 4;
-        for (int g = 0; g < groups; ++g) {
-            const char* yg = (const char*)y + (int64_t)g * rows * C * esz;
-            const char* dg = (const char*)dout + (int64_t)g * rows * dcs * esz;
-            char* dyg = (char*)dy + (int64_t)g * rows * C * esz;
-            const float* auxg = aux + (int64_t)g * 4 * C;
-            SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_fused_kernel<T, YT, ACT>), dim3(Co / V, 1), dim3(256), 0,
-                                                           (hipStream_t)stream, (const YT*)yg, (const T*)dg, auxg,
-                                                           (T*)dyg, dgamma, dbeta, rows, C, dcs, dco)));
-        }
-        return SBA_CHECK_LAUNCH();
-    }
-    SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_fused_kernel<T, YT, ACT>), dim3(Co / V, groups),
-                                                           dim3(256), 0, (hipStream_t)stream, (const YT*)y,
-                                                           (const T*)dout, aux, (T*)dy, dgamma, dbeta, rows, C, dcs,
-                                                           dco)));
-    return SBA_CHECK_LAUNCH();
+    const int V = vec_width(dtype), Co = act_width(C, act);
+    if (!slice_ok(dcs, dco, Co, V)) return SBA_E_ARG;
+    const int64_t esz = elem_size(dtype);
+    return param_grad_pass(groups, dgamma != nullptr, [&](int g, int ng) -> int {
+        const char* yg = (const char*)y + (int64_t)g * rows * C * esz;
+        const char* dg = (const char*)dout + (int64_t)g * rows * dcs * esz;
+        char* dyg = (char*)dy + (int64_t)g * rows * C * esz;
+        const float* auxg = aux + (int64_t)g * 4 * C;
+        SBA_DISPATCH_Y(dtype, ACT_SWITCH(act, SBA_LAUNCH((bn_bwd_fused_kernel<T, YT, ACT>), dim3(Co / V, ng), dim3(256), 0,
+                                                               (hipStream_t)stream, (const YT*)yg, (const T*)dg, auxg,
+                                                               (T*)dyg, dgamma, dbeta, rows, C, dcs, dco)));
+        return SBA_OK;
+    });
 }
 
 extern "C" int sba_bn1d_glu_fwd(int dtype, const float* y, const float* gamma, const float* beta,
@@ -1126,7 +1120,7 @@ extern "C" int sba_bn1d_glu_bwd(int dtype, const float* y, const void* dout, con
 static bool in_shape_ok(int dtype, int N, int HW, int C) {
     // (the dtype is refused HERE, before sba_instnorm_stats clears its outputs: a refused call writes nothing)
     if (dtype != SBA_F32 && dtype != SBA_BF16) return false;
-    const int V = dtype != SBA_F32 ? 8 : 4;
+    const int V = vec_width(dtype);
     return N > 0 && HW > 0 && C > 0 && C % V == 0 && C / V <= 256 && pow2(C / V);
 }
 
@@ -1134,32 +1128,30 @@ extern "C" int sba_instnorm_stats(int dtype, const void* h, float* mean, float* 
                                   float eps, void* stream) {
     if (!h || !mean || !rstd || !in_shape_ok(dtype, N, HW, C)) return SBA_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    static int fused = -1;      // SBA_INSTNORM_FUSED=0: clear + accumulate (atomics) + finalize (A/B aid)
-    if (fused < 0) { const char* e = getenv("SBA_INSTNORM_FUSED"); fused = (e && e[0] == '0') ? 0 : 1; }
-    if (fused && N * (C / V) >= 64 && HW >= 1024) {        // enough workgroups of enough pixels: one launch
+    const int V = vec_width(dtype);
+    if (N * (C / V) >= 64 && HW >= 1024) {                  // enough workgroups of enough pixels: one launch
         SBA_DISPATCH(dtype, SBA_LAUNCH((instnorm_stats_fused_kernel<T>), dim3(N, C / V), dim3(256), 0, st, (const T*)h, mean,
                                                rstd, HW, C, eps));
         return SBA_CHECK_LAUNCH();
     }
+    // small shapes: clear + accumulate + finalize
     sba_zero_f32(mean, rstd, (int64_t)N * C, st);
     const int rpi = 256 / (C / V);
-    int splits = cdiv(HW, rpi * 16);
-    if (splits > 256) splits = 256;
-    const int det = sba_det_on() ? 1 : 0;
-    if (det) splits = 1;            // one workgroup per image, row-groups added in order
-    SBA_DISPATCH(dtype, SBA_LAUNCH((instnorm_accum_kernel<T>), dim3(N, splits), dim3(256),
-                                           (det ? rpi : 1) * 2 * C * sizeof(float), st, (const T*)h, mean, rstd, HW, C, det));
+    const bool det = sba_det_on();
+    SBA_DISPATCH(dtype, SBA_LAUNCH((instnorm_accum_kernel<T>), dim3(N, instnorm_splits(HW, rpi, det)), dim3(256),
+                                           (det ? rpi : 1) * 2 * C * sizeof(float), st, (const T*)h, mean, rstd, HW, C,
+                                           (int)det));
     SBA_LAUNCH(instnorm_finalize_kernel, dim3(cdiv(N * C, 256)), dim3(256), 0, st, mean, rstd, N * C,
                        (float)HW, eps);
     return SBA_CHECK_LAUNCH();
 }
 
+
 extern "C" int sba_adain_fwd(int dtype, const void* h, const float* mean, const float* rstd, const float* style,
                              void* out, int N, int HW, int C, int ocs, int oco, void* stream) {
     if (!h || !mean || !rstd || !style || !out || !in_shape_ok(dtype, N, HW, C)) return SBA_E_ARG;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (ocs < C + oco || ocs % V || oco % V) return SBA_E_ARG;
+    const int V = vec_width(dtype);
+    if (!slice_ok(ocs, oco, C, V)) return SBA_E_ARG;
     const int blocks = grid_for((int64_t)N * HW * (C / V));
     SBA_DISPATCH(dtype, SBA_LAUNCH((adain_fwd_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)h, mean, rstd, style, (T*)out, N, HW, C, ocs, oco));
@@ -1170,16 +1162,13 @@ extern "C" int sba_adain_bwd_reduce(int dtype, const void* h, const void* dout, 
                                     const float* rstd, float* red, int N, int HW, int C, int dcs, int dco,
                                     void* stream) {
     if (!h || !dout || !mean || !rstd || !red || !in_shape_ok(dtype, N, HW, C)) return SBA_E_ARG;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (dcs < C + dco || dcs % V || dco % V) return SBA_E_ARG;
+    const int V = vec_width(dtype);
+    if (!slice_ok(dcs, dco, C, V)) return SBA_E_ARG;
     const int rpi = 256 / (C / V);
-    int splits = cdiv(HW, rpi * 16);
-    if (splits > 256) splits = 256;
-    const int det = sba_det_on() ? 1 : 0;
-    if (det) splits = 1;
-    SBA_DISPATCH(dtype, SBA_LAUNCH((adain_bwd_reduce_kernel<T>), dim3(N, splits), dim3(256),
+    const bool det = sba_det_on();
+    SBA_DISPATCH(dtype, SBA_LAUNCH((adain_bwd_reduce_kernel<T>), dim3(N, instnorm_splits(HW, rpi, det)), dim3(256),
                                            (det ? rpi : 1) * 2 * C * sizeof(float), (hipStream_t)stream, (const T*)h,
-                                           (const T*)dout, mean, rstd, red, HW, C, dcs, dco, det));
+                                           (const T*)dout, mean, rstd, red, HW, C, dcs, dco, (int)det));
     return SBA_CHECK_LAUNCH();
 }
 
@@ -1188,8 +1177,8 @@ extern "C" int sba_adain_bwd_apply(int dtype, const void* h, const void* dout, c
                                    float* dstyle, int N, int HW, int C, int dcs, int dco, int accumulate,
                                    void* stream) {
     if (!h || !dout || !mean || !rstd || !style || !red || !dh || !in_shape_ok(dtype, N, HW, C)) return SBA_E_ARG;
-    const int V = dtype != SBA_F32 ? 8 : 4;
-    if (dcs < C + dco || dcs % V || dco % V) return SBA_E_ARG;
+    const int V = vec_width(dtype);
+    if (!slice_ok(dcs, dco, C, V)) return SBA_E_ARG;
     const int blocks = grid_for((int64_t)N * HW * (C / V));
     SBA_DISPATCH(dtype, SBA_LAUNCH((adain_bwd_apply_kernel<T>), dim3(blocks), dim3(256), 0,
                                            (hipStream_t)stream, (const T*)h, (const T*)dout, mean, rstd, style,

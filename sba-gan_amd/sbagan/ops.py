@@ -786,7 +786,7 @@ def bn_act_forward(y, stats, bn, act, residual=None, groups=1):
     return out, st
 
 
-BN_FUSED_BWD_ROWS = int(os.environ.get('SBA_BN_FUSED_ROWS', '2560'))       # rows per group up to which the one-launch backward is used
+BN_FUSED_BWD_ROWS = 2560        # rows per group up to which the one-launch forward (grouped maps) and backward are used
 
 
 def bn_act_backward(y, dout, st, bn, act, need_param_grad=True, out=None, red=None):
@@ -831,6 +831,16 @@ def bn_stats(y, groups=1):
     return stats
 
 
+def bn_act_forward_grouped(y, bn, act, groups):
+    """BatchNorm + activation of a conv output that came without statistics (`groups` BatchNorm batches back to back):
+    a small map in training mode takes the one-launch kernel, everything else a statistics pass + bn_act_forward."""
+    N, C, H, W = y.shape
+    if bn.training and (N // groups) * H * W <= BN_FUSED_BWD_ROWS:
+        return bn_act_forward_fused(y, bn, act, groups)
+    stats = bn_stats(y, groups) if bn.training else None
+    return bn_act_forward(y, stats, bn, act, None, groups)
+
+
 # ----------------------------------------------------------------------------
 # autograd Functions
 # ----------------------------------------------------------------------------
@@ -855,18 +865,11 @@ class ConvBNActFn(torch.autograd.Function):
         x = as_act(x)
         if groups == 1:
             y, stats = conv_forward(x, layer.pw, kind, want_stats=layer.bn.training, pre_bn=True)
+            out, sts = bn_act_forward(y, stats, layer.bn, act, residual)
         else:
             assert residual is None and x.shape[0] % groups == 0
             y, _ = conv_forward(x, layer.pw, kind, want_stats=False, pre_bn=True)
-            rows_g = (y.shape[0] // groups) * y.shape[2] * y.shape[3]
-            if layer.bn.training and rows_g <= BN_FUSED_BWD_ROWS:
-                out, sts = bn_act_forward_fused(y, layer.bn, act, groups)
-                ctx.layer, ctx.kind, ctx.act, ctx.sts, ctx.groups = layer, kind, act, sts, groups
-                ctx.has_res = False
-                ctx.save_for_backward(x, y)
-                return out
-            stats = bn_stats(y, groups) if layer.bn.training else None
-        out, sts = bn_act_forward(y, stats, layer.bn, act, residual, groups)
+            out, sts = bn_act_forward_grouped(y, layer.bn, act, groups)
         ctx.layer, ctx.kind, ctx.act, ctx.sts, ctx.groups = layer, kind, act, sts, groups
         ctx.has_res = residual is not None
         ctx.save_for_backward(x, y)
@@ -1474,10 +1477,7 @@ class DHeadsFn(torch.autograd.Function):
                 layer = cnet.jointConv._layer()
                 off = slices[hi][0]
                 xin, y = xin_all[off:off + rows], y_all[off:off + rows]
-                if rows * 16 <= BN_FUSED_BWD_ROWS:
-                    hc, st = bn_act_forward_fused(y, layer.bn, ACT_LRELU, 1)
-                else:
-                    hc, st = bn_act_forward(y, bn_stats(y, 1), layer.bn, ACT_LRELU)
+                hc, st = bn_act_forward_grouped(y, layer.bn, ACT_LRELU, 1)      # (grouped: the BatchNorm is in training mode)
                 o = cnet.outlogits[0]
                 call('sba_logits_fwd', dt, _p(hc), _p(o.weight), _p(o.bias), _p(pslice), rows, K, _stream())
                 tape.append((xin, y, st, hc))

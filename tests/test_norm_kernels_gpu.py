@@ -35,8 +35,8 @@ adain_bwd_reduce_kernel        sba_adain_bwd_reduce                             
 adain_bwd_apply_kernel         sba_adain_bwd_apply: accumulate 0 / 1, dstyle or NULL   test_adain
 every SBA_E_ARG condition      --                                                      test_refusals
 
-The switches SBA_BN_FUSED_ROWS, SBA_BN_RED_BLOCKS and SBA_INSTNORM_FUSED are read once per process and are left alone:
-the entry point called -- for InstanceNorm the shape -- selects the kernel.
+No environment switch selects a kernel (ops.BN_FUSED_BWD_ROWS, the workgroup caps and the InstanceNorm threshold are
+constants): the entry point called -- for InstanceNorm the shape -- does.
 
 Bounds.  f32 outputs: elementwise rtol 2e-4 / atol 2e-5 (test_kernels_gpu.tol).  Per-channel sums (statistics, red,
 dgamma, dbeta, dstyle): |error| <= 1e-5 x the float64 sum of the ABSOLUTE summands of that channel (f32 partial sums

@@ -27,7 +27,7 @@ def main():
     dev = torch.device('cuda:0')
     ops.set_compute_dtype(torch.bfloat16)
     acts = {'glu': ACT_GLU, 'lrelu': ACT_LRELU, 'none': ACT_NONE}
-    print('SBA_BN_RED_BLOCKS=%s' % os.environ.get('SBA_BN_RED_BLOCKS', '(default)'))
+    print('library: %s' % os.environ.get('SBA_LIB_PATH', '(in-tree build)'))
 
     def timeit(fn, n=20):
         for _ in range(3):
