@@ -611,10 +611,9 @@ extern "C" int sba_resize_bilinear(const float* in, float* out, int NC, int S, i
     if (!backward) {
         SBA_LAUNCH(resize_fwd_kernel, dim3(grid_for((int64_t)NC * D * D)), dim3(256), 0, st, in, out, NC, S, D);
     } else {     // in = d(out) [NC][D][D], out = d(in) [NC][S][S]
-        static int tab = -1;        // SBA_RESIZE_BWD_TAB=0: the kernel that re-derives the candidates per pixel (A/B aid)
-        if (tab < 0) { const char* e = getenv("SBA_RESIZE_BWD_TAB"); tab = (e && e[0] == '0') ? 0 : 1; }
+        // tabulated candidates; out of its range, the kernel that re-derives the candidates per pixel
         // (an input index collects the outputs o with o (S-1)/(D-1) within (r-1, r+1): at most 2 (D-1)/(S-1) + 1 <= RESIZE_MAXC)
-        if (tab && D >= S && S >= 2 && S <= 2048 && 2 * (int64_t)(D - 1) <= 3 * (int64_t)(S - 1))
+        if (D >= S && S >= 2 && S <= 2048 && 2 * (int64_t)(D - 1) <= 3 * (int64_t)(S - 1))
             SBA_LAUNCH(resize_bwd_tab_kernel, dim3(grid_for((int64_t)NC * S * S, 2048)), dim3(256), (size_t)S * RESIZE_MAXC * 8,
                        st, in, out, NC, S, D);
         else
@@ -637,9 +636,7 @@ extern "C" int sba_enc_stem_bwd(int dtype, const float* w, const void* out, cons
                                 int S, int C, void* stream) {
     if (!w || !out || !dout || !dimg || N <= 0 || S < 3 || C <= 0 || C % 8 || C > 256) return SBA_E_ARG;
     const int O = (S - 3) / 2 + 1;
-    static int mf = -1;         // SBA_ENC_STEM_BWD_MFMA=0: the VALU kernel also for bf16 (A/B aid)
-    if (mf < 0) { const char* e = getenv("SBA_ENC_STEM_BWD_MFMA"); mf = (e && e[0] == '0') ? 0 : 1; }
-    if (mf && dtype == SBA_BF16 && C == 32 && (((uintptr_t)out | (uintptr_t)dout) & 15) == 0) {
+    if (dtype == SBA_BF16 && C == 32 && (((uintptr_t)out | (uintptr_t)dout) & 15) == 0) {
         const int BH = (S + 1) / 2, ntiles = N * BH * ((BH + 15) / 16);
         SBA_LAUNCH(enc_stem_bwd_mfma_kernel, dim3((ntiles + 3) / 4 < 8192 ? (ntiles + 3) / 4 : 8192), dim3(256), 0,
                    (hipStream_t)stream, w, (const bf16_t*)out, (const bf16_t*)dout, dimg, N, S, O, ntiles);

@@ -251,10 +251,10 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
     if damsm is not None:
         w_loss, s_loss = damsm[0], damsm[1]
     else:
-        # ranking loss on the last scale (losses.py:187-204).  An encoder that forks its own streams
-        # (sbagan.inception_hip) stays on the calling stream: it already overlaps the D branches, and
-        # nested forks inside a captured branch crash hipStreamEndCapture on ROCm 7.2.
-        own = streams and not getattr(image_encoder, 'parallel', False)
+        # ranking loss on the last scale (losses.py:187-204).  An encoder that schedules its own branches
+        # (sbagan.inception_hip: it has a `mode`) stays on the calling stream: it already overlaps the D branches, and
+        # nested forks (mode 'streams') inside a captured branch crash hipStreamEndCapture on ROCm 7.2.
+        own = streams and not hasattr(image_encoder, 'mode')
         with (branch(numDs) if own else contextlib.nullcontext()):
             region_features, cnn_code = image_encoder(fake_imgs[numDs - 1])
             w_loss0, w_loss1, _ = words_loss(region_features, words_embs, match_labels, cap_lens, class_ids,

@@ -12,7 +12,7 @@ reference's checkpoints) and is a drop-in callable: (B x 3 x S x S f32) ->
 (B x nef x 17 x 17 f32, B x nef f32).
 """
 import ctypes
-import os
+import functools
 
 import torch
 
@@ -20,11 +20,7 @@ from . import _lib, ops
 from ._lib import ConvGeom, ConvGroupItem, call
 
 BN_EPS = 1e-3
-SAVE_ARGMAX = os.environ.get('SBA_ENC_SAVE_ARGMAX', '1') != '0'    # max-pool forward keeps the window argmax for the backward
-GROUP_MIN_TILES = int(os.environ.get('SBA_ENC_GROUP_MIN_TILES', '512'))
-GROUP_TILE = int(os.environ.get('SBA_ENC_GROUP_TILE', '0'))             # tuning aid: force the grouped launches' tile id
-FRAG_STEM = os.environ.get('SBA_ENC_FRAG_STEM', '1') != '0'         # register-weight halo kernel for the trunk's first 3 x 3 layers
-GROUP_T7_MIN = int(os.environ.get('SBA_ENC_GROUP_T7_MIN', '0'))         # 128 x 128 tiles (tile id 7) when a level has at least this many (0 = never)
+GROUP_MIN_TILES = 512       # a grouped level takes the biggest tile that still gives it this many workgroups (two per CU)
 
 
 def _pad32(c):
@@ -45,28 +41,40 @@ class _Act(object):
         return self.t.shape
 
 
+def _fold(weight, bn=None, bias=None):
+    """f32 (w, b) of a conv followed by `bn` (BatchNorm in eval mode: folded into the weights and a bias), or of a plain
+    conv with `bias` (None: zeros)"""
+    w = weight.detach().float()
+    if bn is None:
+        return w, bias.detach().float() if bias is not None else torch.zeros(w.shape[0], device=w.device)
+    s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+    return w * s.view(-1, 1, 1, 1), bn.bias.detach().float() - bn.running_mean.detach().float() * s
+
+
+def _pack(w, Op, Ip):
+    """[O, I, KH, KW] -> f32 [Op][KH * KW][Ip], zero-padded"""
+    O, I, KH, KW = w.shape
+    wp = torch.zeros((Op, KH * KW, Ip), dtype=torch.float32, device=w.device)
+    wp[:O, :, :I] = w.permute(0, 2, 3, 1).reshape(O, KH * KW, I)
+    return wp
+
+
 class _Conv(object):
-    """One BasicConv2d (conv, BN eval, ReLU) or a plain conv: folded + packed operands."""
+    """One BasicConv2d (conv, BN eval, ReLU), a plain conv, or a Linear layer (a 1 x 1 conv): folded + packed operands."""
 
     def __init__(self, conv, bn, dtype, relu=True):
-        w = conv.weight.detach().float()
+        lin = isinstance(conv, torch.nn.Linear)
+        w, b = _fold(conv.weight[:, :, None, None] if lin else conv.weight, bn, conv.bias)
         O, I, KH, KW = w.shape
         dev = w.device
-        if bn is not None:
-            s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-            b = bn.bias.detach().float() - bn.running_mean.detach().float() * s
-            w = w * s.view(-1, 1, 1, 1)
-        else:
-            b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(O, device=dev)
         self.O, self.I, self.KH, self.KW = O, I, KH, KW
         self.Op, self.Ip = _pad32(O), _pad32(I)
         self.bn, self.conv_mod, self._w_raw = bn, conv, None
-        self.stride = conv.stride[0]
-        self.ph, self.pw = conv.padding
+        self.stride = 1 if lin else conv.stride[0]
+        self.ph, self.pw = (0, 0) if lin else conv.padding
         self.relu = relu
         taps = KH * KW
-        wp = torch.zeros((self.Op, taps, self.Ip), dtype=torch.float32, device=dev)
-        wp[:O, :, :I] = w.permute(0, 2, 3, 1).reshape(O, taps, I)
+        wp = _pack(w, self.Op, self.Ip)
         self.bias = torch.zeros(self.Op, dtype=torch.float32, device=dev)
         self.bias[:O] = b
         self.w_fwd = wp.to(dtype).contiguous()
@@ -88,11 +96,7 @@ def _raw_weights(L, dtype):
     """UNFOLDED packed weights [O][taps][Ip] of a BasicConv2d (training-mode BatchNorm: the conv output is normalised
     with batch statistics, so the running statistics cannot be folded in)"""
     if L._w_raw is None or L._w_raw.dtype != dtype:
-        w = L.conv_mod.weight.detach().float()
-        O, I, KH, KW = w.shape
-        wp = torch.zeros((O, KH * KW, L.Ip), dtype=torch.float32, device=w.device)
-        wp[:, :, :I] = w.permute(0, 2, 3, 1).reshape(O, KH * KW, I)
-        L._w_raw = wp.to(dtype).contiguous()
+        L._w_raw = _pack(L.conv_mod.weight.detach().float(), L.O, L.Ip).to(dtype).contiguous()
     return L._w_raw
 
 
@@ -107,7 +111,7 @@ class _FusedHeads(object):
         self.I, self.Ip = parts[0].I, parts[0].Ip
         self.O = self.Op = sum(c.Op for c in parts)
         self.KH = self.KW = 1
-        self.stride, self.ph, self.pw, self.relu = 1, 0, 0, True
+        self.stride, self.ph, self.pw, self.relu, self.bn = 1, 0, 0, True, None
         self.bias = torch.cat([c.bias for c in parts]).contiguous()
         self.w_fwd = torch.cat([c.w_fwd for c in parts], 0).contiguous()               # [sum Op][1][Ip]
         self.w_dgrad = [torch.cat([c.w_dgrad[0] for c in parts], 2).contiguous()]      # [Ip][1][sum Op]
@@ -130,58 +134,60 @@ def _geom(N, IH, IW, Cin, OH, OW, Cout, taps, sy=1, OHs=None, OWs=None, osy=1, o
     return g
 
 
+def _group_tile(shapes):
+    """tile id of one grouped launch from the (M, Cout) of its items: 128- (tile 5), 96- (tile 3) or 64-row (tile 1) tiles,
+    64 channels wide.  Bigger tiles move fewer bytes L2 -> LDS per FLOP; use them when they still fill two workgroups per CU"""
+    def tiles(bm):
+        return sum(((M + bm - 1) // bm) * ((C + 63) // 64) for M, C in shapes)
+    return 5 if tiles(128) >= GROUP_MIN_TILES else (3 if tiles(96) >= GROUP_MIN_TILES else 1)
+
+
+class _Block(object):
+    """One Inception block as data: its input, the ops of the fused head convs (`pre`, main stream) and of every branch
+    [(side stream k, ops)]; `bodies` holds the functions that build the branches [(k, body)] until _end_block has run them"""
+
+    def __init__(self, x):
+        self.x, self.pre, self.branches, self.bodies = x, [], [], []
+
+
 class InceptionHIP(object):
     def __init__(self, enc, dtype=None):
         self.enc = enc
         self.dtype = dtype or ops.compute_dtype()
         self.nef = enc.nef
-        self._convs = {}
-        self._frag, self._frag_keep = {}, []
-        self._fused = {}
-        self._geoms = {}
-        self._side, self._branch_ops, self._block = None, None, None
-        self.parallel = os.environ.get('SBA_ENC_PARALLEL', '1') == '1'      # Inception branches on side streams
-        # GROUPED launches (bf16): the branches of a block are issued level by level on ONE stream, and the implicit-GEMM
-        # convs of one level -- independent of each other -- go out as one sba_conv_igemm_group grid instead of one
-        # 120..273-workgroup launch each (hipGraph replay runs the side streams back to back anyway, ROCm 7.2)
-        self.group = os.environ.get('SBA_ENC_GROUP', '1') == '1' and self.dtype == torch.bfloat16
-        self._thunks = None          # forward: launch closures of the branch being recorded
+        self.device = next(enc.parameters()).device
+        # How the independent branches of a block are issued (forward and backward), see _issue:
+        # 'group' (bf16): level by level on ONE stream, the implicit-GEMM convs of one level -- independent of each other --
+        # as one sba_conv_igemm_group grid instead of one 120..273-workgroup launch each (hipGraph replay runs side streams
+        # back to back anyway, ROCm 7.2); 'streams': branch k on side stream k; 'serial': one after the other
+        self.mode = 'group' if self.dtype == torch.bfloat16 else 'streams'
+        self.keep_debug = False      # backward keeps the tape, the gradients and d299 (tools/debug_encoder.py)
+        self.d299 = None
         self.last_pooled = None      # the f32 pooled Mixed_7c output [N, 2048] of the last forward
-        self._train = False          # trunk_features(train=True): BatchNorm with batch statistics (DAMSM pre-training)
-        self._keep = []
-        self._pending = None         # implicit-GEMM launches collected for the current level
-        dev = next(enc.parameters()).device
-        self.device = dev
+        self._side = None            # the four side streams of 'streams', made at their first use
+        self._stale = False          # the BatchNorm buffers moved since the operands were folded
+        self._train = False          # this forward: BatchNorm with batch statistics (trunk_features(train=True))
+        self._want_grad = False      # this forward: a backward will follow, the max-pools keep their window argmax
+        self._launches = None        # launch closures of the branch being built (None: launch at once)
+        self._block = None           # the _Block being built
+        self._pending = None         # 'group': implicit-GEMM launches collected for the current level
+        self._reset()
+        self.refold()
+
+    def refold(self):
+        """(re)build the folded (eval-mode), packed operands from the module's current weights and BatchNorm buffers"""
+        enc = self.enc
+        self._convs, self._fused = {}, {}
+        self._frag, self._frag_keep = {}, []        # (keyed by the operands' addresses)
         for name, m in enc.named_modules():
             if m.__class__.__name__ == 'BasicConv2d':
                 self._convs[name] = _Conv(m.conv, m.bn, self.dtype)
         self._convs['emb_features'] = _Conv(enc.emb_features, None, self.dtype, relu=False)
-        lin = enc.emb_cnn_code
-
-        class _L(object):
-            pass
-        fake = _L()
-        fake.weight = lin.weight.detach().view(lin.out_features, lin.in_features, 1, 1)
-        fake.bias, fake.stride, fake.padding = lin.bias, (1, 1), (0, 0)
-        self._convs['emb_cnn_code'] = _Conv(fake, None, self.dtype, relu=False)
+        self._convs['emb_cnn_code'] = _Conv(enc.emb_cnn_code, None, self.dtype, relu=False)
         stem = enc.Conv2d_1a_3x3
-        s = stem.bn.weight.detach().float() / torch.sqrt(stem.bn.running_var.detach().float() + stem.bn.eps)
-        self.stem_w = (stem.conv.weight.detach().float() * s.view(-1, 1, 1, 1)).contiguous(
-            memory_format=torch.channels_last)
-        self.stem_b = (stem.bn.bias.detach().float() - stem.bn.running_mean.detach().float() * s).contiguous()
-
-    def refold(self):
-        """rebuild the folded (eval-mode) operands from the module's current BatchNorm buffers"""
-        for name, m in self.enc.named_modules():
-            if m.__class__.__name__ == 'BasicConv2d':
-                self._convs[name] = _Conv(m.conv, m.bn, self.dtype)
-        self._fused = {}
-        self._frag, self._frag_keep = {}, []        # (keyed by the old operands' addresses)
-        stem = self.enc.Conv2d_1a_3x3
-        s = stem.bn.weight.detach().float() / torch.sqrt(stem.bn.running_var.detach().float() + stem.bn.eps)
-        self.stem_w = (stem.conv.weight.detach().float() * s.view(-1, 1, 1, 1)).contiguous(
-            memory_format=torch.channels_last)
-        self.stem_b = (stem.bn.bias.detach().float() - stem.bn.running_mean.detach().float() * s).contiguous()
+        w, b = _fold(stem.conv.weight, stem.bn)
+        self.stem_w, self.stem_b = w.contiguous(memory_format=torch.channels_last), b.contiguous()
+        self._stale = False
 
     # ------------------------------------------------------------------ primitive ops
     def _dt(self):
@@ -221,7 +227,7 @@ class InceptionHIP(object):
         """the fragment-major copy of the packed weights `w` ([R][9][K], frozen) when this launch goes to the register-weight
         halo-tile kernel (include/sbagan_hip.h: sba_conv_geom.w_layout): stride-1 3 x 3 convs on the big maps of the trunk's
         first layers (>= 64 pixels wide) and their data gradients; None otherwise"""
-        if not FRAG_STEM or self.dtype != torch.bfloat16 or g.ntaps != 9 or g.sy != 1 or \
+        if self.dtype != torch.bfloat16 or g.ntaps != 9 or g.sy != 1 or \
                 g.osy != 1 or g.OW < 64 or g.OWs != g.OW or w.dim() != 3 or w.shape[0] % 32 or w.shape[2] % 32:
             return None
         key = (w.data_ptr(), g.OH, g.OW, g.IH, g.IW, g.N)
@@ -246,7 +252,9 @@ class InceptionHIP(object):
             self._frag[key] = ent
         return ent if ent is not False else None
 
-    def _igemm(self, x_ptr, w, y_ptr, addend_ptr, bias, g, mask_ptr=None):
+    def _igemm(self, x_ptr, w, y_ptr, addend_ptr, bias, g, mask_ptr=None, keep=None):
+        """one implicit-GEMM launch, now or -- while a level is being collected -- as an item of its grouped launch;
+        keep: a temporary the launch reads, held until it has been issued"""
         wf = self._frag_for(w, g)
         if wf is not None:          # register-weight halo kernel: a launch of its own (never part of a grouped level)
             g.w_layout = 1
@@ -257,7 +265,7 @@ class InceptionHIP(object):
                 g.w_layout = 0
             return
         if self._pending is not None:
-            self._pending.append((x_ptr, w, y_ptr, addend_ptr, bias, g, mask_ptr))
+            self._pending.append((x_ptr, w, y_ptr, addend_ptr, bias, g, mask_ptr, keep))
             return
         ws = ops.workspace(self.device)
         ops.tune_geom(g, self._dt())
@@ -266,48 +274,62 @@ class InceptionHIP(object):
              ops.WORKSPACE_BYTES, ops._stream())
 
     def _launch(self, fn):
-        """run a launch closure now, or keep it for the level-by-level issue of the block being recorded"""
-        if self._thunks is not None:
-            self._thunks.append(fn)
+        """run a launch closure now, or keep it for _end_block when a branch of a block is being built"""
+        if self._launches is not None:
+            self._launches.append(fn)
         else:
             fn()
 
     def _flush(self):
         """issue the implicit-GEMM launches collected for one level as one grid (several when there are more than
-        SBA_GROUP_MAX)"""
+        SBA_GROUP_MAX); a single one as an ordinary launch"""
         items, self._pending = self._pending, None
-        grp = items if len(items) >= 2 else []
-        taken = set(id(it) for it in grp)
-        for it in items:
-            if id(it) not in taken:
-                self._igemm(*it)
-        for i0 in range(0, len(grp), _lib.GROUP_MAX):
-            part = grp[i0:i0 + _lib.GROUP_MAX]
+        for i0 in range(0, len(items), _lib.GROUP_MAX):
+            part = items[i0:i0 + _lib.GROUP_MAX]
             if len(part) == 1:
                 self._igemm(*part[0])
                 continue
             arr = (ConvGroupItem * len(part))()
-            m128 = m96 = m7 = 0
-            for a, (x_ptr, w, y_ptr, addend_ptr, bias, g, mask_ptr) in zip(arr, part):
+            for a, (x_ptr, w, y_ptr, addend_ptr, bias, g, mask_ptr, _) in zip(arr, part):
                 a.x, a.w, a.y, a.addend = x_ptr, w.data_ptr(), y_ptr, addend_ptr
                 a.bias = None if bias is None else bias.data_ptr()
                 a.relu_mask = mask_ptr
                 a.g = ctypes.pointer(g)
-                M = g.N * g.OHs * g.OWs
-                ny = (g.Cout + 63) // 64
-                m128 += ((M + 127) // 128) * ny
-                m96 += ((M + 95) // 96) * ny
-                m7 += ((M + 127) // 128) * ((g.Cout + 127) // 128)
-            # bigger tiles move fewer bytes L2 -> LDS per FLOP; use them when they still fill two workgroups per CU
-            tile = 5 if m128 >= GROUP_MIN_TILES else (3 if m96 >= GROUP_MIN_TILES else 1)
-            if GROUP_T7_MIN and m7 >= GROUP_T7_MIN:
-                tile = 7
-            if GROUP_TILE:
-                tile = GROUP_TILE
+            tile = _group_tile([(it[5].N * it[5].OHs * it[5].OWs, it[5].Cout) for it in part])
             call('sba_conv_igemm_group', _lib.SBA_BF16, len(part), arr, tile, ops._stream())
             if ops.IGEMM_LOG is not None:       # (bench.py's per-kernel accounting: these ran in the grouped kernel)
                 ops.IGEMM_LOG.append(('group', tile, [it[5] for it in part]))
-        self._keep = []             # temporaries the collected launches read (ReLU-masked gradients)
+
+    def _issue(self, chains):
+        """issue independent chains [(k, make)] -- the branches of one block, forward or backward; make() returns the
+        chain's launch closures in order (and allocates what they write: under the stream that will run them)"""
+        if self.mode == 'group':
+            # level l = the l-th launch of every chain: independent of each other, the convs among them as one grid
+            chains = [make() for _, make in chains]
+            for lvl in range(max([len(c) for c in chains] or [0])):
+                self._pending = []
+                for c in chains:
+                    if lvl < len(c):
+                        c[lvl]()
+                self._flush()
+        elif self.mode == 'streams':
+            # each chain on its own HIP stream: the individual convs (M = 20*35^2 ... 20*8^2 pixels) are far too small to
+            # fill 256 CUs one at a time
+            if self._side is None:
+                self._side = [torch.cuda.Stream(device=self.device) for _ in range(4)]
+            main = torch.cuda.current_stream()
+            for k, make in chains:
+                self._side[k].wait_stream(main)
+                with torch.cuda.stream(self._side[k]):
+                    for fn in make():
+                        fn()
+            for k, _ in chains:
+                main.wait_stream(self._side[k])
+        else:
+            assert self.mode == 'serial', self.mode
+            for _, make in chains:
+                for fn in make():
+                    fn()
 
     def conv(self, name, x, out=None):
         """y = relu(conv(x) + bias) written to `out` (an _Act slice) or a new tensor."""
@@ -328,22 +350,19 @@ class InceptionHIP(object):
         if out is None:
             out = _Act(self._new(N, OH, OW, L.Op))
         assert out.C == L.Op and out.shape[1] == OH and out.shape[2] == OW, (name, out.C, L.Op)
-        if self._train and getattr(L, 'bn', None) is not None:
-            self._conv_train(L, x, out, OH, OW)
+        if self._train and L.bn is not None:
+            self._launch(lambda: self._conv_train(L, x, out, OH, OW))
             return out
         taps = [(t // L.KW - L.ph, t % L.KW - L.pw) for t in range(L.KH * L.KW)]
         g = _geom(N, H, W, L.Ip, OH, OW, L.Op, taps, sy=L.stride, xcs=Ct, xco=x.coff, ycs=out.shape[3],
                   yco=out.coff, relu=1 if L.relu else 0)
         xp, yp = x.t.data_ptr(), out.t.data_ptr()
         self._launch(lambda: self._igemm(xp, L.w_fwd, yp, None, L.bias, g))
-        self._record(('conv', L, x, out))
+        self._ops.append(('conv', L, x, out))
         self._consume(x)
         if L.relu:
             self._relu_slices.add(self._key(out))
         return out
-
-    def _record(self, op):
-        (self._branch_ops if self._branch_ops is not None else self.tape).append(op)
 
     def _consume(self, a):
         """one more reader of tensor a.t: the backward of the LAST reader to run completes d(loss)/d(a.t)
@@ -393,11 +412,9 @@ class InceptionHIP(object):
         dt = self._dt()
         if L.relu and not self._is_masked(out):
             dpre = self._new(N, OH, OW, L.Op)
-            if self._pending is not None:
-                self._keep.append(dpre)     # read by a launch that is issued later (at the end of the level)
             call('sba_relu_bwd', dt, out.t.data_ptr(), gy[0].data_ptr(), dpre.data_ptr(), N * OH * OW, L.Op, Ct_o,
                  out.coff, Ct_o, out.coff, ops._stream())
-            dsrc, dcs, dco = dpre, L.Op, 0
+            dsrc, dcs, dco = dpre, L.Op, 0      # (a grouped level issues its reader later: _igemm keeps it until then)
         else:       # no ReLU, or its mask was already applied by the data-gradient(s) that completed gy
             dsrc, dcs, dco = gy[0], Ct_o, out.coff
         gx = self._grad_of(x)
@@ -411,7 +428,7 @@ class InceptionHIP(object):
         mask = x.t.data_ptr() if final else None
         if L.stride == 1:
             g = _geom(N, OH, OW, L.Op, H, W, L.Ip, L.dtaps[0], xcs=dcs, xco=dco, ycs=Ct_x, yco=x.coff)
-            self._igemm(dsrc.data_ptr(), L.w_dgrad[0], gx[0].data_ptr(), addend, None, g, mask)
+            self._igemm(dsrc.data_ptr(), L.w_dgrad[0], gx[0].data_ptr(), addend, None, g, mask, dsrc)
         else:
             for cls in range(4):
                 py, px = cls // 2, cls % 2
@@ -421,7 +438,7 @@ class InceptionHIP(object):
                     continue
                 g = _geom(N, OH, OW, L.Op, H, W, L.Ip, L.dtaps[cls], OHs=OHs, OWs=OWs, osy=2, ooy=py, oox=px,
                           xcs=dcs, xco=dco, ycs=Ct_x, yco=x.coff)
-                self._igemm(dsrc.data_ptr(), L.w_dgrad[cls], gx[0].data_ptr(), addend, None, g, mask)
+                self._igemm(dsrc.data_ptr(), L.w_dgrad[cls], gx[0].data_ptr(), addend, None, g, mask, dsrc)
         self._filled.add(kx)
         if final:
             self._masked.add(kx)
@@ -433,32 +450,29 @@ class InceptionHIP(object):
             out = _Act(self._new(N, OH, OW, x.C))
         arg = None
         xp, yp, dt, C, ocs, oco, xco = x.t.data_ptr(), out.t.data_ptr(), self._dt(), x.C, out.shape[3], out.coff, x.coff
-        if SAVE_ARGMAX and getattr(self, '_want_grad', False):
+        if self._want_grad:     # one byte per element: the backward loads 4 instead of 36 inputs per gradient vector
             arg = torch.empty((N, OH, OW, x.C), dtype=torch.uint8, device=self.device)
             ap = arg.data_ptr()
             self._launch(lambda: call('sba_maxpool3x3s2_fwd_arg', dt, xp, yp, ap, N, H, W, C, Ct, xco, ocs, oco,
                                       ops._stream()))
         else:
             self._launch(lambda: call('sba_maxpool3x3s2_fwd', dt, xp, yp, N, H, W, C, Ct, xco, ocs, oco, ops._stream()))
-        self._record(('maxpool', arg, x, out))
+        self._ops.append(('maxpool', arg, x, out))
         self._consume(x)
         return out
 
-    def _maxpool_bwd(self, x, out, arg=None):
+    def _maxpool_bwd(self, x, out, arg):
+        assert arg is not None, 'forward(img, want_grad=True) keeps the argmax this backward reads'
         gy, gx = self._grad_of(out), self._grad_of(x)
         N, H, W, Ct = x.shape
         kx = self._key(x)
         self._readers[kx] -= 1
         # the last reader of a ReLU output to run its backward applies the ReLU's mask (as the data-gradient convs do in
         # their epilogue): the stem's two pools, whose producers then skip the separate relu_bwd pass
-        final = arg is not None and self._readers[kx] == 0 and kx in self._relu_slices
-        if arg is not None:
-            call('sba_maxpool3x3s2_bwd_arg', self._dt(), arg.data_ptr(), gy[0].data_ptr(), gx[0].data_ptr(), N, H, W, x.C,
-                 out.shape[3], out.coff, Ct, x.coff, 1 if self._has_grad(x) else 0, x.t.data_ptr() if final else None,
-                 ops._stream())
-        else:
-            call('sba_maxpool3x3s2_bwd', self._dt(), x.t.data_ptr(), gy[0].data_ptr(), gx[0].data_ptr(), N, H, W, x.C, Ct,
-                 x.coff, out.shape[3], out.coff, Ct, x.coff, 1 if self._has_grad(x) else 0, ops._stream())
+        final = self._readers[kx] == 0 and kx in self._relu_slices
+        call('sba_maxpool3x3s2_bwd_arg', self._dt(), arg.data_ptr(), gy[0].data_ptr(), gx[0].data_ptr(), N, H, W, x.C,
+             out.shape[3], out.coff, Ct, x.coff, 1 if self._has_grad(x) else 0, x.t.data_ptr() if final else None,
+             ops._stream())
         self._filled.add(kx)
         if final:
             self._masked.add(kx)
@@ -468,7 +482,7 @@ class InceptionHIP(object):
         out = _Act(self._new(N, H, W, x.C))
         xp, yp, dt, C, xco = x.t.data_ptr(), out.t.data_ptr(), self._dt(), x.C, x.coff
         self._launch(lambda: call('sba_avgpool3x3', dt, xp, yp, N, H, W, C, Ct, xco, C, 0, 0, ops._stream()))
-        self._record(('avgpool', None, x, out))
+        self._ops.append(('avgpool', None, x, out))
         self._consume(x)
         return out
 
@@ -481,52 +495,30 @@ class InceptionHIP(object):
         self._readers[self._key(x)] -= 1
 
     # ------------------------------------------------------------------ Inception blocks
-    # The branches of a block are independent given its input: each runs on its own HIP stream
-    # (forward and backward), which matters because the individual convs (M = 20*35^2 ... 20*8^2
-    # pixels) are far too small to fill 256 CUs one at a time.
-    def _streams(self):
-        if self._side is None:
-            self._side = [torch.cuda.Stream(device=self.device) for _ in range(4)]
-        return self._side
-
-    class _Branch(object):
-        def __init__(self, runner, k):
-            self.r, self.k = runner, k
-
-        def __enter__(self):
-            r = self.r
-            r._branch_ops = []
-            if r.group:
-                r._thunks = []              # the branch's launches are issued level by level in _end_block
-            elif r.parallel:
-                st = r._streams()[self.k]
-                st.wait_stream(r._main)
-                self.ctx = torch.cuda.stream(st)
-                self.ctx.__enter__()
-            return self
-
-        def __exit__(self, *a):
-            r = self.r
-            if r.group:
-                r._block_thunks.append(r._thunks)
-                r._thunks = None
-            elif r.parallel:
-                self.ctx.__exit__(*a)
-            r._block.append((self.k, r._branch_ops))
-            r._branch_ops = None
-
+    # The branches of a block are independent given its input: each is a function that, when _end_block has _issue run it,
+    # records its ops (for the backward) and collects its launch closures.
     def _begin_block(self, x):
-        self._main = torch.cuda.current_stream()
-        self._block = []
-        self._block_x = x
-        self._block_pre = []
-        self._block_thunks = []
+        self._block = _Block(x)
+
+    def _branch(self, k):
+        """decorator: the function below it builds branch k of the block"""
+        return lambda body: self._block.bodies.append((k, body))
+
+    def _build(self, blk, k, body):
+        ops_k, launches = [], []
+        self._ops, self._launches = ops_k, launches
+        try:
+            body()
+        finally:
+            self._ops, self._launches = self.tape, None
+        blk.branches.append((k, ops_k))
+        return launches
 
     def _heads(self, names, x, ext):
         """the fused 1x1 head convs of a block: outputs occupy channels [0, sum Op) of `ext`; returns the
         per-branch views in the order of `names`"""
         f = self.fused(names)
-        self._branch_ops = self._block_pre                 # recorded as a main-stream op of the block
+        self._ops = self._block.pre                        # recorded as a main-stream op of the block
         if self._train:     # training-mode BatchNorm: no folded (hence no fused) operands -- one conv per head
             off = 0
             for c in f.parts:
@@ -534,7 +526,7 @@ class InceptionHIP(object):
                 off += c.Op
         else:
             self.conv_L(f, x, _Act(ext, 0, f.Op))
-        self._branch_ops = None
+        self._ops = self.tape
         views, off = [], 0
         for c in f.parts:
             v = _Act(ext, off, c.Op)
@@ -544,21 +536,11 @@ class InceptionHIP(object):
         return views
 
     def _end_block(self, cat_view):
-        if self.group:
-            # level l = the l-th launch of every branch: independent of each other, the convs among them as one grid
-            for lvl in range(max(len(t) for t in self._block_thunks)):
-                self._pending = []
-                for t in self._block_thunks:
-                    if lvl < len(t):
-                        t[lvl]()
-                self._flush()
-            self._block_thunks = []
-        elif self.parallel:
-            for k, _ in self._block:
-                self._main.wait_stream(self._streams()[k])
+        blk, self._block = self._block, None
+        self._issue([(k, functools.partial(self._build, blk, k, body)) for k, body in blk.bodies])
+        blk.bodies = None
         self._relu_slices.add(self._key(cat_view))          # every slice of the concat is a ReLU (or max-pool of ReLU) output
-        self.tape.append(('block', self._block, self._block_x, self._block_pre))
-        self._block = None
+        self.tape.append(blk)
         return cat_view
 
     # Layout of a block's output tensor `ext`: [temps of the fused heads | branch1x1 | other branches ...];
@@ -571,12 +553,15 @@ class InceptionHIP(object):
         ext = self._new(N, H, W, T + 64 + 64 + 96 + pf)
         self._begin_block(x)
         t5, t3, _b1 = self._heads(names, x, ext)
-        with self._Branch(self, 1):
+        @self._branch(1)
+        def _():
             self.conv(p + '.branch5x5_2', t5, _Act(ext, T + 64, 64))
-        with self._Branch(self, 2):
+        @self._branch(2)
+        def _():
             t = self.conv(p + '.branch3x3dbl_2', t3)
             self.conv(p + '.branch3x3dbl_3', t, _Act(ext, T + 128, 96))
-        with self._Branch(self, 3):
+        @self._branch(3)
+        def _():
             self.conv(p + '.branch_pool', self.avgpool(x), _Act(ext, T + 224, pf))
         return self._end_block(_Act(ext, T, 64 + 64 + 96 + pf))
 
@@ -585,12 +570,15 @@ class InceptionHIP(object):
         OH = (H - 3) // 2 + 1
         cat = self._new(N, OH, OH, 384 + 96 + x.C)
         self._begin_block(x)
-        with self._Branch(self, 0):
+        @self._branch(0)
+        def _():
             self.conv(p + '.branch3x3', x, _Act(cat, 0, 384))
-        with self._Branch(self, 1):
+        @self._branch(1)
+        def _():
             t = self.conv(p + '.branch3x3dbl_2', self.conv(p + '.branch3x3dbl_1', x))
             self.conv(p + '.branch3x3dbl_3', t, _Act(cat, 384, 96))
-        with self._Branch(self, 2):
+        @self._branch(2)
+        def _():
             self.maxpool(x, _Act(cat, 480, x.C))
         return self._end_block(_Act(cat))
 
@@ -601,15 +589,18 @@ class InceptionHIP(object):
         ext = self._new(N, H, W, T + 768)
         self._begin_block(x)
         t7, t7d, _b1 = self._heads(names, x, ext)
-        with self._Branch(self, 1):
+        @self._branch(1)
+        def _():
             t = self.conv(p + '.branch7x7_2', t7)
             self.conv(p + '.branch7x7_3', t, _Act(ext, T + 192, 192))
-        with self._Branch(self, 2):
+        @self._branch(2)
+        def _():
             t = t7d
             for k in (2, 3, 4):
                 t = self.conv(p + '.branch7x7dbl_%d' % k, t)
             self.conv(p + '.branch7x7dbl_5', t, _Act(ext, T + 384, 192))
-        with self._Branch(self, 3):
+        @self._branch(3)
+        def _():
             self.conv(p + '.branch_pool', self.avgpool(x), _Act(ext, T + 576, 192))
         return self._end_block(_Act(ext, T, 768))
 
@@ -621,14 +612,17 @@ class InceptionHIP(object):
         tmp = self._new(N, H, W, sum(self._convs[n].Op for n in names))
         self._begin_block(x)
         t3, t7 = self._heads(names, x, tmp)
-        with self._Branch(self, 0):
+        @self._branch(0)
+        def _():
             self.conv(p + '.branch3x3_2', t3, _Act(cat, 0, 320))
-        with self._Branch(self, 1):
+        @self._branch(1)
+        def _():
             t = t7
             for k in (2, 3):
                 t = self.conv(p + '.branch7x7x3_%d' % k, t)
             self.conv(p + '.branch7x7x3_4', t, _Act(cat, 320, 192))
-        with self._Branch(self, 2):
+        @self._branch(2)
+        def _():
             self.maxpool(x, _Act(cat, 512, x.C))
         return self._end_block(_Act(cat))
 
@@ -649,30 +643,40 @@ class InceptionHIP(object):
         views = self._heads(names, x, tmp)
         t3, t3d = views[0], views[1]
         if dense_out:
-            with self._Branch(self, 0):
+            @self._branch(0)
+            def _():
                 self.conv(p + '.branch1x1', x, _Act(ext, 0, 320))
-        with self._Branch(self, 1):
+        @self._branch(1)
+        def _():
             self.conv(p + '.branch3x3_2a', t3, _Act(ext, T + 320, 384))
             self.conv(p + '.branch3x3_2b', t3, _Act(ext, T + 704, 384))
-        with self._Branch(self, 2):
+        @self._branch(2)
+        def _():
             t = self.conv(p + '.branch3x3dbl_2', t3d)
             self.conv(p + '.branch3x3dbl_3a', t, _Act(ext, T + 1088, 384))
             self.conv(p + '.branch3x3dbl_3b', t, _Act(ext, T + 1472, 384))
-        with self._Branch(self, 3):
+        @self._branch(3)
+        def _():
             self.conv(p + '.branch_pool', self.avgpool(x), _Act(ext, T + 1856, 192))
         return self._end_block(_Act(ext, T, 2048))
 
     # ------------------------------------------------------------------ forward / backward
-    def forward(self, img):
-        if not self._train and getattr(self, '_stale', False):
+    def _reset(self):
+        """(drop) the state of one forward + backward"""
+        self.tape, self.named = [], {}      # ops (kind, layer | argmax, x, out) and _Blocks in forward order; outputs by name
+        self._saved, self._grads = None, {}
+        self._readers, self._relu_slices, self._masked, self._filled = {}, set(), set(), set()
+        self._ops = self.tape               # where ops are recorded: the tape, or the op list of the block part being built
+
+    def forward(self, img, want_grad=False, train=False):
+        """want_grad: backward() will follow; train: BatchNorm with batch statistics (see trunk_features)"""
+        self._train, self._want_grad = train, want_grad
+        if not train and self._stale:
             self.refold()
-            self._stale = False
         img = img.float().contiguous()
         N, _, S, _ = img.shape
         dt = self._dt()
-        self.tape, self._grads = [], {}
-        self._readers, self._relu_slices, self._masked, self._filled = {}, set(), set(), set()
-        self.named = {}
+        self._reset()
         st = ops._stream()
         # the 299 x 299 resize (model.py:210) is never written: the stem conv interpolates on the fly
         a0 = _Act(self._new(N, 149, 149, 32))
@@ -712,7 +716,7 @@ class InceptionHIP(object):
         nef = self.nef
         features = torch.empty((N, f.C, 17, 17), dtype=torch.float32, device=self.device)
         call('sba_layout_nhwc_nchw', dt, f.t.data_ptr(), features.data_ptr(), N, 289, f.C, 0, st)
-        self._saved = (img.shape, None, a0, f, a, pooled_t, code)
+        self._saved = (img.shape, a0, f, a, pooled_t, code)
         return features[:, :nef], code.t.view(N, -1)[:, :nef].float()
 
     def trunk_features(self, img, train=False):
@@ -726,37 +730,31 @@ class InceptionHIP(object):
         image_encoder*.pth carries into the GAN.  Each BasicConv2d then runs as conv (unfolded weights, statistics in
         the epilogue) + one BatchNorm/ReLU pass; train=False (evaluate(), pretrain_DAMSM.py:134) is the folded trunk."""
         with torch.no_grad():
-            saved = (self._train, self.group, self.parallel)
-            if train:
-                self._train, self.group, self.parallel = True, False, False
+            mode = self.mode
+            if train:       # (_conv_train allocates and launches as it goes)
+                self.mode = 'serial'
             try:
-                self.forward(img)
+                self.forward(img, train=train)
             finally:
-                self._train, self.group, self.parallel = saved
+                self.mode = mode
             if train:       # the folded operands of the next eval-mode call must see the moved running statistics
                 self._stale = True
-            (_, _, _, _, last, pooled_t, _) = self._saved
             feat_in = self.named['Mixed_6e']
             f768 = feat_in.t[..., feat_in.coff:feat_in.coff + 768].float().contiguous()
-            pooled = pooled_t.t.view(img.shape[0], -1)[:, :2048].float().contiguous()
-        self.tape, self._grads, self._saved, self.named = [], {}, None, {}
+            pooled = self._saved[4].t.view(img.shape[0], -1)[:, :2048].float().contiguous()
+        self._reset()
         return f768, pooled
 
     def pooled_features(self, img):
         """The pooled Mixed_7c output [B, 2048] in f32 as the global average pool wrote it (not rounded to the compute
         dtype): an eval-mode forward without a tape.  The feature FID is taken on (sbagan/fid.py)."""
         with torch.no_grad():
-            saved = self._train
-            self._train = False
-            try:
-                self.forward(img)
-            finally:
-                self._train = saved
-        self.tape, self._grads, self._saved, self.named = [], {}, None, {}
+            self.forward(img)
+        self._reset()
         return self.last_pooled
 
     def backward(self, dfeat, dcode):
-        (ishape, x299, a0, f, last, pooled_t, code) = self._saved
+        (ishape, a0, f, last, pooled_t, code) = self._saved
         N = ishape[0]
         dt, st = self._dt(), ops._stream()
         # seed the two head gradients
@@ -780,6 +778,7 @@ class InceptionHIP(object):
             if dcode is not None:
                 gc[0].view(N, -1)[:, :self.nef] = dcode.to(self.dtype)
         self._filled.add(self._key(code))
+
         def run(op):
             kind, L, x, out = op
             if kind == 'conv':
@@ -795,54 +794,22 @@ class InceptionHIP(object):
                 self._avgpool_bwd(x, out)
 
         for entry in reversed(self.tape):
-            if entry[0] != 'block':
+            if not isinstance(entry, _Block):
                 run(entry)
                 continue
-            # a block: every branch back-propagates on its own stream; ops that read the block INPUT (they
+            # a block: every branch back-propagates as a chain of its own; ops that read the block INPUT (they
             # accumulate into its shared gradient) are held back and run in order on the main stream after
             # the join -- pools first, convs next, the fused head conv last: the last accumulation is then
             # a conv data-gradient, whose epilogue applies the input's ReLU mask
-            main = torch.cuda.current_stream()
-            _, branches, bx, pre = entry
-            held = []
-            used = []
-            if self.group:
-                chains = []
-                for k, ops_k in branches:
-                    rest = list(ops_k)
-                    if rest and rest[0][2].t is bx.t:
-                        held.append(rest.pop(0))
-                    if rest:
-                        chains.append(list(reversed(rest)))
-                for lvl in range(max([len(c) for c in chains] or [0])):
-                    self._pending = []
-                    for c in chains:
-                        if lvl < len(c):
-                            run(c[lvl])
-                    self._flush()
-                for op in sorted(held, key=lambda o: 0 if o[0] != 'conv' else 1) + list(reversed(pre)):
-                    run(op)
-                continue
-            for k, ops_k in branches:
+            held, chains = [], []
+            for k, ops_k in entry.branches:
                 rest = list(ops_k)
-                if rest and rest[0][2].t is bx.t:
+                if rest and rest[0][2].t is entry.x.t:
                     held.append(rest.pop(0))
-                if not rest:
-                    continue
-                used.append(k)
-                if self.parallel:
-                    sk = self._streams()[k]
-                    sk.wait_stream(main)
-                    with torch.cuda.stream(sk):
-                        for op in reversed(rest):
-                            run(op)
-                else:
-                    for op in reversed(rest):
-                        run(op)
-            if self.parallel:
-                for k in used:
-                    main.wait_stream(self._streams()[k])
-            for op in sorted(held, key=lambda o: 0 if o[0] != 'conv' else 1) + list(reversed(pre)):
+                if rest:
+                    chains.append((k, lambda rest=rest: [functools.partial(run, op) for op in reversed(rest)]))
+            self._issue(chains)
+            for op in sorted(held, key=lambda o: o[0] == 'conv') + entry.pre[::-1]:
                 run(op)
         g0 = self._grad_of(a0)
         d299 = torch.empty((N, 3, 299, 299), dtype=torch.float32, device=self.device)
@@ -850,9 +817,9 @@ class InceptionHIP(object):
              299, 32, st)
         dimg = torch.empty(ishape, dtype=torch.float32, device=self.device)
         call('sba_resize_bilinear', d299.data_ptr(), dimg.data_ptr(), N * 3, ishape[2], 299, 1, st)
-        if not getattr(self, 'keep_debug', False):
-            self.tape, self._grads, self._saved, self.named = [], {}, None, {}
-        self.d299 = d299 if getattr(self, 'keep_debug', False) else None
+        self.d299 = d299 if self.keep_debug else None
+        if not self.keep_debug:
+            self._reset()
         return dimg
 
     def __call__(self, img):
@@ -863,8 +830,7 @@ class _InceptionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, runner):
         ctx.runner = runner
-        runner._want_grad = bool(ctx.needs_input_grad[0])      # a backward will follow: keep the max-pool argmax
-        feats, code = runner.forward(img)
+        feats, code = runner.forward(img, want_grad=bool(ctx.needs_input_grad[0]))
         return feats.contiguous(), code.contiguous()
 
     @staticmethod

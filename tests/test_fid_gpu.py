@@ -307,9 +307,9 @@ class _CountForwards(object):
         self.cls, self.orig, self.n = InceptionHIP, InceptionHIP.forward, 0
         counter = self
 
-        def forward(runner, img):
+        def forward(runner, img, *args, **kwargs):
             counter.n += 1
-            return counter.orig(runner, img)
+            return counter.orig(runner, img, *args, **kwargs)
         InceptionHIP.forward = forward
         return self
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the HIP Inception-v3 trunk (sbagan.inception_hip) forward + backward-data at B = 20, 256 px: eager launches and
-ONE hipGraph replay (the form it takes inside the benched step).  SBA_ENC_GROUP=0/1 switches the grouped per-level launches.
+ONE hipGraph replay (the form it takes inside the benched step).
     python tools/bench_encoder_hip.py [bf16|f32]"""
 import os
 import sys

@@ -10,7 +10,7 @@ dev = torch.device('cuda:0')
 ops.set_compute_dtype(torch.bfloat16)
 enc = model.CNN_ENCODER(256).to(dev).eval()
 run = InceptionHIP(enc)
-run.parallel = (sys.argv[1] == '1') if len(sys.argv) > 1 else True
+run.mode = sys.argv[1] if len(sys.argv) > 1 else 'streams'      # 'group' | 'streams' | 'serial'
 x = torch.rand(20, 3, 256, 256, device=dev) * 2 - 1
 xi = x.clone().requires_grad_(True)
 def step():

@@ -12,6 +12,7 @@ inputs from oracle/fill.py, and only numeric outputs are written.
     python tools/make_golden.py infer      # the eval-mode generator fixtures (infer_*.npz)
     SBA_LIB_PATH=<parent build> python tools/make_golden.py igemm_plan     # the kernel-choice recording
     SBA_LIB_PATH=<recorder build> python tools/make_golden.py wgrad_plan   # ... of the weight gradient
+    SBA_ENCODER_DRIVER=<module> python tools/make_golden.py encoder_trace  # the Inception driver's launches (needs a GPU)
 """
 import os
 import sys
@@ -438,6 +439,26 @@ def gen_wgrad_plan():
                                                      os.path.getsize(T.GOLDEN)))
 
 
+def gen_encoder_trace():
+    """encoder_trace.jsonl: every launch of the Inception trunk driver in the cases of tests/test_encoder_trace_gpu.py, from
+    a driver that is NOT the code under test: SBA_ENCODER_DRIVER names a module holding the parent commit's
+    sbagan/inception_hip.py (`git show <parent>:sba-gan_amd/sbagan/inception_hip.py` into an untracked sibling module of the
+    package, e.g. sbagan/_inception_hip_parent.py -> SBA_ENCODER_DRIVER=sbagan._inception_hip_parent)."""
+    import importlib
+    import json
+    assert os.environ.get('SBA_ENCODER_DRIVER'), 'set SBA_ENCODER_DRIVER to a module with the parent commit\'s driver'
+    sys.path[:0] = [os.path.join(ROOT, 'sba-gan_amd'), os.path.join(ROOT, 'tests')]
+    import test_encoder_trace_gpu as T
+    module = importlib.import_module(os.environ['SBA_ENCODER_DRIVER'])
+    traces = [(name, T.run_case(module, dt, what, torch.device('cuda:0'))) for name, dt, what in T.CASES]
+    with open(T.GOLDEN, 'w') as f:
+        for name, trace in traces:
+            for entry, args in trace:
+                f.write(json.dumps([name, entry, args], separators=(',', ':')) + '\n')
+    print('encoder_trace.jsonl from %s: %s, %d bytes' % (module.__file__, {name: len(t) for name, t in traces},
+                                                         os.path.getsize(T.GOLDEN)))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     what = sys.argv[1:] or ['units', 'step_tiny', 'step_full']
@@ -450,6 +471,11 @@ def main():
     if 'wgrad_plan' in what:
         gen_wgrad_plan()
         what = [w for w in what if w != 'wgrad_plan']
+        if not what:
+            return
+    if 'encoder_trace' in what:
+        gen_encoder_trace()
+        what = [w for w in what if w != 'encoder_trace']
         if not what:
             return
     ref = load_reference()

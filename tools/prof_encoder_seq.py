@@ -9,7 +9,7 @@ dev = torch.device('cuda:0')
 ops.set_compute_dtype(torch.bfloat16)
 enc = model.CNN_ENCODER(256).to(dev).eval()
 run = InceptionHIP(enc)
-run.parallel = os.environ.get('PAR', '0') == '1'
+run.mode = os.environ.get('MODE', 'serial')      # 'group' | 'streams' | 'serial'
 x = torch.rand(20, 3, 256, 256, device=dev) * 2 - 1
 def step():
     xi = x.clone().requires_grad_(True)
@@ -24,4 +24,4 @@ torch.cuda.synchronize(); t0 = time.perf_counter()
 tb = 0
 for _ in range(5): tb += step()
 torch.cuda.synchronize(); tt = time.perf_counter() - t0
-print('hip encoder (parallel=%s) fwd %.2f ms  bwd %.2f ms' % (run.parallel, (tt - tb) / 5 * 1e3, tb / 5 * 1e3))
+print('hip encoder (mode=%s) fwd %.2f ms  bwd %.2f ms' % (run.mode, (tt - tb) / 5 * 1e3, tb / 5 * 1e3))
