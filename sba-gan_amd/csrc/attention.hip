@@ -10,7 +10,6 @@
 // Mask quirk (GlobalAttention.py:105-108): the reference masks row r = b*Q + q of
 // the (B*Q) x L score matrix with mask.repeat(Q, 1)[r] = mask[r % B], not mask[b].
 // mask_mode 0 reproduces that bit-for-bit; mask_mode 1 is the per-sample mask.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -670,13 +669,6 @@ __global__ __launch_bounds__(256) void word_attn_bwd_mfma_kernel(
     }
 }
 
-// SBA_ATTN_MFMA=0: the VALU kernel for bf16 as well (A/B aid)
-static int attn_mfma_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("SBA_ATTN_MFMA"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v;
-}
-
 template <int IDF, int MODE>
 int launch_fwd_mfma(const void* h, const float* src, const uint8_t* mask, void* ctx, float* att, int B, int Q, int L,
                     int mode, int ocs, int oco, hipStream_t st) {
@@ -691,7 +683,7 @@ int launch_fwd_mfma(const void* h, const float* src, const uint8_t* mask, void* 
 template <typename T, int IDF>
 int launch_fwd(const void* h, const float* src, const uint8_t* mask, void* ctx, float* att, int B, int Q, int L,
                int mode, int ocs, int oco, hipStream_t st) {
-    if (sizeof(T) == 2 && IDF <= 64 && ocs % 4 == 0 && oco % 4 == 0 && attn_mfma_enabled())
+    if (sizeof(T) == 2 && IDF <= 64 && ocs % 4 == 0 && oco % 4 == 0)
         return launch_fwd_mfma<(IDF <= 64 ? IDF : 32), 0>(h, src, mask, ctx, att, B, Q, L, mode, ocs, oco, st);
     dim3 grid(cdiv(Q, 256), B);
     SBA_LAUNCH((word_attn_fwd_kernel<T, IDF>), grid, dim3(256), 0, st, (const T*)h, src, mask, (T*)ctx, att,
@@ -702,7 +694,7 @@ int launch_fwd(const void* h, const float* src, const uint8_t* mask, void* ctx, 
 template <typename T, int IDF>
 int launch_bwd(const void* h, const float* src, const uint8_t* mask, const void* dctx, void* dh, float* dsrc, int B,
                int Q, int L, int mode, int dcs, int dco, int acc, hipStream_t st) {
-    if (sizeof(T) == 2 && IDF == 32 && dcs % 8 == 0 && dco % 8 == 0 && attn_mfma_enabled()) {
+    if (sizeof(T) == 2 && IDF == 32 && dcs % 8 == 0 && dco % 8 == 0) {
         const int tiles = cdiv(Q, 32);
         const int tpw = tiles * B >= 16384 ? 4 : (tiles * B >= 4096 ? 2 : 1);
         dim3 grid(cdiv(tiles, 4 * tpw), B);

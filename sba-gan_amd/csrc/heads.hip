@@ -5,7 +5,6 @@
 //   - logits head           conv4x4 s4 (8ndf->1)+sigmoid on the 4x4 map (D_GET_LOGITS, model.py:590-607)
 //   - conditioning concat   (model.py:597-600)
 // Images stay in the reference's NCHW f32 layout at the boundary; features are NHWC.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -1189,6 +1188,32 @@ template <typename K> void set_lds(K kernel, size_t bytes) {
         (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// The bf16 image head / discriminator stem run on the matrix cores at these shapes (forward and backward alike).
+inline bool img_head_on_mfma(int dtype, int C, int H, int W, int64_t total) {
+    return dtype == SBA_BF16 && C == 32 && W % 32 == 0 && H % 8 == 0 && total / 256 <= 0x7fffffff;
+}
+inline bool stem_on_mfma(int dtype, int64_t pix) { return dtype == SBA_BF16 && pix < 0x7fffffff; }
+
+// Per-workgroup partial sums of a weight gradient, `blocks` slots of `n` floats: from the deterministic ring in deterministic
+// mode (false = the ring is full), else from the reduce ring where `reduce_ring` allows it and more than 64 workgroups would
+// add into the same addresses, else none (buf stays null: the kernel adds with atomics).  fold() adds the slots into dw.
+struct Partials {
+    float* buf = nullptr;
+    bool det = false;
+    int blocks = 0;
+    int64_t n = 0;
+    bool alloc(int blocks_, int64_t n_, bool reduce_ring) {
+        blocks = blocks_, n = n_, det = sba_det_on();
+        if (det) buf = sba_det_alloc(blocks * n);
+        else if (reduce_ring && blocks > 64) buf = sba_reduce_alloc(blocks * n);
+        return buf || !det;
+    }
+    void fold(float* dw, hipStream_t st) const {
+        if (buf && det) sba_det_fold(buf, 1, blocks, n, dw, 0, 0, st);
+        else if (buf) sba_fold_add(buf, blocks, n, dw, st);
+    }
+};
+
 }  // namespace
 
 #define CH_SWITCH(C_, CALL)                              \
@@ -1204,9 +1229,7 @@ extern "C" int sba_img_head_fwd(int dtype, const void* h, const float* w, float*
     if (!h || !w || !img || N <= 0 || H <= 0 || W <= 0) return SBA_E_ARG;
     const int64_t total = (int64_t)N * H * W;
     if (total > 0x7fffffffLL * 64) return SBA_E_ARG;
-    static int mfma = -1;       // SBA_HEAD_MFMA=0: the VALU kernel for bf16 as well (A/B aid)
-    if (mfma < 0) { const char* e = getenv("SBA_HEAD_MFMA"); mfma = (e && e[0] == '0') ? 0 : 1; }
-    if (dtype == SBA_BF16 && mfma && C_ == 32 && W % 32 == 0 && H % 8 == 0 && total / 256 <= 0x7fffffff) {
+    if (img_head_on_mfma(dtype, C_, H, W, total)) {
         const int ntiles = (int)(total / 256);
         const int blocks = ntiles < 1024 ? ntiles : 1024;       // persistent: four workgroups per CU
         SBA_LAUNCH(img_head_fwd_mfma_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)h, w, img,
@@ -1224,31 +1247,26 @@ extern "C" int sba_img_head_bwd(int dtype, const void* h, const float* w, const 
     if (!h || !w || !img || !dimg || !dh || !dw || N <= 0 || H <= 0 || W <= 0) return SBA_E_ARG;
     if (C_ > 64) return SBA_E_ARG;       // LDS budget of the fused wgrad contraction
     const int64_t total = (int64_t)N * H * W;
-    static int mfma = -1;       // SBA_HEAD_MFMA=0: the VALU / f32-MFMA kernel for bf16 as well (A/B aid)
-    if (mfma < 0) { const char* e = getenv("SBA_HEAD_MFMA"); mfma = (e && e[0] == '0') ? 0 : 1; }
-    if (dtype == SBA_BF16 && mfma && C_ == 32 && W % 32 == 0 && H % 8 == 0 && total / 256 <= 0x7fffffff) {
+    if (img_head_on_mfma(dtype, C_, H, W, total)) {
         const int ntiles = (int)(total / 256);
         const int blocks = ntiles < 1024 ? ntiles : 1024;       // persistent: four workgroups per CU
         hipStream_t st = (hipStream_t)stream;
-        float* part = nullptr;
-        const bool det = sba_det_on();
-        if (det) { part = sba_det_alloc((int64_t)blocks * 27 * 32); if (!part) return SBA_E_ARG; }
-        else if (blocks > 64) part = sba_reduce_alloc((int64_t)blocks * 27 * 32);      // (none: atomics)
+        Partials part;
+        if (!part.alloc(blocks, 27 * 32, true)) return SBA_E_ARG;
         SBA_LAUNCH(img_head_bwd_mfma_kernel, dim3(blocks), dim3(256), 0, st, (const bf16_t*)h, w, img, dimg,
-                   (bf16_t*)dh, dw, N, H, W, accumulate, ntiles, part);
-        if (part && det) sba_det_fold(part, 1, blocks, 27 * 32, dw, 0, 0, st);
-        else if (part) sba_fold_add(part, blocks, 27 * 32, dw, st);
+                   (bf16_t*)dh, dw, N, H, W, accumulate, ntiles, part.buf);
+        part.fold(dw, st);
         return SBA_CHECK_LAUNCH();
     }
     SBA_DISPATCH(dtype, CH_SWITCH(C_, {
         const size_t sh = sizeof(float) * (27 * C + 256 * (C + 1) + 256 * 33 + 32 * C);
         set_lds(img_head_bwd_kernel<T, C>, sh);
         const int blocks = cdiv(total, 256);
-        float* part = nullptr;
-        if (sba_det_on()) { part = sba_det_alloc((int64_t)blocks * 27 * C); if (!part) return SBA_E_ARG; }
+        Partials part;
+        if (!part.alloc(blocks, 27 * C, false)) return SBA_E_ARG;
         SBA_LAUNCH((img_head_bwd_kernel<T, C>), dim3(blocks), dim3(256), sh, (hipStream_t)stream,
-                           (const T*)h, w, img, dimg, (T*)dh, dw, N, H, W, accumulate, part);
-        if (part) sba_det_fold(part, 1, blocks, 27 * C, dw, 0, 0, (hipStream_t)stream);
+                           (const T*)h, w, img, dimg, (T*)dh, dw, N, H, W, accumulate, part.buf);
+        part.fold(dw, (hipStream_t)stream);
     }));
     return SBA_CHECK_LAUNCH();
 }
@@ -1258,9 +1276,7 @@ extern "C" int sba_d_stem_fwd(int dtype, const float* img, const float* w, void*
     if (!img || !w || !out || N <= 0 || S <= 0 || S % 2 || C <= 0 || C % STEM_CB || C > 256) return SBA_E_ARG;
     const int64_t pix = (int64_t)N * (S / 2) * (S / 2);
     if ((pix + 255) / 256 > 0x7fffffff) return SBA_E_ARG;
-    static int mfma = -1;       // SBA_STEM_MFMA=0: the VALU kernel for bf16 as well (A/B aid)
-    if (mfma < 0) { const char* e = getenv("SBA_STEM_MFMA"); mfma = (e && e[0] == '0') ? 0 : 1; }
-    if (dtype == SBA_BF16 && mfma && (C == 32 || C == 64 || C == 128) && pix < 0x7fffffff) {
+    if (stem_on_mfma(dtype, pix) && (C == 32 || C == 64 || C == 128)) {
         const int64_t tiles = (pix + 31) / 32;
         const int tpw = tiles >= 16384 ? 4 : (tiles >= 4096 ? 2 : 1);
         const dim3 grid((unsigned)((tiles + 4 * tpw - 1) / (4 * tpw)));
@@ -1281,23 +1297,18 @@ extern "C" int sba_d_stem_bwd(int dtype, const float* img, const float* w, const
                               float* dimg, float* dw, int N, int S, int C, void* stream) {
     if (!img || !w || !out || !dout || N <= 0 || S <= 0 || S % 2 || C <= 0 || C % 32 || C > 256) return SBA_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    static int mfma = -1;       // SBA_STEM_MFMA=0: the VALU / f32-MFMA kernels for bf16 as well (A/B aid)
-    if (mfma < 0) { const char* e = getenv("SBA_STEM_MFMA"); mfma = (e && e[0] == '0') ? 0 : 1; }
-    const bool mm = dtype == SBA_BF16 && mfma && C == 64 && (int64_t)N * (S / 2) * (S / 2) < 0x7fffffff;
+    const bool mm = stem_on_mfma(dtype, (int64_t)N * (S / 2) * (S / 2)) && C == 64;
     if (dw && mm) {
         const int64_t pix = (int64_t)N * (S / 2) * (S / 2);
         const int64_t tiles = (pix + 63) / 64;
         int tpb = (int)((tiles + 767) / 768);       // three workgroups per CU (48 KB of LDS each)
         if (tpb < 1) tpb = 1;
         const int blocks = (int)((tiles + tpb - 1) / tpb);
-        float* part = nullptr;
-        const bool det = sba_det_on();
-        if (det) { part = sba_det_alloc((int64_t)blocks * C * 48); if (!part) return SBA_E_ARG; }
-        else if (blocks > 64) part = sba_reduce_alloc((int64_t)blocks * C * 48);    // (none: atomics)
+        Partials part;
+        if (!part.alloc(blocks, (int64_t)C * 48, true)) return SBA_E_ARG;
         SBA_LAUNCH(d_stem_wgrad_mfma_kernel, dim3(blocks), dim3(256), 0, st, img, (const bf16_t*)out,
-                   (const bf16_t*)dout, part ? part : dw, N, S, tpb, part ? 1 : 0);
-        if (part && det) sba_det_fold(part, 1, blocks, (int64_t)C * 48, dw, 0, 0, st);
-        else if (part) sba_fold_add(part, blocks, (int64_t)C * 48, dw, st);
+                   (const bf16_t*)dout, part.buf ? part.buf : dw, N, S, tpb, part.buf ? 1 : 0);
+        part.fold(dw, st);
         dw = nullptr;
     }
     if (dimg && mm && (S / 2) % 16 == 0) {
@@ -1316,14 +1327,14 @@ extern "C" int sba_d_stem_bwd(int dtype, const float* img, const float* w, const
         if (tpb < 1) tpb = 1;
         const int blocks = (int)((tiles + tpb - 1) / tpb);
         const size_t sh = sizeof(float) * (64 * (C + (C % 64 == 0 ? 32 : 0)) + 64 * 96);
-        float* part = nullptr;
-        if (sba_det_on()) { part = sba_det_alloc((int64_t)blocks * C * 48); if (!part) return SBA_E_ARG; }
+        Partials part;
+        if (!part.alloc(blocks, (int64_t)C * 48, false)) return SBA_E_ARG;
         SBA_DISPATCH(dtype, {
             set_lds(d_stem_wgrad_kernel<T>, sh);
             SBA_LAUNCH((d_stem_wgrad_kernel<T>), dim3(blocks), dim3(256), sh, st, img, (const T*)out,
-                               (const T*)dout, part ? part : dw, N, S, C, tpb, part ? 1 : 0);
+                               (const T*)dout, part.buf ? part.buf : dw, N, S, C, tpb, part.buf ? 1 : 0);
         });
-        if (part) sba_det_fold(part, 1, blocks, (int64_t)C * 48, dw, 0, 0, st);
+        part.fold(dw, st);
     }
     if (dimg) {
         const size_t sh = sizeof(float) * (48 * C + 100 * (C + 4));

@@ -67,7 +67,7 @@ __global__ void adam_prepare_kernel(AdamState* st, float lr, float beta1, float 
 // backward at 292 us, a 36 us stem data gradient at 387 us, a 10 us 8x8 conv at 280 us while adam_step runs).  Nothing in
 // the update is read twice, so every access is marked streaming.  MEASURED (same box, two runs each,
 // gpurun_out/r4_ab_adam_nt*.json): 10.54 / 10.69 ms with, 10.59 / 10.67 ms without -- no difference: the neighbours are
-// slowed by the HBM queues, not by L2 evictions.  Kept (harmless, SBA_ADAM_NT=0 turns it off).
+// slowed by the HBM queues, not by L2 evictions.  Kept (harmless).
 template <bool NT>
 __device__ __forceinline__ f32x4_t ld4(const float* a, int64_t i) {
     const f32x4_t* q = reinterpret_cast<const f32x4_t*>(a) + i;
@@ -168,14 +168,8 @@ extern "C" int sba_adam_step(float* p, const float* g, float* m, float* v, float
     int64_t blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    static int nt = -1;         // SBA_ADAM_NT=0: ordinary (cached) accesses (A/B aid)
-    if (nt < 0) { const char* e = getenv("SBA_ADAM_NT"); nt = (e && e[0] == '0') ? 0 : 1; }
-    if (nt)
-        SBA_LAUNCH(adam_step_kernel<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, avg,
-                   (bf16_t*)shadow, (const AdamState*)state, n, beta1, beta2, eps, grad_scale);
-    else
-        SBA_LAUNCH(adam_step_kernel<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, avg,
-                   (bf16_t*)shadow, (const AdamState*)state, n, beta1, beta2, eps, grad_scale);
+    SBA_LAUNCH(adam_step_kernel<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, avg,
+               (bf16_t*)shadow, (const AdamState*)state, n, beta1, beta2, eps, grad_scale);
     return SBA_CHECK_LAUNCH();
 }
 

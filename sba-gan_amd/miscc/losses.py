@@ -13,7 +13,6 @@ Differences from the reference, none of which change a result:
     (losses.py:24-32,73-76) -- it is integer work on `class_ids`, a host array.
 """
 import numpy as np
-import os
 
 import torch
 
@@ -53,9 +52,7 @@ class LossLogs(dict):
 
 
 _MASK_CACHE = {}
-BATCH_REAL_FAKE = True
-FUSED_HEADS = os.environ.get('SBA_FUSED_HEADS', '1') != '0'   # ops.DHeadsFn: one autograd node per discriminator term
-DIRECT_DAMSM = os.environ.get('SBA_DIRECT_DAMSM', '1') != '0'  # damsm_image_terms: loss heads + gradients without autograd
+DIRECT_DAMSM = True     # damsm_image_terms: loss heads + gradients without autograd
 
 
 def class_mask(class_ids, batch_size, device):
@@ -100,55 +97,49 @@ def words_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size)
     return l0, l1, []
 
 
+def d_term_heads(n, uncond):
+    """The heads of errD (losses.py:141-158) over feats = [n real | n fake] rows, as ops.Head records in the reference's
+    call order: cond_real, cond_fake, cond_wrong (real rows 0..n-2 with conditions 1..n-1), then real and fake logits.
+    errD = (real + cond_real)/2 + (fake + cond_fake + cond_wrong)/3; without the unconditional head
+    cond_real + (cond_fake + cond_wrong)/2."""
+    H = ops.Head
+    if uncond:
+        return (H(0, n, 0, 1., .5, 1), H(n, n, 0, 0., 1. / 3, 3), H(0, n - 1, 1, 0., 1. / 3, 4),
+                H(0, n, None, 1., .5, 0), H(n, n, None, 0., 1. / 3, 2))
+    return (H(0, n, 0, 1., 1., 0), H(n, n, 0, 0., .5, 1), H(0, n - 1, 1, 0., .5, 2))
+
+
+def g_term_heads(n, uncond):
+    """The heads of one discriminator's term of errG (losses.py:168-186) over the n fake rows."""
+    H = ops.Head
+    if uncond:
+        return (H(0, n, 0, 1., 1., 1), H(0, n, None, 1., 1., 0))
+    return (H(0, n, 0, 1., 1., 0),)
+
+
 def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake_labels, real_features=None):
-    """losses.py:136-161: two separate trunk passes (real, fake.detach()), five heads,
+    """losses.py:136-161: the real and the fake.detach() trunk pass, five heads,
     errD = (real + cond_real)/2 + (fake + cond_fake + cond_wrong)/3.
+
+    The two passes run as one over [real | fake] with per-half BatchNorm batches: same results and module state as the
+    reference's two calls, half the launches and weight reads.  The heads and the BCE sum are one autograd node over
+    that feature map (ops.DHeadsFn).
 
     real_features (optional, beyond the reference's signature): netD(real_imgs) evaluated AHEAD of this call (the
     data-parallel step runs it beside the generator's gradient exchange: it does not depend on the generator); the
     fake half then runs as its own pass, in the reference's order (real first), with the same per-pass BatchNorm
     batches and running-statistic updates."""
-    feats = None
     if real_features is not None:
-        n = real_features.size(0)
-        fake_features = netD(fake_imgs.detach())
-        if FUSED_HEADS and fake_features.shape == real_features.shape:
-            feats = torch.cat((real_features, fake_features), 0)
-            if netD.UNCOND_DNET is not None:
-                heads = ((0, n, 0, 1., .5, 1), (n, n, 0, 0., 1. / 3, 3), (0, n - 1, 1, 0., 1. / 3, 4),
-                         (0, n, None, 1., .5, 0), (n, n, None, 0., 1. / 3, 2))
-            else:
-                heads = ((0, n, 0, 1., 1., 0), (n, n, 0, 0., .5, 1), (0, n - 1, 1, 0., .5, 2))
-            return ops.d_heads(netD, feats, conditions, heads)
-    elif BATCH_REAL_FAKE and real_imgs.shape == fake_imgs.shape:
-        # one trunk pass over [real | fake] with per-half BatchNorm batches: same results and module
-        # state as the reference's two calls, half the launches and weight reads
-        n = real_imgs.size(0)
-        feats = netD(torch.cat((real_imgs, fake_imgs.detach()), 0), groups=2)
-        real_features, fake_features = feats[:n], feats[n:]
+        real, fake = real_features, netD(fake_imgs.detach())
     else:
-        real_features = netD(real_imgs)
-        fake_features = netD(fake_imgs.detach())
-    batch_size = real_features.size(0)
-    if FUSED_HEADS and feats is not None:
-        # the five heads + the BCE sum as one autograd node over the [real | fake] feature map (ops.DHeadsFn):
-        # evaluated in the reference's call order, summed in the order of the terms of errD
-        n = batch_size
-        if netD.UNCOND_DNET is not None:
-            heads = ((0, n, 0, 1., .5, 1), (n, n, 0, 0., 1. / 3, 3), (0, n - 1, 1, 0., 1. / 3, 4),
-                     (0, n, None, 1., .5, 0), (n, n, None, 0., 1. / 3, 2))
-        else:
-            heads = ((0, n, 0, 1., 1., 0), (n, n, 0, 0., .5, 1), (0, n - 1, 1, 0., .5, 2))
-        return ops.d_heads(netD, feats, conditions, heads)
-    cond_real = netD.COND_DNET(real_features, conditions)
-    cond_fake = netD.COND_DNET(fake_features, conditions)
-    cond_wrong = netD.COND_DNET(real_features[:(batch_size - 1)], conditions[1:batch_size])
-    if netD.UNCOND_DNET is not None:
-        real = netD.UNCOND_DNET(real_features)
-        fake = netD.UNCOND_DNET(fake_features)
-        return ops.BCEMultiFn.apply((1., 1., 0., 0., 0.), (.5, .5, 1. / 3, 1. / 3, 1. / 3),
-                                    real, cond_real, fake, cond_fake, cond_wrong)
-    return ops.BCEMultiFn.apply((1., 0., 0.), (1., .5, .5), cond_real, cond_fake, cond_wrong)
+        real, fake = real_imgs, fake_imgs.detach()
+    if real.shape != fake.shape:
+        raise ValueError('discriminator_loss: real %s and fake %s differ in shape'
+                         % (tuple(real.shape), tuple(fake.shape)))
+    feats = torch.cat((real, fake), 0)
+    if real_features is None:
+        feats = netD(feats, groups=2)
+    return ops.d_heads(netD, feats, conditions, d_term_heads(real.size(0), netD.UNCOND_DNET is not None))
 
 
 def damsm_image_terms(image_encoder, fake_img, words_embs, sent_emb, match_labels, cap_lens, class_ids):
@@ -184,16 +175,7 @@ def damsm_image_terms(image_encoder, fake_img, words_embs, sent_emb, match_label
 
 def _g_term(netD, features, sent_emb):
     """the adversarial term of generator_loss for one discriminator's features of the fake images (losses.py:168-186)"""
-    if FUSED_HEADS:
-        n = features.size(0)
-        if netD.UNCOND_DNET is not None:
-            return ops.d_heads(netD, features, sent_emb, ((0, n, 0, 1., 1., 1), (0, n, None, 1., 1., 0)))
-        return ops.d_heads(netD, features, sent_emb, ((0, n, 0, 1., 1., 0),))
-    cond_logits = netD.COND_DNET(features, sent_emb)
-    if netD.UNCOND_DNET is not None:
-        logits = netD.UNCOND_DNET(features)
-        return ops.BCEMultiFn.apply((1., 1.), (1., 1.), logits, cond_logits)
-    return ops.BCEMultiFn.apply((1.,), (1.,), cond_logits)
+    return ops.d_heads(netD, features, sent_emb, g_term_heads(features.size(0), netD.UNCOND_DNET is not None))
 
 
 def generator_d_term(netD, fake_img, sent_emb):

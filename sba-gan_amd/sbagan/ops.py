@@ -13,6 +13,7 @@ parameters.
 """
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 
@@ -1376,13 +1377,7 @@ class BCEMultiFn(torch.autograd.Function):
         offs = [0]
         for s in sizes:
             offs.append(offs[-1] + s)
-        key = (tuple(offs), tuple(targets), tuple(weights), dev)
-        meta = _BCE_META.get(key)
-        if meta is None:
-            meta = (torch.tensor(offs, dtype=torch.int32, device=dev),
-                    torch.tensor(targets, dtype=torch.float32, device=dev),
-                    torch.tensor(weights, dtype=torch.float32, device=dev))
-            _BCE_META[key] = meta
+        meta = _bce_meta(offs, targets, weights, dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dprob = torch.empty_like(cat)
         call('sba_bce_multi', _p(cat), _p(meta[0]), _p(meta[1]), _p(meta[2]), len(sizes), _p(loss), _p(dprob),
@@ -1412,7 +1407,73 @@ def _bce_meta(offs, targets, weights, dev):
     return meta
 
 
-GROUP_COND_HEADS = os.environ.get('SBA_GROUP_COND_HEADS', '1') != '0'
+Head = namedtuple('Head', 'row0 rows cond_row0 target weight segment')
+
+
+class _CondGroup(object):
+    """Conditional heads that share one jointConv launch: their inputs back to back in `xin`, the conv output `y`;
+    off[head index] = the head's first row in both (and in the gradient of y)."""
+    __slots__ = ('heads', 'off', 'xin', 'y', 'stats', 'want_stats', 'bn_forward')
+
+
+def _cond_groups(heads, bn):
+    """The conditional heads of one term (real / fake / wrong pairs, losses.py:143-149) share jointConv's weights: in
+    training mode their inputs go into ONE tensor and one conv / data-gradient / weight-gradient launch serves all of them
+    (M = 944 rows at B = 20 instead of three GEMM-like launches of 320 / 320 / 304 rows, each with its own K split +
+    finishing launch); otherwise every head is a group of its own.  BatchNorm stays per head, in the reference's call
+    order (batch statistics and running-statistic updates of three separate module calls)."""
+    cond_idx = [i for i, hd in enumerate(heads) if hd.cond_row0 is not None]
+    together = len(cond_idx) >= 2 and bn.training
+    groups = []
+    for idx in ([cond_idx] if together else [[i] for i in cond_idx]):
+        g = _CondGroup()
+        g.heads, g.off = idx, {}
+        if len(idx) == 1:       # the statistics come out of the conv epilogue
+            g.want_stats = bn.training
+            g.bn_forward = lambda y, stats: bn_act_forward(y, stats, bn, ACT_LRELU)
+        else:
+            g.want_stats = False
+            g.bn_forward = lambda y, stats: bn_act_forward_grouped(y, bn, ACT_LRELU, 1)
+        groups.append(g)
+    return groups
+
+
+def _issue_order(heads):
+    """the heads' backward passes go widest first (stable)"""
+    return sorted(range(len(heads)), key=lambda i: -heads[i][1])
+
+
+def _row_modes(heads, n_rows, groups=()):
+    """The issue order of the heads' backward passes and, per head, how it writes its rows of
+    d feats: 0 = store (nobody has written them yet), 1 = accumulate (all of them are written).  A head writes at its
+    place in the issue order, except the heads of a `groups` entry (lists of head indices that share one data-gradient
+    launch), which all write behind the last of them.  Widest first, so that the row ranges of the reference's five heads
+    never overlap partially."""
+    heads = [Head(*h) for h in heads]
+    order = _issue_order(heads)
+    pos = {i: k for k, i in enumerate(order)}
+    at = dict(pos)
+    for g in groups:
+        for i in g:
+            at[i] = max(pos[j] for j in g)
+    written, modes = [], {}
+    for i in sorted(order, key=lambda i: (at[i], pos[i])):
+        r0, r1 = heads[i].row0, heads[i].row0 + heads[i].rows
+        inside = any(a <= r0 and r1 <= b for a, b in written)
+        if not inside:
+            assert all(r1 <= a or b <= r0 for a, b in written), 'partially overlapping head rows'
+            written.append((r0, r1))
+        modes[i] = 1 if inside else 0
+    covered = sorted(written)
+    assert covered and covered[0][0] == 0 and covered[-1][1] == n_rows and \
+        all(covered[k][1] == covered[k + 1][0] for k in range(len(covered) - 1)), 'rows without a head'
+    return order, modes
+
+
+def _logits_bwd(dt, h, o, prob, dprob, dh, need_p, rows, K, accumulate):
+    call('sba_logits_bwd', dt, _p(h), _p(o.weight), _p(prob), _p(dprob), _p(dh),
+         _p(param_grad(o.weight)) if need_p else None, _p(param_grad(o.bias)) if need_p else None,
+         rows, K, accumulate, _stream())
 
 
 class DHeadsFn(torch.autograd.Function):
@@ -1421,7 +1482,7 @@ class DHeadsFn(torch.autograd.Function):
     heads (model.py:590-592) and the weighted BCE sum (losses.py:141-158 for the discriminator update,
     :169-178 for the generator term).
 
-    `heads` = tuple of (row0, rows, cond_row0 | None, target, weight, segment): the head reads feats[row0:row0+rows]
+    `heads` = tuple of Head(row0, rows, cond_row0 | None, target, weight, segment): the head reads feats[row0:row0+rows]
     (and cond[cond_row0:cond_row0+rows] when conditional); they are evaluated in the order given (the reference's
     call order, which fixes the order of the jointConv BatchNorm running-statistic updates) and summed in `segment`
     order (the reference's order of the terms of errD / g_loss).  The same kernels as the per-head Functions
@@ -1440,72 +1501,45 @@ class DHeadsFn(torch.autograd.Function):
         cnet, unet = netD.COND_DNET, netD.UNCOND_DNET
         if cond is not None:
             cond = cond.reshape(-1, cnet.ef_dim).float().contiguous()
-        sizes = [0] * len(heads)
-        for (r0, rows, c0, tgt, wt, seg) in heads:
-            sizes[seg] = rows
+        sizes, targets, weights = [0] * len(heads), [0.] * len(heads), [0.] * len(heads)
+        for hd in heads:
+            sizes[hd.segment], targets[hd.segment], weights[hd.segment] = hd.rows, hd.target, hd.weight
         offs = [0]
         for s in sizes:
             offs.append(offs[-1] + s)
         prob = torch.empty(offs[-1], dtype=torch.float32, device=dev)
-        tape = []
-        # The conditional heads of one term (real / fake / wrong pairs, losses.py:143-149) share jointConv's weights: their
-        # inputs go into ONE tensor, one conv / data-gradient / weight-gradient launch serves all of them (M = 944 rows at
-        # B = 20 instead of three GEMM-like launches of 320 / 320 / 304 rows, each with its own K split + finishing launch);
-        # BatchNorm stays per head, in the reference's call order (batch statistics and running-statistic updates of three
-        # separate module calls).
-        cond_idx = [i for i, hd in enumerate(heads) if hd[2] is not None]
-        grouped = GROUP_COND_HEADS and len(cond_idx) >= 2 and cnet.jointConv._layer().bn.training
-        xin_all = y_all = None
-        slices = {}
-        if grouped:
-            layer = cnet.jointConv._layer()
-            E = cond.shape[1]
-            total = sum(heads[i][1] for i in cond_idx)
-            xin_all = empty_act(total, C + E, 4, 4, feats)
-            off = 0
-            for i in cond_idx:
-                r0, rows, c0 = heads[i][0], heads[i][1], heads[i][2]
-                call('sba_cond_cat_fwd', dt, _p(feats[r0:r0 + rows]), _p(cond[c0:c0 + rows]), _p(xin_all[off:off + rows]),
-                     rows, C, E, _stream())
-                slices[i] = (off, rows)
-                off += rows
-            y_all, _ = conv_forward(xin_all, layer.pw, '3x3', want_stats=False, pre_bn=True)
-        for hi, (r0, rows, c0, tgt, wt, seg) in enumerate(heads):
-            h = feats[r0:r0 + rows]
-            pslice = prob[offs[seg]:offs[seg] + rows]
-            if c0 is not None and grouped:
-                layer = cnet.jointConv._layer()
-                off = slices[hi][0]
-                xin, y = xin_all[off:off + rows], y_all[off:off + rows]
-                hc, st = bn_act_forward_grouped(y, layer.bn, ACT_LRELU, 1)      # (grouped: the BatchNorm is in training mode)
-                o = cnet.outlogits[0]
-                call('sba_logits_fwd', dt, _p(hc), _p(o.weight), _p(o.bias), _p(pslice), rows, K, _stream())
-                tape.append((xin, y, st, hc))
-            elif c0 is not None:
-                layer = cnet.jointConv._layer()
-                E = cond.shape[1]
-                xin = empty_act(rows, C + E, 4, 4, feats)
-                call('sba_cond_cat_fwd', dt, _p(h), _p(cond[c0:c0 + rows]), _p(xin), rows, C, E, _stream())
-                y, stats = conv_forward(xin, layer.pw, '3x3', want_stats=layer.bn.training, pre_bn=True)
-                hc, st = bn_act_forward(y, stats, layer.bn, ACT_LRELU)
-                o = cnet.outlogits[0]
-                call('sba_logits_fwd', dt, _p(hc), _p(o.weight), _p(o.bias), _p(pslice), rows, K, _stream())
-                tape.append((xin, y, st, hc))
+        layer = cnet.jointConv._layer() if any(hd.cond_row0 is not None for hd in heads) else None
+        groups = _cond_groups(heads, layer.bn) if layer is not None else []
+        group_of = {i: g for g in groups for i in g.heads}
+        tape = [None] * len(heads)
+        for hi, hd in enumerate(heads):
+            if hd.cond_row0 is None:
+                x, o = feats[hd.row0:hd.row0 + hd.rows], unet.outlogits[0]
             else:
-                o = unet.outlogits[0]
-                call('sba_logits_fwd', dt, _p(h), _p(o.weight), _p(o.bias), _p(pslice), rows, K, _stream())
-                tape.append(None)
-        targets = [0.] * len(heads)
-        weights = [0.] * len(heads)
-        for (r0, rows, c0, tgt, wt, seg) in heads:
-            targets[seg], weights[seg] = tgt, wt
+                g = group_of[hi]
+                if hi == g.heads[0]:        # the inputs of the group's heads, then its one conv launch
+                    E = cond.shape[1]
+                    g.xin = empty_act(sum(heads[i].rows for i in g.heads), C + E, 4, 4, feats)
+                    off = 0
+                    for i in g.heads:
+                        r0, rows, c0 = heads[i][:3]
+                        call('sba_cond_cat_fwd', dt, _p(feats[r0:r0 + rows]), _p(cond[c0:c0 + rows]),
+                             _p(g.xin[off:off + rows]), rows, C, E, _stream())
+                        g.off[i] = off
+                        off += rows
+                    g.y, g.stats = conv_forward(g.xin, layer.pw, '3x3', want_stats=g.want_stats, pre_bn=True)
+                y = g.y[g.off[hi]:g.off[hi] + hd.rows]
+                x, st = g.bn_forward(y, g.stats)
+                tape[hi] = (y, st, x)
+                o = cnet.outlogits[0]
+            pslice = prob[offs[hd.segment]:offs[hd.segment] + hd.rows]
+            call('sba_logits_fwd', dt, _p(x), _p(o.weight), _p(o.bias), _p(pslice), hd.rows, K, _stream())
         meta = _bce_meta(offs, targets, weights, dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dprob = torch.empty_like(prob)
         call('sba_bce_multi', _p(prob), _p(meta[0]), _p(meta[1]), _p(meta[2]), len(heads), _p(loss), _p(dprob),
              _stream())
-        ctx.netD, ctx.heads, ctx.offs, ctx.tape = netD, heads, offs, tape
-        ctx.grouped = (xin_all, y_all, slices) if grouped else None
+        ctx.netD, ctx.heads, ctx.offs, ctx.tape, ctx.groups = netD, heads, offs, tape, groups
         ctx.has_cond = cond is not None
         ctx.cond_shape = None if cond is None else tuple(cond.shape)
         ctx.save_for_backward(feats, prob, dprob)
@@ -1514,7 +1548,7 @@ class DHeadsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         feats, prob, dprob = ctx.saved_tensors
-        netD, heads, offs = ctx.netD, ctx.heads, ctx.offs
+        netD, heads, offs, groups = ctx.netD, ctx.heads, ctx.offs, ctx.groups
         cnet, unet = netD.COND_DNET, netD.UNCOND_DNET
         dt = _dt(feats)
         C = feats.shape[1]
@@ -1525,83 +1559,46 @@ class DHeadsFn(torch.autograd.Function):
         need_p = any(ctx.needs_input_grad[4:])
         dfeats = torch.empty_like(feats) if need_feats else None
         dcond = torch.zeros(ctx.cond_shape, dtype=torch.float32, device=feats.device) if need_cond else None
-        # a head whose rows nobody has written yet stores, one whose rows are all written accumulates; widest
-        # heads first, so that the row ranges of the reference's five heads never overlap partially
-        order = sorted(range(len(heads)), key=lambda i: -heads[i][1])
-        written = []
+        # (a term without a gradient to feats may hold any subset of the heads: nothing to cover)
+        order, modes = _row_modes(heads, feats.shape[0], [grp.heads for grp in groups]) if need_feats \
+            else (_issue_order(heads), None)
+        group_of = {i: grp for grp in groups for i in grp.heads}
+        issued = {grp: [j for j in order if j in grp.off] for grp in groups}      # a group's heads in issue order
+        dy = {grp: torch.empty(grp.y.shape, dtype=_act_dtype(grp.y), device=grp.y.device, memory_format=CL)
+              for grp in groups}
 
-        def mode(r0, rows):
-            inside = any(a <= r0 and r0 + rows <= b for a, b in written)
-            if not inside:
-                assert all(r0 + rows <= a or b <= r0 for a, b in written), 'partially overlapping head rows'
-                written.append((r0, r0 + rows))
-            return 1 if inside else 0
+        def dh_rows(i):
+            """(head i's rows of d feats | a scratch tensor when nobody wants them, store / accumulate)"""
+            rows = slice(heads[i].row0, heads[i].row0 + heads[i].rows)
+            return (dfeats[rows], modes[i]) if need_feats else (torch.empty_like(feats[rows]), 0)
 
-        dy_all = None
-        if ctx.grouped is not None:
-            xin_all, y_all, slices = ctx.grouped
-            dy_all = torch.empty(y_all.shape, dtype=_act_dtype(y_all), device=y_all.device, memory_format=CL)
         for i in order:
-            r0, rows, c0, tgt, wt, seg = heads[i]
-            ps, ds = prob[offs[seg]:offs[seg] + rows], d[offs[seg]:offs[seg] + rows]
-            if c0 is not None and dy_all is not None:
-                # grouped conditional heads: this head's BatchNorm backward into its rows of dy_all; the conv gradients
-                # follow once, below
-                xin, y, st, hc = ctx.tape[i]
-                layer = cnet.jointConv._layer()
-                o = cnet.outlogits[0]
-                dhc = torch.empty_like(hc)
-                call('sba_logits_bwd', dt, _p(hc), _p(o.weight), _p(ps), _p(ds), _p(dhc),
-                     _p(param_grad(o.weight)) if need_p else None, _p(param_grad(o.bias)) if need_p else None,
-                     rows, K, 0, _stream())
-                off = slices[i][0]
-                bn_act_backward(y, dhc, st, layer.bn, ACT_LRELU, need_p, out=dy_all[off:off + rows])
+            hd = heads[i]
+            ps, ds = prob[offs[hd.segment]:offs[hd.segment] + hd.rows], d[offs[hd.segment]:offs[hd.segment] + hd.rows]
+            if hd.cond_row0 is None:
+                if need_feats or need_p:
+                    dh, acc = dh_rows(i)
+                    _logits_bwd(dt, feats[hd.row0:hd.row0 + hd.rows], unet.outlogits[0], ps, ds, dh, need_p, hd.rows, K,
+                                acc)
                 continue
-            if c0 is None:
-                o = unet.outlogits[0]
-                if not (need_feats or need_p):
-                    continue
-                dh = dfeats[r0:r0 + rows] if need_feats else torch.empty_like(feats[r0:r0 + rows])
-                call('sba_logits_bwd', dt, _p(feats[r0:r0 + rows]), _p(o.weight), _p(ps), _p(ds), _p(dh),
-                     _p(param_grad(o.weight)) if need_p else None, _p(param_grad(o.bias)) if need_p else None,
-                     rows, K, mode(r0, rows) if need_feats else 0, _stream())
-                continue
-            xin, y, st, hc = ctx.tape[i]
-            layer = cnet.jointConv._layer()
-            o = cnet.outlogits[0]
+            # a conditional head: back to its rows of the group's dy; behind the group's last head the conv gradients, once
+            grp, layer = group_of[i], cnet.jointConv._layer()
+            y, st, hc = ctx.tape[i]
             dhc = torch.empty_like(hc)
-            call('sba_logits_bwd', dt, _p(hc), _p(o.weight), _p(ps), _p(ds), _p(dhc),
-                 _p(param_grad(o.weight)) if need_p else None, _p(param_grad(o.bias)) if need_p else None,
-                 rows, K, 0, _stream())
-            dy = bn_act_backward(y, dhc, st, layer.bn, ACT_LRELU, need_p)
+            _logits_bwd(dt, hc, cnet.outlogits[0], ps, ds, dhc, need_p, hd.rows, K, 0)
+            bn_act_backward(y, dhc, st, layer.bn, ACT_LRELU, need_p, out=dy[grp][grp.off[i]:grp.off[i] + hd.rows])
+            if i != issued[grp][-1]:
+                continue
             if need_p:
-                conv_wgrad_overlapped(xin, dy, layer.conv.weight, '3x3')
+                conv_wgrad_overlapped(grp.xin, dy[grp], layer.conv.weight, '3x3')
             if need_feats or need_cond:
-                dxin = conv_dgrad(dy, layer.pw, '3x3', (4, 4))
-                E = xin.shape[1] - C
-                dh = dfeats[r0:r0 + rows] if need_feats else torch.empty_like(feats[r0:r0 + rows])
-                call('sba_cond_cat_bwd', dt, _p(dxin), _p(dh), _p(dcond[c0:c0 + rows]) if need_cond else None,
-                     rows, C, E, mode(r0, rows) if need_feats else 0, _stream())
-        if dy_all is not None:
-            layer = cnet.jointConv._layer()
-            if need_p:
-                conv_wgrad_overlapped(xin_all, dy_all, layer.conv.weight, '3x3')
-            if need_feats or need_cond:
-                dxin_all = conv_dgrad(dy_all, layer.pw, '3x3', (4, 4))
-                E = xin_all.shape[1] - C
-                for i in order:
-                    r0, rows, c0, tgt, wt, seg = heads[i]
-                    if c0 is None:
-                        continue
-                    off = slices[i][0]
-                    dh = dfeats[r0:r0 + rows] if need_feats else torch.empty_like(feats[r0:r0 + rows])
-                    call('sba_cond_cat_bwd', dt, _p(dxin_all[off:off + rows]), _p(dh),
-                         _p(dcond[c0:c0 + rows]) if need_cond else None, rows, C, E,
-                         mode(r0, rows) if need_feats else 0, _stream())
-        if need_feats:
-            covered = sorted(written)
-            assert covered and covered[0][0] == 0 and covered[-1][1] == feats.shape[0] and \
-                all(covered[k][1] == covered[k + 1][0] for k in range(len(covered) - 1)), 'rows without a head'
+                dxin = conv_dgrad(dy[grp], layer.pw, '3x3', (4, 4))
+                E = grp.xin.shape[1] - C
+                for j in issued[grp]:
+                    r0, rows, c0 = heads[j][:3]
+                    dh, acc = dh_rows(j)
+                    call('sba_cond_cat_bwd', dt, _p(dxin[grp.off[j]:grp.off[j] + rows]), _p(dh),
+                         _p(dcond[c0:c0 + rows]) if need_cond else None, rows, C, E, acc, _stream())
         return (dfeats, dcond, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
 
 
@@ -1618,7 +1615,7 @@ def d_heads(netD, feats, cond, heads):
     if netD.UNCOND_DNET is not None:
         u = netD.UNCOND_DNET
         params += [u.outlogits[0].weight, u.outlogits[0].bias]
-    return DHeadsFn.apply(feats, cond, netD, tuple(heads), *params)
+    return DHeadsFn.apply(feats, cond, netD, tuple(Head(*h) for h in heads), *params)
 
 
 class KLFn(torch.autograd.Function):
@@ -1639,7 +1636,7 @@ class KLFn(torch.autograd.Function):
         return dmu * g, dlv * g
 
 
-DAMSM_MFMA = os.environ.get('SBA_DAMSM_MFMA', '1') != '0'
+DAMSM_MFMA = True       # the words loss on the matrix cores where the shape allows (False: the f32 kernels)
 
 
 def _damsm_prep(feat, words, cap_lens, B, nef, R, L):

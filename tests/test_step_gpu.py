@@ -162,25 +162,38 @@ def test_fused_heads_equal_the_per_head_functions(dev, b_jcu):
     sent0 = fill.unit((B, 256), 962).to(dev)
     ones, zeros = torch.ones(B, device=dev), torch.zeros(B, device=dev)
 
+    def per_head(net, fake, sent, term):
+        """the term as the reference composes it (losses.py:136-161, 168-186), one autograd Function per head"""
+        if term == 'G':
+            feats = net(fake)
+            if b_jcu:
+                return ops.BCEMultiFn.apply((1., 1.), (1., 1.), net.UNCOND_DNET(feats), net.COND_DNET(feats, sent))
+            return ops.BCEMultiFn.apply((1.,), (1.,), net.COND_DNET(feats, sent))
+        feats = net(torch.cat((real, fake.detach()), 0), groups=2)
+        real_features, fake_features = feats[:B], feats[B:]
+        cond_real = net.COND_DNET(real_features, sent)
+        cond_fake = net.COND_DNET(fake_features, sent)
+        cond_wrong = net.COND_DNET(real_features[:(B - 1)], sent[1:B])
+        if b_jcu:
+            real_logits = net.UNCOND_DNET(real_features)
+            fake_logits = net.UNCOND_DNET(fake_features)
+            return ops.BCEMultiFn.apply((1., 1., 0., 0., 0.), (.5, .5, 1. / 3, 1. / 3, 1. / 3),
+                                        real_logits, cond_real, fake_logits, cond_fake, cond_wrong)
+        return ops.BCEMultiFn.apply((1., 0., 0.), (1., .5, .5), cond_real, cond_fake, cond_wrong)
+
     def run(fused, term):
         net = model.D_NET64(b_jcu=b_jcu)
         net.load_state_dict(P)
         net.to(dev).train()
         fake = fill.uniform((B, 3, S, S), 961).to(dev).requires_grad_(True)
         sent = sent0.clone().requires_grad_(True)
-        L.FUSED_HEADS = fused
-        try:
-            if term == 'D':
-                err = L.discriminator_loss(net, real, fake, sent, ones, zeros)
-            else:
-                feats = net(fake)
-                err = (ops.d_heads(net, feats, sent, ((0, B, 0, 1., 1., 1), (0, B, None, 1., 1., 0)) if b_jcu
-                                   else ((0, B, 0, 1., 1., 0),)) if fused else
-                       (ops.BCEMultiFn.apply((1., 1.), (1., 1.), net.UNCOND_DNET(feats), net.COND_DNET(feats, sent))
-                        if b_jcu else ops.BCEMultiFn.apply((1.,), (1.,), net.COND_DNET(feats, sent))))
-            err.backward()
-        finally:
-            L.FUSED_HEADS = True
+        if not fused:
+            err = per_head(net, fake, sent, term)
+        elif term == 'D':
+            err = L.discriminator_loss(net, real, fake, sent, ones, zeros)
+        else:
+            err = ops.d_heads(net, net(fake), sent, L.g_term_heads(B, b_jcu))
+        err.backward()
         ops.join_wgrads()
         torch.cuda.synchronize()
         out = {'loss': err.detach().reshape(1), 'dsent': sent.grad}

@@ -13,6 +13,7 @@ inputs from oracle/fill.py, and only numeric outputs are written.
     SBA_LIB_PATH=<parent build> python tools/make_golden.py igemm_plan     # the kernel-choice recording
     SBA_LIB_PATH=<recorder build> python tools/make_golden.py wgrad_plan   # ... of the weight gradient
     SBA_ENCODER_DRIVER=<module> python tools/make_golden.py encoder_trace  # the Inception driver's launches (needs a GPU)
+    python tools/make_golden.py heads_trace        # the loss heads' launches: run it in the PARENT commit's tree (needs a GPU)
 """
 import os
 import sys
@@ -459,6 +460,24 @@ def gen_encoder_trace():
                                                          os.path.getsize(T.GOLDEN)))
 
 
+def gen_heads_trace():
+    """heads_trace.jsonl: every launch of the loss heads in the cases of tests/test_heads_trace_gpu.py, from code that is
+    NOT the code under test: run this in a checkout of the parent commit (with its own library built) into which this file
+    and tests/test_heads_trace_gpu.py have been copied -- the driver of the test uses only API that commit has -- and
+    copy the fixture back."""
+    import json
+    sys.path[:0] = [os.path.join(ROOT, 'sba-gan_amd'), os.path.join(ROOT, 'tests')]
+    import test_heads_trace_gpu as T
+    from sbagan import ops
+    traces = [(name, T.run_case(name, torch.device('cuda:0'))) for name in sorted(T.CASES)]
+    with open(T.GOLDEN, 'w') as f:
+        for name, trace in traces:
+            for entry, args in trace:
+                f.write(json.dumps([name, entry, args], separators=(',', ':')) + '\n')
+    print('heads_trace.jsonl from %s: %s, %d bytes' % (ops.__file__, {name: len(t) for name, t in traces},
+                                                       os.path.getsize(T.GOLDEN)))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     what = sys.argv[1:] or ['units', 'step_tiny', 'step_full']
@@ -476,6 +495,11 @@ def main():
     if 'encoder_trace' in what:
         gen_encoder_trace()
         what = [w for w in what if w != 'encoder_trace']
+        if not what:
+            return
+    if 'heads_trace' in what:
+        gen_heads_trace()
+        what = [w for w in what if w != 'heads_trace']
         if not what:
             return
     ref = load_reference()
