@@ -4,7 +4,10 @@ classes) against the CPU oracle or a plain torch fp32 CPU reference of the same 
 Tolerances (stated per dtype):
   float32 path (exact f32 MFMA): elementwise rtol 2e-4 / atol 2e-5 unless noted;
   bfloat16 path (bf16 storage + MFMA, f32 accumulate): relative L2 error <= 2e-2 per tensor
-  (bf16 has an 8-bit mantissa; elementwise bounds are not meaningful).
+  (bf16 has an 8-bit mantissa; fixed elementwise tolerances are not meaningful).  The raw convolutions are held
+  tighter (test_conv_fwd_dgrad_wgrad): y and dx element by element to one bf16 rounding of the float64 result plus
+  1e-5 x the contraction of the absolute values (tests/conv_ref.py), the f32 weight gradient to the f32 tolerances
+  and to 1e-5 x the sum of the absolute products.
 """
 import numpy as np
 import pytest
@@ -13,6 +16,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import conv_ref as CR  # noqa: E402
 from helpers import rel_l2  # noqa: E402
 from oracle import fill  # noqa: E402
 from oracle import sbagan_oracle as O  # noqa: E402
@@ -49,6 +53,26 @@ def close(got, ref, dt, name='', scale=1.0):
         err = (got - ref).abs()
         bound = scale * (t['atol'] + t['rtol'] * ref.abs()) + 1e-6 * float(ref.abs().max())
         assert bool((err <= bound).all()), '%s: max err %.3e' % (name, float(err.max()))
+
+
+def elem_bound(got, ref, A, name, u=CR.U_BF16):
+    """a bf16 convolution output element by element (tests/conv_ref.py): one rounding of an f32 accumulator,
+    |got - ref| <= u |ref| + c A with A the same contraction on absolute values"""
+    got, ref, A = got.detach().double().cpu(), ref.detach().double().cpu(), A.detach().double().cpu()
+    assert got.shape == ref.shape == A.shape, (name, got.shape, ref.shape, A.shape)
+    assert bool(torch.isfinite(got).all()), name
+    worst = float(((got - ref).abs() / (u * ref.abs() + CR.C_ACC * A).clamp(min=1e-300)).max())
+    print('%-34s elementwise: worst err / bound = %.3f' % (name, worst))
+    assert worst <= 1.0, '%s: worst err / bound = %.3f' % (name, worst)
+
+
+def sums_bound(got, ref, A, name):
+    """an f32 sum of products (weight gradient): |got - ref| <= c x the float64 sum of the absolute products"""
+    got, ref, A = got.detach().double().cpu(), ref.detach().double().cpu(), A.detach().double().cpu()
+    assert got.shape == ref.shape == A.shape, (name, got.shape, ref.shape, A.shape)
+    worst = float(((got - ref).abs() / A.clamp(min=1e-30)).max())
+    print('%-34s f32 sums: worst |err| / sum |products| = %.2e' % (name, worst))
+    assert worst <= CR.C_ACC, '%s: %.3e > %.0e' % (name, worst, CR.C_ACC)
 
 
 def act(x, dt, dev):
@@ -146,12 +170,30 @@ def test_conv_fwd_dgrad_wgrad(dev, dt, case):
     dyr = rounded(dy, dt).double()
     gx, gw = torch.autograd.grad(yref, [xr, wr], dyr)
 
+    bf = dt == torch.bfloat16
+    if bf:
+        # the same contractions on absolute values: the scale of the f32 partial sums (tests/conv_ref.py)
+        xb, wb = xr.detach().abs().requires_grad_(True), wr.detach().abs().requires_grad_(True)
+        ya = torch_conv(xb, wb, kind)
+        gxa, gwa = torch.autograd.grad(ya, [xb, wb], dyr.abs())
+        ya = ya.detach()
+
+    def dw_close(got, name):
+        close(got, gw, dt, name)
+        if bf:
+            # f32 accumulation of bf16-rounded inputs: the only error is the summation order, whatever the storage
+            # type of the activations -- held to the f32 tolerances and to c x the sum of the absolute products
+            close(got, gw, torch.float32, name + ' at the f32 tolerances')
+            sums_bound(got, gw, gwa, name)
+
     wp = torch.nn.Parameter(w.to(dev).contiguous(memory_format=torch.channels_last))
     pw = ops.PackedWeight(wp)
     xa = act(x, dt, dev)
     y, stats = ops.conv_forward(xa, pw, kind)
     torch.cuda.synchronize()
     close(y, yref, dt, 'y')
+    if bf:
+        elem_bound(y, yref, ya, 'y')
     # BN statistics of the f32 accumulators
     stats = stats.sum(0)                # add the statistics slots up
     close(stats[:Cout], yref.sum((0, 2, 3)), torch.float32, 'sum', scale=30 if dt == torch.float32 else 2000)
@@ -159,10 +201,26 @@ def test_conv_fwd_dgrad_wgrad(dev, dt, case):
     dya = act(dy, dt, dev)
     dx = ops.conv_dgrad(dya, pw, kind, (H, W))
     close(dx, gx, dt, 'dx')
+    if bf and kind != '3x3up':
+        elem_bound(dx, gx, gxa, 'dx')
+    elif bf:
+        # behind the nearest x2 upsample the data gradient is ONE 4x4 / stride-2 conv over dy whose operand holds SUMS of
+        # up to four weights (sba_pack_weight mode 3), formed in f32 from the master weights and rounded once: the
+        # storage-rounded operand of this launch is that tensor, not the per-tap rounded weights behind gx.  So the
+        # operand is pinned at one rounding of the float64 tap sums, and dx at the elementwise bound on the operand.
+        wd = pw.dgrad(dt, kind).float().cpu().view(Cin, 16, Cout).double()
+        S = [[2], [1, 2], [0, 1], [0]]
+        wm = w.double()                                                     # [Cout][Cin][kh][kw]
+        wsum = torch.stack([sum(wm[:, :, kh, kw] for kh in S[t // 4] for kw in S[t % 4]).t() for t in range(16)], 1)
+        wabs = torch.stack([sum(wm[:, :, kh, kw].abs() for kh in S[t // 4] for kw in S[t % 4]).t() for t in range(16)], 1)
+        assert bool(((wd - wsum).abs() <= CR.U_BF16 * wsum.abs() + 2.0 ** -22 * wabs).all()), 'mode-3 operand'
+        g4 = CR.geom(N, 2 * H, 2 * W, Cout, H, W, Cin, [(t // 4 - 1, t % 4 - 1) for t in range(16)], sy=2)
+        dyn = dyr.permute(0, 2, 3, 1).contiguous()
+        elem_bound(dx.permute(0, 2, 3, 1), CR.contract(dyn, wd, g4), CR.contract(dyn.abs(), wd.abs(), g4), 'dx (4x4 collapse)')
     ops.conv_wgrad(xa, dya, wp, kind)
     ops.conv_wgrad(xa, dya, wp, kind)        # accumulates: twice -> 2x
     torch.cuda.synchronize()
-    close(wp.grad * 0.5, gw, dt, 'dw')
+    dw_close(wp.grad * 0.5, 'dw')
     # a parameter whose cleared gradient buffer is tracked (trainer.FlatParams): the first launch may STORE
     # (sba_conv_geom.first_write), the second accumulates; a clear + epoch bump re-arms the store
     wq = torch.nn.Parameter(w.to(dev).contiguous(memory_format=torch.channels_last))
@@ -172,12 +230,12 @@ def test_conv_fwd_dgrad_wgrad(dev, dt, case):
     assert wq._sba_wepoch == 1
     ops.conv_wgrad(xa, dya, wq, kind)
     torch.cuda.synchronize()
-    close(wq.grad * 0.5, gw, dt, 'dw (first write + accumulate)')
+    dw_close(wq.grad * 0.5, 'dw (first write + accumulate)')
     wq.grad.zero_()
     wq._sba_gepoch[0] += 1
     ops.conv_wgrad(xa, dya, wq, kind)
     torch.cuda.synchronize()
-    close(wq.grad, gw, dt, 'dw (first write after a clear)')
+    dw_close(wq.grad, 'dw (first write after a clear)')
 
 
 @pytest.mark.parametrize('dt', DTYPES)
