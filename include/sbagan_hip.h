@@ -688,6 +688,32 @@ int sba_fid_accumulate(const float* x, int n, int D, int ldx, double* sum, doubl
 int sba_fid_finalize(const double* sum, const double* gram, int64_t n, int D, double* mu, double* sigma, double* trace,
                      void* stream);
 
+/* k-nearest-neighbour manifold metrics (evaluation; sbagan/prdc.py): all-pairs squared distances between
+ * two sets of f32 feature rows (unit column stride, row stride ld >= D floats, ld % 4 == 0, 16-byte aligned, D a positive
+ * multiple of 64) with a row-wise selection fused behind them; the na x nb matrix is never written.  All distance
+ * arithmetic is float64:
+ *     d2(i, j) = max((na[i] + nb[j]) - 2 g(i, j), 0)
+ * g the dot product on the f64 matrix instruction over the feature axis in ascending order (the f32 values are widened in
+ * registers, every product is exact), na / nb the squared norms in f64 in one fixed order.  d2(i, j) has the same bits
+ * whichever tile or column split computed it, and d2(i, j) == d2(j, i) bitwise when both sets are the same rows.
+ * sba_prdc_knn_radius: radius2[i] = the k-th smallest d2(i, j) over the OTHER rows j != i of x [n][D]; self is excluded
+ *   by index, not by value, so a duplicate row counts at distance 0.  1 <= k <= 8, n >= k + 1.
+ * sba_prdc_ball_counts: in_b[i] = #{j : d2(i, j) <= radius_b[j]} and in_own[i] = #{j : d2(i, j) <= radius_a[i]} over the
+ *   rows j of b [nb][D], for every row i of a [na][D], as int32.  Either radius vector may be null: its count is then not
+ *   written (and its output pointer is ignored); one of them must be given, and a given vector needs its output.
+ * splits: the B range is cut into that many parts of whole 64-row tiles (one workgroup per 64 A rows and part), capped at
+ *   32 and at the number of tiles; 0 = the library's choice (enough parts for 512 workgroups).  With more than one part
+ *   the partial lists / counts go to `ws` (8-byte aligned, at least sba_prdc_workspace_bytes(na, nb, splits) bytes; -1
+ *   for bad arguments, 0 when one part is used and ws may be null) and a second small launch merges them in part order.
+ *   Results are bit-identical for every split count.  No atomics, no memset, no allocation.
+ * SBA_E_ARG before any launch on a null pointer, bad D, k, n, strides, alignment, splits or a workspace too small. */
+int64_t sba_prdc_workspace_bytes(int na, int nb, int splits);
+int sba_prdc_knn_radius(const float* x, int n, int D, int ld, int k, int splits, double* radius2, void* ws,
+                        int64_t ws_bytes, void* stream);
+int sba_prdc_ball_counts(const float* a, int na, int lda, const float* b, int nb, int ldb, int D, const double* radius_a,
+                         const double* radius_b, int splits, int32_t* in_b, int32_t* in_own, void* ws, int64_t ws_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

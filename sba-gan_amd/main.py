@@ -4,8 +4,8 @@
 
 cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_example(example_filenames.txt).
 --fused_inference, --r_precision R (sampling also writes r_precision.json), --attention_maps (the attention-map
-overlay images, sbagan/visualize.py) and --fid [--fid_stats PATH] (sampling also writes fid.json, sbagan/fid.py) are this
-project's additions."""
+overlay images, sbagan/visualize.py), --fid [--fid_stats PATH] (sampling also writes fid.json, sbagan/fid.py) and --prdc K
+(sampling also writes prdc.json: precision, recall, density and coverage, sbagan/prdc.py) are this project's additions."""
 import os
 import sys
 import time
@@ -82,6 +82,7 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo.attention_maps = bool(getattr(args, 'attention_maps', False))
     algo.fid = bool(getattr(args, 'fid', False))
     algo.fid_stats = getattr(args, 'fid_stats', None)
+    algo.prdc = int(getattr(args, 'prdc', 0))
     start_t = time.time()
     if training:
         algo.train()

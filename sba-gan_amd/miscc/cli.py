@@ -1,6 +1,6 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
-    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]
+    --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
     [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
@@ -27,6 +27,13 @@ def _r_precision(text):
     return r
 
 
+def _prdc(text):
+    k = int(text)
+    if k < 0 or k > 8:
+        raise argparse.ArgumentTypeError('K must be 0 (off) or a neighbour count from 1 to 8')
+    return k
+
+
 def options(what, default_cfg, argv=None, bert=False):
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
@@ -51,6 +58,11 @@ def options(what, default_cfg, argv=None, bert=False):
     ap.add_argument('--fid_stats', dest='fid_stats', type=str, default=None, metavar='PATH',
                     help='with --fid: an .npz of the real images\' statistics; read instead of the real pass when it '
                          'exists, written after the run when it does not')
+    ap.add_argument('--prdc', dest='prdc', type=_prdc, default=0, metavar='K',
+                    help='sampling: also take precision, recall, density and coverage (the K-nearest-neighbour manifold '
+                         'metrics, sbagan.prdc) between the real images of the split and the generated ones on the same '
+                         'trunk features as --fid and write prdc.json; 0 = off, K from 1 to 8, 5 = the usual setting.  '
+                         'On this project\'s own trunk and compute dtype: not comparable with published numbers')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

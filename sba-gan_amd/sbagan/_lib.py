@@ -146,6 +146,8 @@ SIGNATURES = {
     'sba_vis_compose': [P, I, I, I, I, I, I, I, P, P, P, P, I, P, I, I, P, I, I, P],
     'sba_fid_accumulate': [P, I, I, I, P, P, P],
     'sba_fid_finalize': [P, P, L, I, P, P, P, P],
+    'sba_prdc_knn_radius': [P, I, I, I, I, I, P, P, L, P],
+    'sba_prdc_ball_counts': [P, I, I, P, I, I, I, P, P, I, P, P, P, L, P],
     'sba_set_deterministic': [I, P, L],
     'sba_set_reduce_scratch': [P, L],
     'sba_det_reset': [],
@@ -172,6 +174,8 @@ lib.sba_damsm_prep_bytes.restype = c_int64
 lib.sba_damsm_prep_bytes.argtypes = [I, I, I, I]
 lib.sba_damsm_bwd_bytes.restype = c_int64
 lib.sba_damsm_bwd_bytes.argtypes = [I, I, I, I]
+lib.sba_prdc_workspace_bytes.restype = c_int64
+lib.sba_prdc_workspace_bytes.argtypes = [I, I, I]
 
 _ERR = {-1: 'SBA_E_ARG (unsupported shape/alignment/enum)', -2: 'SBA_E_LAUNCH (HIP launch failed)',
         -3: 'SBA_E_UNSUPPORTED (graph node kind the replayer cannot re-issue)'}

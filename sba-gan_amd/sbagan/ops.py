@@ -2119,3 +2119,88 @@ def fid_finalize(sum, gram, n):
     trace = torch.empty(1, dtype=torch.float64, device=sum.device)
     call('sba_fid_finalize', _p(sum), _p(gram), n, D, _p(mu), _p(sigma), _p(trace), _stream())
     return mu, sigma, trace
+
+
+# ----------------------------------------------------------------------------
+# evaluation: k-NN manifold metrics (sbagan/prdc.py)
+PRDC_MAX_K, PRDC_MAX_SPLITS = 8, 32
+
+
+def _prdc_rows(name, x, what, device=None, D=None):
+    """(n, D, row stride) of an f32 [n][D] feature-row tensor the prdc kernels can read"""
+    if not torch.is_tensor(x):
+        raise TypeError('%s: %s must be a tensor' % (name, what))
+    _need_gpu(x)
+    if x.dtype != torch.float32:
+        raise TypeError('%s: %s must be float32 (got %s)' % (name, what, x.dtype))
+    if x.dim() != 2:
+        raise ValueError('%s: %s must be 2-D (got %s)' % (name, what, tuple(x.shape)))
+    if device is not None and x.device != device:
+        raise ValueError('%s: %s is on %s, not on %s' % (name, what, x.device, device))
+    n, d = x.shape
+    if n < 1 or d < 64 or d % 64 or (D is not None and d != D):
+        raise ValueError('%s: %s must be [n >= 1][%s] (got %s)'
+                         % (name, what, D if D is not None else 'a positive multiple of 64', tuple(x.shape)))
+    ld = x.stride(0) if n > 1 else d        # (a single row has no meaningful row stride)
+    if x.stride(1) != 1 or ld < d or ld % 4:
+        raise ValueError('%s: %s needs unit column stride and a row stride >= D that is a multiple of 4 (got strides '
+                         '%s)' % (name, what, tuple(x.stride())))
+    if x.data_ptr() % 16:
+        raise ValueError('%s: %s must be 16-byte aligned' % (name, what))
+    return n, d, ld
+
+
+def _prdc_workspace(name, na, nb, splits, device):
+    """(workspace tensor or None, its size in bytes) for a launch over na x nb rows"""
+    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits <= PRDC_MAX_SPLITS:
+        raise ValueError('%s: splits must be an integer in [0, %d], 0 = the library\'s choice (got %r)'
+                         % (name, PRDC_MAX_SPLITS, splits))
+    nbytes = int(_lib.lib.sba_prdc_workspace_bytes(na, nb, splits))
+    if nbytes < 0:
+        raise ValueError('%s: no workspace size for %d x %d rows in %d splits' % (name, na, nb, splits))
+    if nbytes == 0:
+        return None, 0
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), nbytes
+
+
+def prdc_knn_radius(x, k, splits=0):
+    """radius2 [n] f64: the k-th smallest squared distance from every row of x [n][D] to the OTHER rows of x, in float64
+    (sba_prdc_knn_radius).  x: f32 rows on the device, unit column stride, row stride >= D and a multiple of 4, 16-byte
+    aligned, D % 64 == 0; 1 <= k <= 8, n >= k + 1.  Self is excluded by index: a duplicate row counts at distance 0.
+    splits: column parts of the launch (0 = the library's choice); the result has the same bits for every value.  The
+    workspace is a torch allocation on the current stream; no host sync.  Everything is checked before the launch:
+    TypeError for a dtype, ValueError for a shape, a stride, an alignment, k or splits."""
+    n, D, ld = _prdc_rows('prdc_knn_radius', x, 'x')
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= PRDC_MAX_K:
+        raise ValueError('prdc_knn_radius: k must be an integer in [1, %d] (got %r)' % (PRDC_MAX_K, k))
+    if n < k + 1:
+        raise ValueError('prdc_knn_radius: the %d-th neighbour needs at least %d rows (got %d)' % (k, k + 1, n))
+    ws, nbytes = _prdc_workspace('prdc_knn_radius', n, n, splits, x.device)
+    radius2 = torch.empty(n, dtype=torch.float64, device=x.device)
+    call('sba_prdc_knn_radius', _p(x), n, D, ld, k, splits, _p(radius2), _p(ws), nbytes, _stream())
+    return radius2
+
+
+def prdc_ball_counts(a, b, radius_a=None, radius_b=None, splits=0):
+    """(in_b, in_own), int32 [na] each or None (sba_prdc_ball_counts): for every row i of a [na][D],
+    in_b[i] = #{j : d2(i, j) <= radius_b[j]} and in_own[i] = #{j : d2(i, j) <= radius_a[i]} over the rows j of b [nb][D],
+    d2 the float64 squared distance of prdc_knn_radius.  radius_a [na] / radius_b [nb]: contiguous f64 on the rows'
+    device; a count whose radius vector is None is not computed and comes back as None (one of the two is needed).
+    Rows, splits, workspace and refusals as in prdc_knn_radius."""
+    name = 'prdc_ball_counts'
+    na, D, lda = _prdc_rows(name, a, 'a')
+    nb, _, ldb = _prdc_rows(name, b, 'b', a.device, D)
+    if radius_a is None and radius_b is None:
+        raise ValueError('%s: one of radius_a and radius_b is needed' % name)
+    for what, r, n in (('radius_a', radius_a, na), ('radius_b', radius_b, nb)):
+        if r is None:
+            continue
+        _vis_need(name, r, what, torch.float64, 1)
+        if r.shape[0] != n or r.device != a.device:
+            raise ValueError('%s: %s must be [%d] on %s (got %s on %s)' % (name, what, n, a.device, tuple(r.shape), r.device))
+    ws, nbytes = _prdc_workspace(name, na, nb, splits, a.device)
+    in_b = torch.empty(na, dtype=torch.int32, device=a.device) if radius_b is not None else None
+    in_own = torch.empty(na, dtype=torch.int32, device=a.device) if radius_a is not None else None
+    call('sba_prdc_ball_counts', _p(a), na, lda, _p(b), nb, ldb, D, _p(radius_a), _p(radius_b), splits, _p(in_b),
+         _p(in_own), _p(ws), nbytes, _stream())
+    return in_b, in_own

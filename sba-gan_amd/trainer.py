@@ -365,6 +365,19 @@ class condGANTrainer(object):
             print('Load real FID statistics from:', self.fid_stats)
         return evaluator
 
+    prdc = 0                    # --prdc K: sampling() also takes precision / recall / density / coverage at k = K
+    prdc_result = None          # the result dict of the last sampling() with prdc != 0
+
+    def _prdc_evaluator(self, image_encoder):
+        """sbagan.prdc.PRDC on the pooled trunk feature of `image_encoder` (an InceptionHIP)"""
+        from sbagan import ops
+        from sbagan.prdc import PRDC
+        if isinstance(self.prdc, bool) or not isinstance(self.prdc, int) or not 1 <= self.prdc <= ops.PRDC_MAX_K:
+            raise ValueError('prdc must be 0 (off) or a neighbour count from 1 to %d (got %r)'
+                             % (ops.PRDC_MAX_K, self.prdc))
+        dtype = str(ops.compute_dtype()).replace('torch.', '')
+        return PRDC(image_encoder.pooled_features, D=2048, k=self.prdc, dtype=dtype)
+
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
         root = self._output_root()
@@ -374,11 +387,14 @@ class condGANTrainer(object):
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
         evaluator = self._r_precision_evaluator(text_encoder) if self.r_precision else None
-        fid = fid_real = None
-        if self.fid:            # one image encoder serves both evaluators
+        fid = fid_real = prdc = None
+        if self.fid or self.prdc:       # one image encoder serves the three evaluators
             image_encoder = evaluator.image_encoder if evaluator is not None else self._load_image_encoder()
+        if self.fid:
             fid = self._fid_evaluator(image_encoder, split_dir)
             fid_real = not fid.is_loaded('real')
+        if self.prdc:
+            prdc = self._prdc_evaluator(image_encoder)
         noise = torch.empty(self._noise_shape(self.batch_size), device=self.device)
         made = set()
         for nbatch, data in enumerate(self.data_loader):
@@ -389,13 +405,18 @@ class condGANTrainer(object):
             last = fake_imgs[-1]
             if evaluator is not None:
                 evaluator.update(last, sent_emb, class_ids)
-            if fid is not None:
-                if evaluator is not None:       # R-precision has just run this batch through the trunk
-                    fid.update_features('fake', image_encoder.last_pooled)
-                else:
-                    fid.update('fake', last)
-                if fid_real:
-                    fid.update('real', real_imgs[-1])
+            if fid is not None or prdc is not None:     # each batch goes through the trunk once, for all of them
+                if evaluator is None:           # (R-precision has otherwise just run this batch through it)
+                    image_encoder.pooled_features(last)
+                for ev in (fid, prdc):
+                    if ev is not None:
+                        ev.update_features('fake', image_encoder.last_pooled)
+                if fid_real or prdc is not None:        # with cached FID statistics: encoded for PRDC alone
+                    real_feats = image_encoder.pooled_features(real_imgs[-1])
+                    if fid_real:
+                        fid.update_features('real', real_feats)
+                    if prdc is not None:
+                        prdc.update_features('real', real_feats)
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
         if evaluator is not None:
@@ -417,6 +438,14 @@ class condGANTrainer(object):
             if self.fid_stats and fid_real:
                 fid.save_real(self.fid_stats)
                 print('Save real FID statistics to:', self.fid_stats)
+        if prdc is not None:
+            self.prdc_evaluator = prdc
+            res = self.prdc_result = prdc.result()
+            print('PRDC (k = %d, %d real, %d generated images, %s trunk): precision %.4f  recall %.4f  density %.4f  '
+                  'coverage %.4f' % (res['k'], res['n_real'], res['n_fake'], res['dtype'], res['precision'],
+                                     res['recall'], res['density'], res['coverage']))
+            with open(os.path.join(out_dir, 'prdc.json'), 'w') as f:
+                json.dump(res, f, indent=1, sort_keys=True)
         return out_dir
 
     def gen_example(self, data_dic):
