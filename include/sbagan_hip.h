@@ -313,7 +313,8 @@ int sba_linear_fwd(const float* x, const float* w, const float* bias, float* y, 
  * taps = 1, Cin = K, glu = 1).  F2 % 16 == 0. */
 int sba_linear_glu_fwd(int dtype, const float* x, const float* wp, const float* bias, void* out, int B, int K,
                        int F2, void* stream);
-/* dx = dy*W (may be NULL); dw += dy^T x; dbias += sum dy (may be NULL). */
+/* dx = dy*W (may be NULL); dw += dy^T x (may be NULL); dbias += sum dy (may be NULL).  dbias is summed by the dw
+ * kernels: dbias without dw is refused (SBA_E_ARG), not ignored. */
 int sba_linear_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw,
                    float* dbias, int B, int K, int N, void* stream);
 /* CA_NET tail (model.py:281-294): h[B][4c] -> GLU -> mu|logvar; c = eps*exp(.5*logvar)+mu. */

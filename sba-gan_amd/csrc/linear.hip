@@ -513,6 +513,7 @@ extern "C" int sba_linear_fwd(const float* x, const float* w, const float* bias,
 extern "C" int sba_linear_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* dbias,
                               int B, int K, int N, void* stream) {
     if (!x || !w || !dy || B <= 0 || K <= 0 || N <= 0) return SBA_E_ARG;
+    if (dbias && !dw) return SBA_E_ARG;     // dbias is summed by the dW kernels: it has no launch of its own
     hipStream_t st = (hipStream_t)stream;
     if (B <= 32 && N % 4 == 0 && (N <= 2048 || (N % 32 == 0 && cdiv(N, 32) <= 65535))) {
         if (dw && dx && N <= 2048) {        // one launch for both (linear_bwd_xw_mfma_kernel)
