@@ -715,6 +715,25 @@ int sba_prdc_ball_counts(const float* a, int na, int lda, const float* b, int nb
                          const double* radius_b, int splits, int32_t* in_b, int32_t* in_own, void* ws, int64_t ws_bytes,
                          void* stream);
 
+/* Training batches from the device-resident image cache (sbagan/device_data.py): gather, crop, mirror,
+ * every scale of the image pyramid and the normalisation in ONE launch, bit-identical to the PIL data path.
+ * cache: all images back to back, each HWC uint8 [H_i][W_i][3]; offset[i] (int64): byte offset of image i; hw[i] = {H_i,
+ * W_i} (int32), i < N.  params[b] = {index, x1, y1, flip} (int32), b < B: the window [y1, y1 + T) x [x1, x1 + T) of image
+ * `index`, mirrored left-right when flip != 0.  out_l [B][3][T >> l][T >> l]: f32, planar, contiguous, l < levels.
+ *   level 0: out0 = lut[byte], lut a 256-entry f32 table (the host builds it with the torch operations of ToTensor and
+ *   Normalize, which is what makes the floats bit-equal);
+ *   levels 1, 2 (factors 2, 4): each resized FROM THE LEVEL-0 CROP by PIL's 8-bit BILINEAR resampling -- the horizontal
+ *   pass, the intermediate rounded to a byte, then the vertical pass; each pass byte = clip((2^21 + sum pixel k) >> 22,
+ *   0, 255) in int32 -- then lut[byte].  The coefficients come from the host: tab_l [T >> l][10] = {xmin, n, k0..k7}
+ *   (int32), windows clipped to the crop, n <= 8; a tap outside the crop window is never read.
+ * out1 / tab1 (out2 / tab2) are ignored when levels < 2 (< 3).  A params row whose index is outside [0, N) or whose
+ * window is not inside its image writes nothing for that image and reads nothing out of range.  One workgroup per 32 x 32
+ * level-0 tile, no atomics, no workspace.  SBA_E_ARG before any launch on a null pointer of a level in use, or unless
+ * 1 <= levels <= 3, 4 <= T <= 1024, T % (1 << (levels - 1)) == 0, 1 <= B <= 65535, N >= 1. */
+int sba_batch_pyramid(const uint8_t* cache, const int64_t* offset, const int32_t* hw, int N, const int32_t* params, int B,
+                      int T, int levels, const int32_t* tab1, const int32_t* tab2, const float* lut, float* out0,
+                      float* out1, float* out2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

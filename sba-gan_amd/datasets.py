@@ -56,21 +56,57 @@ def prepare_data(batch):
     return [images, captions.to(device), lengths.to(device), class_ids.index_select(0, order).numpy(), keys]
 
 
-def _crop_around(img, box):
-    """square window of 1.5 x the longer side of box = (x, y, w, h), centred on the box, clipped to the image"""
+class PreparedBatch(list):
+    """what prepare_data returns, made by a loader that prepares its batches itself (sbagan.device_data)"""
+
+
+def as_batch(data):
+    """the batch loops' way to their batch: an already prepared one passes through, a collated one is prepared"""
+    return data if isinstance(data, PreparedBatch) else prepare_data(data)
+
+
+def _window(size, box):
+    """square window of 1.5 x the longer side of box = (x, y, w, h), centred on the box, clipped to the image of
+    `size` = (W, H): [left, top, right, bottom]"""
     x, y, w, h = box
     half = int(max(w, h) * 0.75)
     cx, cy = int((2 * x + w) / 2), int((2 * y + h) / 2)
-    W, H = img.size
-    return img.crop([max(0, cx - half), max(0, cy - half), min(W, cx + half), min(H, cy + half)])
+    W, H = size
+    return [max(0, cx - half), max(0, cy - half), min(W, cx + half), min(H, cy + half)]
+
+
+def _crop_around(img, box):
+    return img.crop(_window(img.size, box))
+
+
+def load_image(img_path, bbox=None, resize=None):
+    """The deterministic head of the image path: the file as RGB, cropped to the bounding-box window, and (resize given)
+    its shorter side resized to `resize`.  get_imgs and the device-resident cache (sbagan/device_data.py) both start
+    here, so both see the same bytes."""
+    img = Image.open(img_path).convert('RGB')
+    if bbox is not None:
+        img = _crop_around(img, bbox)
+    if resize is not None:
+        img = transforms.Resize(resize)(img)
+    return img
+
+
+def loaded_size(img_path, bbox=None, resize=None):
+    """(height, width) of load_image's result, from the file's header alone (nothing is decoded)"""
+    with Image.open(img_path) as img:
+        w, h = img.size
+    if bbox is not None:
+        left, top, right, bottom = _window((w, h), bbox)
+        w, h = right - left, bottom - top
+    if resize is not None:
+        w, h = transforms.Resize(resize).output_size(w, h)
+    return h, w
 
 
 def get_imgs(img_path, imsize, bbox=None, transform=None, normalize=None):
     """The image pyramid of one sample: crop to the bounding box, apply the (random) transform once, then one
     normalised tensor per scale -- the transform's output is the LARGEST scale, the others are resized from it."""
-    img = Image.open(img_path).convert('RGB')
-    if bbox is not None:
-        img = _crop_around(img, bbox)
+    img = load_image(img_path, bbox)
     if transform is not None:
         img = transform(img)
     if cfg.GAN.B_DCGAN:
@@ -154,6 +190,12 @@ class TextDataset(data.Dataset):
     def _caption_store(self, data_dir):
         return _CaptionStore(data_dir, self.embeddings_num)
 
+    def image_path(self, index):
+        return '%s/images/%s.jpg' % (self.image_root, self.filenames[index])
+
+    def image_box(self, index):
+        return self.bbox[self.filenames[index]] if self.bbox is not None else None
+
     def get_caption(self, sent_ix):
         """caption `sent_ix` as a zero-padded WORDS_NUM x 1 int64 column and its (clipped) length; a longer caption
         keeps WORDS_NUM of its words, a random subset in the original order"""
@@ -172,8 +214,7 @@ class TextDataset(data.Dataset):
     def __getitem__(self, index):
         key = self.filenames[index]
         box = self.bbox[key] if self.bbox is not None else None
-        imgs = get_imgs('%s/images/%s.jpg' % (self.image_root, key), self.imsize, box, self.transform,
-                        normalize=self.norm)
+        imgs = get_imgs(self.image_path(index), self.imsize, box, self.transform, normalize=self.norm)
         which = np.random.randint(0, self.embeddings_num)             # one of the image's captions
         caption, length = self.get_caption(index * self.embeddings_num + which)
         return imgs, caption, length, self.class_id[index], key

@@ -5,7 +5,9 @@
 cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_example(example_filenames.txt).
 --fused_inference, --r_precision R (sampling also writes r_precision.json), --attention_maps (the attention-map
 overlay images, sbagan/visualize.py), --fid [--fid_stats PATH] (sampling also writes fid.json, sbagan/fid.py) and --prdc K
-(sampling also writes prdc.json: precision, recall, density and coverage, sbagan/prdc.py) are this project's additions."""
+(sampling also writes prdc.json: precision, recall, density and coverage, sbagan/prdc.py) and --device_data
+[--device_data_gb G] (training: the split is decoded once into a device-resident cache and every batch is cropped, flipped,
+resized to every scale and normalised there, sbagan/device_data.py) are this project's additions."""
 import os
 import sys
 import time
@@ -73,6 +75,12 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     assert dataset
     dataloader = torch.utils.data.DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True,
                                              shuffle=True, num_workers=int(cfg.WORKERS))
+    if getattr(args, 'device_data', False):
+        if training:     # the split cached on the device, batches made there: same batch contract, its own draws
+            from sbagan import device_data
+            dataloader = device_data.from_cfg(dataset, imsize, args.manualSeed, args.device_data_gb)
+        else:
+            print('--device_data is ignored outside training')
     print(len(dataloader))
     if make_trainer is None:
         from trainer import condGANTrainer as make_trainer

@@ -1,6 +1,7 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
+    [--device_data]  [--device_data_gb G]
     [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
@@ -63,6 +64,13 @@ def options(what, default_cfg, argv=None, bert=False):
                          'metrics, sbagan.prdc) between the real images of the split and the generated ones on the same '
                          'trunk features as --fid and write prdc.json; 0 = off, K from 1 to 8, 5 = the usual setting.  '
                          'On this project\'s own trunk and compute dtype: not comparable with published numbers')
+    ap.add_argument('--device_data', dest='device_data', action='store_true', default=False,
+                    help='training: decode the split once into a device-resident uint8 cache and make every batch '
+                         'there -- crop, flip, every scale of the pyramid and the normalisation in one HIP launch '
+                         '(sbagan.device_data), bit-identical to the PIL path for the same draws; the draws come from '
+                         'the loader\'s own generator, seeded by --manualSeed')
+    ap.add_argument('--device_data_gb', dest='device_data_gb', type=float, default=64.0, metavar='G',
+                    help='with --device_data: refuse a split whose cache would need more than G GiB')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

@@ -23,17 +23,21 @@ class Resize(object):
     def __init__(self, size, interpolation=Image.BILINEAR):
         self.size, self.interpolation = size, interpolation
 
-    def __call__(self, img):
+    def output_size(self, w, h):
+        """(width, height) of the result for a w x h input"""
         if isinstance(self.size, int):
-            w, h = img.size
             if (w <= h and w == self.size) or (h <= w and h == self.size):
-                return img
+                return w, h
             if w < h:
-                ow, oh = self.size, int(self.size * h / w)
-            else:
-                oh, ow = self.size, int(self.size * w / h)
-            return img.resize((ow, oh), self.interpolation)
-        return img.resize(self.size[::-1], self.interpolation)
+                return self.size, int(self.size * h / w)
+            return int(self.size * w / h), self.size
+        return tuple(self.size[::-1])
+
+    def __call__(self, img):
+        size = self.output_size(*img.size)
+        if isinstance(self.size, int) and size == img.size:
+            return img
+        return img.resize(size, self.interpolation)
 
 
 Scale = Resize          # the name pretrain_DAMSM.py:244 still uses

@@ -4,7 +4,8 @@
 
 train / evaluate / build_models keep the reference's signatures; the per-batch work is sbagan.damsm.DAMSMStep
 (HIP kernels).  --attention_maps: the reference's Image/attention_maps<step>.png (sbagan.visualize.build_super_images)
-wherever the interval log line is printed."""
+wherever the interval log line is printed.  --device_data [--device_data_gb G]: both splits are decoded once into a
+device-resident cache and every batch is cropped, flipped and normalised there (sbagan.device_data)."""
 import os
 import sys
 import time
@@ -15,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
-from datasets import TextDataset, prepare_data  # noqa: E402
+from datasets import TextDataset, as_batch, prepare_data  # noqa: E402,F401
 from miscc import cli, transforms  # noqa: E402
 from miscc.config import cfg  # noqa: E402
 from miscc.utils import mkdir_p  # noqa: E402
@@ -38,7 +39,7 @@ def train(dataloader, cnn_model, rnn_model, batch_size, labels, optimizer, epoch
     count = (epoch + 1) * len(dataloader)
     start_time = time.time()
     for step, data in enumerate(dataloader, 0):
-        imgs, captions, cap_lens, class_ids, keys = prepare_data(data)
+        imgs, captions, cap_lens, class_ids, keys = as_batch(data)
         out = optimizer.step(imgs[-1], captions, cap_lens, class_ids)
         w0 += float(out['w_loss0']); w1 += float(out['w_loss1'])
         s0 += float(out['s_loss0']); s1 += float(out['s_loss1'])
@@ -93,7 +94,7 @@ def evaluate(dataloader, cnn_model, rnn_model, batch_size, damsm=None):
     s_total = w_total = 0.0
     step = 0
     for step, data in enumerate(dataloader, 0):
-        real_imgs, captions, cap_lens, class_ids, keys = prepare_data(data)
+        real_imgs, captions, cap_lens, class_ids, keys = as_batch(data)
         s, w = damsm.evaluate(real_imgs[-1], captions, cap_lens, class_ids)
         s_total += float(s)
         w_total += float(w)
@@ -143,6 +144,10 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
     dataset_val = dataset_cls(cfg.DATA_DIR, 'test', base_size=cfg.TREE.BASE_SIZE, transform=image_transform)
     dataloader_val = torch.utils.data.DataLoader(dataset_val, batch_size=batch_size, drop_last=True, shuffle=True,
                                                  num_workers=int(cfg.WORKERS))
+    if getattr(args, 'device_data', False):      # both splits cached on the device, batches made there
+        from sbagan import device_data
+        dataloader = device_data.from_cfg(dataset, imsize, args.manualSeed, args.device_data_gb)
+        dataloader_val = device_data.from_cfg(dataset_val, imsize, args.manualSeed + 1, args.device_data_gb)
     text_encoder, image_encoder, labels, start_epoch = build(dataset.n_words, batch_size)
     from sbagan.damsm import DAMSMStep
     damsm = DAMSMStep(text_encoder, image_encoder, batch_size, lr=cfg.TRAIN.ENCODER_LR)

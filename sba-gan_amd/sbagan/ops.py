@@ -15,6 +15,7 @@ import ctypes
 import os
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2204,3 +2205,55 @@ def prdc_ball_counts(a, b, radius_a=None, radius_b=None, splits=0):
     call('sba_prdc_ball_counts', _p(a), na, lda, _p(b), nb, ldb, D, _p(radius_a), _p(radius_b), splits, _p(in_b),
          _p(in_own), _p(ws), nbytes, _stream())
     return in_b, in_own
+
+
+# ----------------------------------------------------------------------------
+# training batches from the device-resident image cache (sbagan/device_data.py)
+def check_pyramid_shape(T, levels):
+    """ValueError unless sba_batch_pyramid takes a T px crop at `levels` scales"""
+    if not 1 <= levels <= 3:
+        raise ValueError('batch_pyramid: levels must be 1, 2 or 3 (got %r)' % (levels,))
+    if not 4 <= T <= 1024 or T % (1 << (levels - 1)):
+        raise ValueError('batch_pyramid: T must be in [4, 1024] and a multiple of %d for %d levels (got %r)'
+                         % (1 << (levels - 1), levels, T))
+
+
+def batch_pyramid(cache, params_host, T, levels, params_dev=None):
+    """The image pyramids of one batch from a sbagan.device_data.DeviceImageCache in one launch (sba_batch_pyramid).
+    params_host: int32 [B][4] = {index, x1, y1, flip} on the HOST (numpy): image `index`, window [y1, y1 + T) x
+    [x1, x1 + T), mirrored when flip != 0.  Every row is checked against the cache's host size table before anything
+    is uploaded: ValueError for an index or a window out of range, or a T / levels the kernel does not take.
+    params_dev: the same rows already on the cache's device (the loader uploads them with its captions); otherwise
+    they are uploaded here.  Returns [out_0 .. out_{levels-1}], out_l [B][3][T >> l][T >> l] float32: level 0 the
+    normalised crop, the others resized from it as PIL's BILINEAR does."""
+    T, levels = int(T), int(levels)
+    check_pyramid_shape(T, levels)
+    params_host = np.ascontiguousarray(params_host)
+    if params_host.dtype != np.int32 or params_host.ndim != 2 or params_host.shape[1] != 4 or params_host.shape[0] < 1:
+        raise ValueError('batch_pyramid: params must be int32 [B][4], B >= 1 (got %s %s)'
+                         % (params_host.dtype, params_host.shape))
+    B, N = params_host.shape[0], len(cache)
+    index = params_host[:, 0].astype(np.int64)
+    x1, y1 = params_host[:, 1].astype(np.int64), params_host[:, 2].astype(np.int64)
+    if (index < 0).any() or (index >= N).any():
+        raise ValueError('batch_pyramid: image index out of range [0, %d): %s' % (N, index.tolist()))
+    H, W = cache.hw_host[index, 0].astype(np.int64), cache.hw_host[index, 1].astype(np.int64)
+    bad = (x1 < 0) | (y1 < 0) | (x1 + T > W) | (y1 + T > H)
+    if bad.any():
+        b = int(np.nonzero(bad)[0][0])
+        raise ValueError('batch_pyramid: row %d: the %d px window at (x1 = %d, y1 = %d) is not inside image %d (%d x %d)'
+                         % (b, T, x1[b], y1[b], index[b], H[b], W[b]))
+    dev = cache.device
+    _need_gpu(cache.data)
+    if params_dev is None:
+        params_dev = torch.from_numpy(params_host).pin_memory().to(dev, non_blocking=True)
+    elif (params_dev.dtype != torch.int32 or tuple(params_dev.shape) != (B, 4) or params_dev.device != dev
+          or not params_dev.is_contiguous()):
+        raise ValueError('batch_pyramid: params_dev must be contiguous int32 [%d][4] on %s' % (B, dev))
+    from .device_data import pyramid_tables
+    tab1, tab2, lut = pyramid_tables(T, levels, dev)
+    outs = [torch.empty((B, 3, T >> l, T >> l), dtype=torch.float32, device=dev) for l in range(levels)]
+    call('sba_batch_pyramid', _p(cache.data), _p(cache.offset), _p(cache.hw), N, _p(params_dev), B, T, levels, _p(tab1),
+         _p(tab2), _p(lut), _p(outs[0]), _p(outs[1]) if levels > 1 else None, _p(outs[2]) if levels > 2 else None,
+         _stream())
+    return outs

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from datasets import prepare_data
+from datasets import as_batch, prepare_data
 from miscc.config import cfg
 from miscc.utils import copy_G_params, load_params, mkdir_p, weights_init
 from model import CNN_ENCODER, D_NET64, D_NET128, D_NET256, G_NET, RNN_ENCODER
@@ -201,7 +201,7 @@ class condGANTrainer(object):
             start_t = time.time()
             step = 0
             for data in self.data_loader:
-                imgs, captions, cap_lens, class_ids, keys = prepare_data(data)
+                imgs, captions, cap_lens, class_ids, keys = as_batch(data)
                 words_embs, sent_emb = self._encode(text_encoder, captions, cap_lens)
                 mask = build_mask(captions, words_embs.size(2))
                 noise.normal_(0, 1)
