@@ -734,6 +734,18 @@ int sba_batch_pyramid(const uint8_t* cache, const int64_t* offset, const int32_t
                       int T, int levels, const int32_t* tab1, const int32_t* tab2, const float* lut, float* out0,
                       float* out1, float* out2, void* stream);
 
+/* The two masks of one training batch from integers already on the device, in ONE launch (sbagan/static_batch.py,
+ * DESIGN.md 7g): deterministic and free of host state, so it can be recorded in front of the training step.
+ * captions [B][L] int64 word ids, 0 = padding; class_ids [B] int64, compared as full 64-bit values.
+ *   word_mask  [B][L] uint8: 1 where captions == 0, else 0          (sbagan.trainer.build_mask)
+ *   class_mask [B][B] uint8: class_mask[i][j] = 1 where class_ids[j] == class_ids[i] and j != i, else 0
+ *                                                                    (miscc.losses.class_mask)
+ * Every byte written is exactly 0 or 1 and nothing outside the two outputs is written.  Grid-stride over B * L + B * B
+ * elements, plain byte stores, no atomics, no LDS, no workspace.  SBA_E_ARG before any launch on a null pointer or
+ * unless 1 <= B <= 65535 and 1 <= L <= 65535. */
+int sba_batch_masks(const int64_t* captions, const int64_t* class_ids, uint8_t* word_mask, uint8_t* class_mask, int B,
+                    int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
-    [--device_data]  [--device_data_gb G]
+    [--device_data]  [--device_data_gb G]  [--replay]
     [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
@@ -71,6 +71,11 @@ def options(what, default_cfg, argv=None, bert=False):
                          'the loader\'s own generator, seeded by --manualSeed')
     ap.add_argument('--device_data_gb', dest='device_data_gb', type=float, default=64.0, metavar='G',
                     help='with --device_data: refuse a split whose cache would need more than G GiB')
+    ap.add_argument('--replay', dest='replay', action='store_true', default=False,
+                    help='GAN training: run every batch through ONE recording of the training step, re-issued by the '
+                         'native launch replayer from a static batch slot (sbagan.static_batch) -- the step at the '
+                         'benchmarked speed; best with --device_data.  The step draws its own noise, so a seeded run '
+                         'differs from one without the flag.  Ignored by DAMSM pre-training and outside training')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

@@ -10,7 +10,9 @@ Differences from the reference, none of which change a result:
     value is an empty list (the PNG visualiser, their only reader, computes the maps of its
     <= 8 samples itself: sbagan.visualize.damsm_attention_maps);
   * the same-class mask is built on the host with numpy exactly like the reference
-    (losses.py:24-32,73-76) -- it is integer work on `class_ids`, a host array.
+    (losses.py:24-32,73-76) -- it is integer work on `class_ids`, a host array.  The recorded training loop
+    (--replay) cannot have a per-batch tensor built on the host: there `class_ids` is an ops.ClassMask, the same mask
+    made on the device by sba_batch_masks, and is used as it is.
 """
 import numpy as np
 
@@ -58,9 +60,16 @@ DIRECT_DAMSM = True     # damsm_image_terms: loss heads + gradients without auto
 def class_mask(class_ids, batch_size, device):
     """masks[i][j] = (class_ids[j] == class_ids[i]) and j != i  (losses.py:24-32).  Bit-exact
     integer work on the host; cached per (ids, device) so a training loop with fixed ids
-    uploads it once."""
+    uploads it once.  A mask already on the device (ops.ClassMask, made by ops.batch_masks from device-side ids: the
+    recorded training step, sbagan/static_batch.py) is returned as it is: no numpy, no cache, no upload."""
     if class_ids is None:
         return None
+    if isinstance(class_ids, ops.ClassMask):
+        m = class_ids.tensor
+        if m.size(0) != batch_size or m.device != torch.device(device):
+            raise ValueError('class_mask: the prepared mask is %s on %s, the batch needs [%d][%d] on %s'
+                             % (tuple(m.shape), m.device, batch_size, batch_size, device))
+        return m
     ids = np.asarray(class_ids).reshape(-1)[:batch_size]
     key = (ids.tobytes(), str(ids.dtype), batch_size, str(device))
     m = _MASK_CACHE.get(key)

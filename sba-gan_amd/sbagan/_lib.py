@@ -149,6 +149,7 @@ SIGNATURES = {
     'sba_prdc_knn_radius': [P, I, I, I, I, I, P, P, L, P],
     'sba_prdc_ball_counts': [P, I, I, P, I, I, I, P, P, I, P, P, P, L, P],
     'sba_batch_pyramid': [P, P, P, I, P, I, I, I, P, P, P, P, P, P, P],
+    'sba_batch_masks': [P, P, P, P, I, I, P],
     'sba_set_deterministic': [I, P, L],
     'sba_set_reduce_scratch': [P, L],
     'sba_det_reset': [],

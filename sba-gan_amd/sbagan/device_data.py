@@ -206,6 +206,7 @@ class DeviceBatchLoader(object):
         self.shuffle, self.drop_last = shuffle, drop_last
         self.rng = np.random.Generator(np.random.PCG64(seed))
         self.last_draws = None
+        self.slot = None
 
     def __len__(self):
         n, b = len(self.dataset), self.batch_size
@@ -238,12 +239,40 @@ class DeviceBatchLoader(object):
         return Draws(index, x1[order], y1[order], flip[order], which[order], np.stack(captions)[order], lengths[order],
                      np.asarray([ds.class_id[int(i)] for i in index]), [ds.filenames[int(i)] for i in index])
 
+    def bind(self, slot):
+        """Write every further batch straight into `slot` (sbagan.static_batch.StaticBatch; None: back to fresh
+        tensors per batch): captions, lengths, CLASS IDS and params go up in the loader's single upload, into the
+        slot's blob, and the pyramid launch writes the slot's image tensors.  The items keep their form; their device
+        tensors are the slot's."""
+        if slot is not None:
+            if (slot.batch_size, slot.levels, slot.crop) != (self.batch_size, self.levels, self.crop) \
+                    or slot.device != self.cache.device:
+                raise ValueError('DeviceBatchLoader.bind: the slot holds batches of %d at %d px x %d scales on %s; the '
+                                 'loader makes %d at %d px x %d on %s'
+                                 % (slot.batch_size, slot.crop, slot.levels, slot.device, self.batch_size, self.crop,
+                                    self.levels, self.cache.device))
+            if not self.drop_last and len(self.dataset) % self.batch_size:
+                raise ValueError('DeviceBatchLoader.bind: a batch slot needs drop_last (the last batch would be smaller)')
+        self.slot = slot
+
+    def _into_slot(self, d, params):
+        from .static_batch import SlotBatch, pack_blob
+        slot = self.slot
+        slot.upload(pack_blob(d.captions, d.lengths, d.class_ids, slot.batch_size, slot.words_num, params))
+        ops.batch_pyramid(self.cache, params, self.crop, self.levels, params_dev=slot.params, out=slot.imgs[::-1])
+        batch = SlotBatch([slot.imgs, slot.captions, slot.cap_lens, d.class_ids, d.keys])
+        batch.slot = slot
+        return batch
+
     def __iter__(self):
         dev = self.cache.device
         for indices in self.epoch_indices():
             d = self.draw_batch(indices)
             self.last_draws = d
             params = d.params()
+            if self.slot is not None:
+                yield self._into_slot(d, params)
+                continue
             # one pinned upload: captions and lengths (int64), then params (int32)
             head = np.concatenate([d.captions.reshape(-1), d.lengths])
             blob = np.concatenate([head.view(np.uint8), params.reshape(-1).view(np.uint8)])

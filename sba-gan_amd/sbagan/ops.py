@@ -2218,14 +2218,15 @@ def check_pyramid_shape(T, levels):
                          % (1 << (levels - 1), levels, T))
 
 
-def batch_pyramid(cache, params_host, T, levels, params_dev=None):
+def batch_pyramid(cache, params_host, T, levels, params_dev=None, out=None):
     """The image pyramids of one batch from a sbagan.device_data.DeviceImageCache in one launch (sba_batch_pyramid).
     params_host: int32 [B][4] = {index, x1, y1, flip} on the HOST (numpy): image `index`, window [y1, y1 + T) x
     [x1, x1 + T), mirrored when flip != 0.  Every row is checked against the cache's host size table before anything
     is uploaded: ValueError for an index or a window out of range, or a T / levels the kernel does not take.
     params_dev: the same rows already on the cache's device (the loader uploads them with its captions); otherwise
     they are uploaded here.  Returns [out_0 .. out_{levels-1}], out_l [B][3][T >> l][T >> l] float32: level 0 the
-    normalised crop, the others resized from it as PIL's BILINEAR does."""
+    normalised crop, the others resized from it as PIL's BILINEAR does.  out (optional): that list preallocated by the
+    caller (shapes, dtype and device are checked); the launch writes into it and it is what is returned."""
     T, levels = int(T), int(levels)
     check_pyramid_shape(T, levels)
     params_host = np.ascontiguousarray(params_host)
@@ -2252,8 +2253,52 @@ def batch_pyramid(cache, params_host, T, levels, params_dev=None):
         raise ValueError('batch_pyramid: params_dev must be contiguous int32 [%d][4] on %s' % (B, dev))
     from .device_data import pyramid_tables
     tab1, tab2, lut = pyramid_tables(T, levels, dev)
-    outs = [torch.empty((B, 3, T >> l, T >> l), dtype=torch.float32, device=dev) for l in range(levels)]
+    if out is None:
+        outs = [torch.empty((B, 3, T >> l, T >> l), dtype=torch.float32, device=dev) for l in range(levels)]
+    else:
+        outs = list(out)
+        if len(outs) != levels:
+            raise ValueError('batch_pyramid: out must hold %d tensors (got %d)' % (levels, len(outs)))
+        for l, o in enumerate(outs):
+            if (not torch.is_tensor(o) or o.dtype != torch.float32 or tuple(o.shape) != (B, 3, T >> l, T >> l)
+                    or o.device != dev or not o.is_contiguous()):
+                raise ValueError('batch_pyramid: out[%d] must be contiguous float32 [%d][3][%d][%d] on %s'
+                                 % (l, B, T >> l, T >> l, dev))
     call('sba_batch_pyramid', _p(cache.data), _p(cache.offset), _p(cache.hw), N, _p(params_dev), B, T, levels, _p(tab1),
          _p(tab2), _p(lut), _p(outs[0]), _p(outs[1]) if levels > 1 else None, _p(outs[2]) if levels > 2 else None,
          _stream())
     return outs
+
+
+class ClassMask(object):
+    """A same-class mask already on the device (uint8 [B][B], what miscc.losses.class_mask builds from host ids),
+    handed to the losses in the `class_ids` position: the wrapper keeps a [B][B] tensor from being taken for ids."""
+    __slots__ = ('tensor',)
+
+    def __init__(self, tensor):
+        if (not torch.is_tensor(tensor) or tensor.dtype != torch.uint8 or tensor.dim() != 2
+                or tensor.size(0) != tensor.size(1) or not tensor.is_contiguous()):
+            raise ValueError('ClassMask: needs a contiguous uint8 [B][B] tensor')
+        self.tensor = tensor
+
+
+def batch_masks(captions, class_ids, word_mask, class_mask):
+    """Both masks of one batch in one launch (sba_batch_masks), from integers already on the device: word_mask [B][L]
+    (bool or uint8) = (captions == 0), class_mask [B][B] (uint8, or a ClassMask) = same class and not the same row.
+    captions int64 [B][L] and class_ids int64 [B], contiguous; the outputs are written in place and returned."""
+    cm = class_mask.tensor if isinstance(class_mask, ClassMask) else class_mask
+    _need_gpu(captions)
+    if captions.dtype != torch.int64 or captions.dim() != 2 or not captions.is_contiguous() or captions.numel() == 0:
+        raise ValueError('batch_masks: captions must be contiguous int64 [B][L], B, L >= 1')
+    B, L = captions.shape
+    dev = captions.device
+    if class_ids.dtype != torch.int64 or tuple(class_ids.shape) != (B,) or not class_ids.is_contiguous() \
+            or class_ids.device != dev:
+        raise ValueError('batch_masks: class_ids must be contiguous int64 [%d] on %s' % (B, dev))
+    if word_mask.dtype not in (torch.bool, torch.uint8) or tuple(word_mask.shape) != (B, L) \
+            or not word_mask.is_contiguous() or word_mask.device != dev:
+        raise ValueError('batch_masks: word_mask must be contiguous bool / uint8 [%d][%d] on %s' % (B, L, dev))
+    if cm.dtype != torch.uint8 or tuple(cm.shape) != (B, B) or not cm.is_contiguous() or cm.device != dev:
+        raise ValueError('batch_masks: class_mask must be contiguous uint8 [%d][%d] on %s' % (B, B, dev))
+    call('sba_batch_masks', _p(captions), _p(class_ids), _p(word_mask), _p(cm), B, L, _stream())
+    return word_mask, class_mask

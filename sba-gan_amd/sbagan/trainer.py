@@ -1014,10 +1014,10 @@ class ReplayedStep(object):
             eps.normal_(0, 1)
             if recorded_prologue is not None:
                 recorded_prologue()
-            gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise, eps=eps)
+            out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise, eps=eps)
         torch.cuda.current_stream().wait_stream(cap)
         torch.cuda.synchronize()
-        return {'cap': cap, 'eps': eps}
+        return {'cap': cap, 'eps': eps, 'out': dict(out)}      # (out: the warm-up step's losses -- it is a training step)
 
     def __init__(self, gan, imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise, prologue=None,
                  recorded_prologue=None, max_streams=None, verbose=False, warm=None):

@@ -6,6 +6,9 @@ What differs, none of it in results:
     `define_optimizers` returns them in the reference's (optimizerG, [optimizerD...]) shape;
   * one training step is GANStep.step (same order as trainer.py:245-299), the per-100-iteration log lines are
     formatted from device scalars outside the step (the reference's five .item() syncs per step are gone);
+  * with `replay` (--replay) the loop trains every batch through ONE recording of that step, re-issued by the native
+    launch replayer from a static batch slot (sbagan.static_batch): per iteration the host draws the
+    batch, uploads its integers, launches the image pyramid, draws the noise and replays;
   * `save_img_results` writes a plain image grid per scale; with `attention_maps` (--attention_maps) it writes the
     reference's attention overlays instead (G_*.png per attention stage, D_*.png for the DAMSM maps), built on the
     device by sbagan.visualize from the overlays' contract (DESIGN.md 7c), and gen_example adds the top-5 strips;
@@ -178,13 +181,53 @@ class condGANTrainer(object):
             Image.fromarray(np.concatenate(tiles, 1)).save('%s/G_%s_%d_%d.png' % (self.image_dir, name, gen_iterations, i))
 
     # ------------------------------------------------------------------ training loop (trainer.py:218-346)
-    def _encode(self, text_encoder, captions, cap_lens):
+    def _encode(self, text_encoder, captions, cap_lens, out=None):
+        """out = (words_embs, sent_emb): the static-output form of the recorded loop -- no host sync, the full padded
+        width out[0].size(2), the same zero hidden state every call (made on the first, eager one), results written
+        into `out`"""
+        if out is not None:
+            key = (id(text_encoder), captions.size(0))
+            if getattr(self, '_static_hidden', (None,))[0] != key:
+                self._static_hidden = (key, text_encoder.init_hidden(captions.size(0)))
+            with torch.no_grad():
+                words_embs, sent_emb = text_encoder(captions, cap_lens, self._static_hidden[1],
+                                                    max_len=out[0].size(2), out=out)
+            if words_embs is not out[0]:        # (an encoder off the HIP path returns tensors of its own)
+                out[0].copy_(words_embs)
+                out[1].copy_(sent_emb)
+            return out
         hidden = text_encoder.init_hidden(captions.size(0))
         with torch.no_grad():
             words_embs, sent_emb = text_encoder(captions, cap_lens, hidden, max_len=int(cap_lens.max()))
         return words_embs.detach(), sent_emb.detach()
 
+    replay = False              # --replay: train() runs every batch through ONE recording of the step (DESIGN.md 7g)
+    replay_eager = False        # with replay: the same loop over the static batch slot, the step launched eagerly
+    average_interval = 1000     # iterations between the 'average' (EMA generator) image dumps
+
+    def _replay_step(self, text_encoder, noise):
+        """the static batch slot and the step over it (sbagan.static_batch); a device loader writes straight into it"""
+        from miscc import cli
+        from sbagan.static_batch import SlotStep, StaticBatch
+        loader = self.data_loader
+        if not getattr(loader, 'drop_last', False):
+            raise RuntimeError('--replay needs a loader that drops the last, smaller batch (drop_last): the recorded '
+                               'step reads a batch slot of fixed shape')
+        slot = StaticBatch(self.batch_size, cfg.TEXT.WORDS_NUM, cfg.TREE.BRANCH_NUM,
+                           getattr(loader, 'crop', None) or cli.image_size(), self.device)
+        if hasattr(loader, 'bind'):
+            loader.bind(slot)
+        prologue = slot.prologue(text_encoder, encode=self._encode)
+        return slot, SlotStep(self.gan, slot, prologue, noise, eager=self.replay_eager)
+
     def train(self, max_steps=None):
+        try:
+            return self._train(max_steps)
+        finally:        # (--replay binds a device loader to the run's batch slot)
+            if getattr(self.data_loader, 'slot', None) is not None:
+                self.data_loader.bind(None)
+
+    def _train(self, max_steps=None):
         built = self.build_models()
         if built is None:
             return
@@ -197,15 +240,26 @@ class condGANTrainer(object):
         fixed_noise = torch.randn(self._noise_shape(batch_size), device=self.device)
         gen_iterations = 0
         out = None
+        slot = stepper = None
+        if self.replay:
+            slot, stepper = self._replay_step(text_encoder, noise)
+        self.slot, self.slot_step = slot, stepper
         for epoch in range(start_epoch, self.max_epoch):
             start_t = time.time()
             step = 0
             for data in self.data_loader:
-                imgs, captions, cap_lens, class_ids, keys = as_batch(data)
-                words_embs, sent_emb = self._encode(text_encoder, captions, cap_lens)
-                mask = build_mask(captions, words_embs.size(2))
-                noise.normal_(0, 1)
-                out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise)
+                if stepper is not None:
+                    # the batch goes into the slot (one pinned upload; the device loader has put it there already), the
+                    # step draws its own noise and eps and is re-issued from the recording: no host sync
+                    imgs, captions, cap_lens, class_ids, keys = slot.load(as_batch(data))
+                    out = stepper.train()
+                    words_embs, sent_emb, mask = slot.words_embs, slot.sent_emb, slot.mask
+                else:
+                    imgs, captions, cap_lens, class_ids, keys = as_batch(data)
+                    words_embs, sent_emb = self._encode(text_encoder, captions, cap_lens)
+                    mask = build_mask(captions, words_embs.size(2))
+                    noise.normal_(0, 1)
+                    out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise)
                 step += 1
                 gen_iterations += 1
                 if gen_iterations % 100 == 0:
@@ -214,13 +268,15 @@ class condGANTrainer(object):
                     print(' '.join('errD%d: %.2f' % (i, v['errD%d' % i]) for i in range(nD)) + '\n' +
                           ' '.join('g_loss%d: %.2f' % (i, v['g_loss%d' % i]) for i in range(nD)) +
                           ' w_loss: %.2f s_loss: %.2f kl_loss: %.2f' % (v['w_loss'], v['s_loss'], v['kl_loss']))
-                if gen_iterations % 1000 == 0:
+                if gen_iterations % self.average_interval == 0:
                     gan.finish()        # (data-parallel: a pending generator update is applied before it is read)
                     backup_para = copy_G_params(netG)
                     load_params(netG, gan.flatG.ema_params())
                     self.save_img_results(netG, fixed_noise, sent_emb, words_embs, mask, image_encoder, captions,
                                           cap_lens, epoch, name='average')
                     load_params(netG, backup_para)
+                    if stepper is not None:     # the parameters were edited behind the recording's back
+                        stepper.resync()
                 if max_steps is not None and gen_iterations >= max_steps:
                     break
             end_t = time.time()
@@ -232,6 +288,8 @@ class condGANTrainer(object):
             if epoch % cfg.TRAIN.SNAPSHOT_INTERVAL == 0:
                 gan.finish()
                 self.save_model(netG, gan.flatG.ema_params(), netsD, epoch)
+                if stepper is not None:
+                    stepper.resync()
             if max_steps is not None and gen_iterations >= max_steps:
                 break
         gan.finish()

@@ -40,9 +40,13 @@ class condGANTrainer(trainer.condGANTrainer):
     def _noise_shape(self, n):
         return (2, n, cfg.GAN.Z_DIM) if cfg.TRAIN.MIXING else (n, cfg.GAN.Z_DIM)
 
-    def _encode(self, text_encoder, captions, cap_lens):
+    def _encode(self, text_encoder, captions, cap_lens, out=None):
         with torch.no_grad():
             words_embs, sent_emb = text_encoder(captions)
+        if out is not None:         # the static-output form of the recorded loop (--replay)
+            out[0].copy_(words_embs)
+            out[1].copy_(sent_emb)
+            return out
         return words_embs.detach(), sent_emb.detach()
 
     def gen_example(self, data_dic):

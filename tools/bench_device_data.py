@@ -6,8 +6,9 @@
       time beside the 6.3 TB/s the project's streaming kernels reach;
   (b) batches/s of DeviceBatchLoader alone against the torch DataLoader + prepare_data at WORKERS 4 and 16, on a seeded
       synthetic CUB-shaped directory of 1000 JPEGs (500 x 375, with boxes), the paths alternated in the same call;
-  (c) ms per iteration of condGANTrainer.train on that directory at the bird_style sizes with random encoders, with and
-      without the flag, alternated.
+  (c) ms per iteration of condGANTrainer.train on that directory at the bird_style sizes with random encoders: with
+      --device_data --replay (the loop through one recording of the step), with --device_data alone and
+      with neither, alternated; and the node and stream counts of the recording.
 
 Every window is at least 200 batches (300 iterations in (c)) after a warm-up and ends in a device synchronise.
 
@@ -193,6 +194,9 @@ class _Timed(object):
     def __len__(self):
         return len(self.loader)
 
+    def __getattr__(self, name):        # drop_last, crop, bind, slot: what the trainer asks its loader
+        return getattr(self.loader, name)
+
     def __iter__(self):
         for data in self.loader:
             if self.n == self.warm:
@@ -216,17 +220,33 @@ def part_c(args, data_dir):
     dev_loader = device_data.from_cfg(ds, imsize, seed=1, gb=4.0)
     pil_loader = torch.utils.data.DataLoader(ds, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True, shuffle=True,
                                              num_workers=int(cfg.WORKERS))
-    out = {'--device_data': [], 'DataLoader WORKERS 4': []}
+    arms = (('--device_data --replay', dev_loader, True), ('--device_data', dev_loader, False),
+            ('DataLoader WORKERS 4', pil_loader, False))
+    out = {name: [] for name, _, _ in arms}
+    info = None
     for r in range(args.rounds):
-        for name, loader in (('--device_data', dev_loader), ('DataLoader WORKERS 4', pil_loader)):
+        for name, loader, replay in arms:
             timed = _Timed(loader, args.warm_iters, args.iters)
             algo = condGANTrainer(os.path.join(args.dir, 'out_%d' % r), timed, ds.n_words, ds.ixtoword,
                                   allow_random_encoders=True)
+            algo.replay = replay
             algo.train(max_steps=args.warm_iters + args.iters + 1)
             out[name].append(timed.ms)
+            if replay:
+                rec = algo.slot_step.recording
+                info = None if rec is None else dict(rec.info)
+            del algo
     for name, ms in out.items():
         say('    %-22s %7.2f ms / iteration = %6.0f images/s   (runs: %s)'
             % (name, float(np.median(ms)), 20e3 / float(np.median(ms)), ' '.join('%.2f' % v for v in ms)))
+    pairs = list(zip(out['--device_data --replay'], out['--device_data']))
+    say('    --replay faster than the eager loop in %d of %d alternated pairs'
+        % (sum(1 for a, b in pairs if a < b), len(pairs)))
+    if info is None:
+        say('    the step could NOT be recorded: the --replay arm ran its eager fallback')
+    else:
+        say('    the recording (prologue + step): %s' % ', '.join('%d %s' % (info[k], k) for k in (
+            'nodes', 'kernels', 'copies', 'memsets', 'streams', 'waits', 'events', 'host_calls')))
 
 
 def main():
