@@ -746,6 +746,34 @@ int sba_batch_pyramid(const uint8_t* cache, const int64_t* offset, const int32_t
 int sba_batch_masks(const int64_t* captions, const int64_t* class_ids, uint8_t* word_mask, uint8_t* class_mask, int B,
                     int L, void* stream);
 
+/* ---- the recorded DAMSM pre-training update (sbagan/damsm.py: DAMSMSlotStep) ----
+ * What the eager update does on the host, or with host floats, done on the device so that the update can be recorded
+ * once and re-issued: plain vector loads and stores, no atomics, no host synchronisation, the same bits on every run.
+ *
+ * Embedding -> Dropout of RNN_ENCODER's training path with the keep mask as a TENSOR (the caller draws it per batch):
+ *   ids [N] int64, W [ntoken][ninput] f32, keep [N][ninput] uint8 (non-zero = kept), out / dout [N][ninput] f32,
+ *   scale = float(1 / (1 - p)).  out[i][c] = keep[i][c] ? W[ids[i]][c] * scale : 0.  An id outside [0, ntoken) is
+ *   compared before it indexes: its output row is zero and it adds nothing to dW.
+ *   dW[id][c] += sum_{j: ids[j] == id} keep[j][c] * dout[j][c] * scale, added in increasing j by the ONE workgroup of
+ *   the first position that holds the id (ids of the batch in LDS).
+ * 1 <= N <= 8192, ninput % 4 == 0, W / out / dout / dW 16-byte aligned, keep 4-byte aligned; else SBA_E_ARG. */
+int sba_embed_dropout_fwd(const int64_t* ids, const float* W, const uint8_t* keep, float scale, float* out, int N,
+                          int ntoken, int ninput, void* stream);
+int sba_embed_dropout_bwd(const int64_t* ids, const uint8_t* keep, float scale, const float* dout, float* dW, int N,
+                          int ntoken, int ninput, void* stream);
+/* clip_grad_norm_ over n contiguous f32 gradients, in two launches.  sba_sqnorm_partials: nparts workgroups (1..1024),
+ * each writes ONE f64 = the sum of g^2 over the elements it visits (the square in f32, the sum in f64, folded in LDS in
+ * a fixed order).  sba_clip_adam_prepare: one workgroup adds the partials in index order in f64 and writes
+ * out[0] = norm, out[1] = min(1, max_norm / (norm + 1e-6)) (both f32); then sba_adam_prepare's work on `state` with the
+ * learning rate READ from lr_dev (one f32 in device memory). */
+int sba_sqnorm_partials(const float* g, int64_t n, double* partials, int nparts, void* stream);
+int sba_clip_adam_prepare(void* state, const double* partials, int nparts, const float* lr_dev, float max_norm,
+                          float beta1, float beta2, float* out, void* stream);
+/* sba_adam_step with the gradient scale read from device memory when the kernel runs (grad_scale_dev: one f32, e.g.
+ * out + 1 of sba_clip_adam_prepare; NULL = 1): the same kernel body, bit-identical to sba_adam_step for the same scale. */
+int sba_adam_step_dscale(float* p, const float* g, float* m, float* v, float* avg, void* shadow, const void* state,
+                         int64_t n, float beta1, float beta2, float eps, const float* grad_scale_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

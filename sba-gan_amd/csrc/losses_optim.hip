@@ -79,11 +79,17 @@ __device__ __forceinline__ void st4(float* a, int64_t i, f32x4_t x) {
     if (NT) __builtin_nontemporal_store(x, q); else *q = x;
 }
 
-template <bool NT>
+// GS: the gradient scale as the launch passes it -- a host float (sba_adam_step), or a pointer to one f32 in device memory
+// that is read when the kernel runs (sba_adam_step_dscale: the clip coefficient of a recorded update; null = 1)
+__device__ __forceinline__ float grad_scale_of(float s) { return s; }
+__device__ __forceinline__ float grad_scale_of(const float* s) { return s ? *s : 1.f; }
+
+template <bool NT, typename GS>
 __global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                  float* __restrict__ v, float* __restrict__ avg, bf16_t* __restrict__ shadow,
                                  const AdamState* __restrict__ st, int64_t n, float beta1, float beta2, float eps,
-                                 float gscale) {
+                                 GS gs) {
+    const float gscale = grad_scale_of(gs);
     const float step_size = st->step_size, isb2 = st->inv_sqrt_bc2;
     const int64_t n4 = n / 4;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
@@ -168,8 +174,22 @@ extern "C" int sba_adam_step(float* p, const float* g, float* m, float* v, float
     int64_t blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    SBA_LAUNCH(adam_step_kernel<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, avg,
+    SBA_LAUNCH((adam_step_kernel<true, float>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, avg,
                (bf16_t*)shadow, (const AdamState*)state, n, beta1, beta2, eps, grad_scale);
+    return SBA_CHECK_LAUNCH();
+}
+
+extern "C" int sba_adam_step_dscale(float* p, const float* g, float* m, float* v, float* avg, void* shadow,
+                                    const void* state, int64_t n, float beta1, float beta2, float eps,
+                                    const float* grad_scale_dev, void* stream) {
+    if (!p || !g || !m || !v || !state || n <= 0) return SBA_E_ARG;
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)avg) & 15) return SBA_E_ARG;
+    if (((uintptr_t)shadow & 7) || ((uintptr_t)grad_scale_dev & 3)) return SBA_E_ARG;
+    int64_t blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    SBA_LAUNCH((adam_step_kernel<true, const float*>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m,
+               v, avg, (bf16_t*)shadow, (const AdamState*)state, n, beta1, beta2, eps, grad_scale_dev);
     return SBA_CHECK_LAUNCH();
 }
 

@@ -75,7 +75,11 @@ def options(what, default_cfg, argv=None, bert=False):
                     help='GAN training: run every batch through ONE recording of the training step, re-issued by the '
                          'native launch replayer from a static batch slot (sbagan.static_batch) -- the step at the '
                          'benchmarked speed; best with --device_data.  The step draws its own noise, so a seeded run '
-                         'differs from one without the flag.  Ignored by DAMSM pre-training and outside training')
+                         'differs from one without the flag.  DAMSM pre-training (pretrain_DAMSM.py): the whole update '
+                         '-- both encoders\' trainable parts, the gradient clip and Adam -- is one recording '
+                         '(sbagan.damsm.DAMSMSlotStep), the dropout mask is drawn per batch outside it and the losses '
+                         'are read only where the interval line is printed.  Ignored by pretrain_DAMSM_bert.py and '
+                         'outside training')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

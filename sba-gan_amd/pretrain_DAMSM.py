@@ -5,7 +5,9 @@
 train / evaluate / build_models keep the reference's signatures; the per-batch work is sbagan.damsm.DAMSMStep
 (HIP kernels).  --attention_maps: the reference's Image/attention_maps<step>.png (sbagan.visualize.build_super_images)
 wherever the interval log line is printed.  --device_data [--device_data_gb G]: both splits are decoded once into a
-device-resident cache and every batch is cropped, flipped and normalised there (sbagan.device_data)."""
+device-resident cache and every batch is cropped, flipped and normalised there (sbagan.device_data).  --replay (training
+only): the update is ONE recording over a static batch slot (sbagan.damsm.DAMSMSlotStep), the losses are
+read only where the interval line is printed."""
 import os
 import sys
 import time
@@ -38,18 +40,29 @@ def train(dataloader, cnn_model, rnn_model, batch_size, labels, optimizer, epoch
     s0 = s1 = w0 = w1 = 0.0
     count = (epoch + 1) * len(dataloader)
     start_time = time.time()
+    # --replay: `optimizer` is a sbagan.damsm.DAMSMSlotStep -- the batch goes into its slot (a bound device loader has put
+    # it there already), the update is one re-issued recording, and the host reads the losses only where it prints them
+    slot_step = optimizer if hasattr(optimizer, 'read_losses') else None
     for step, data in enumerate(dataloader, 0):
-        imgs, captions, cap_lens, class_ids, keys = as_batch(data)
-        out = optimizer.step(imgs[-1], captions, cap_lens, class_ids)
-        w0 += float(out['w_loss0']); w1 += float(out['w_loss1'])
-        s0 += float(out['s_loss0']); s1 += float(out['s_loss1'])
+        if slot_step is not None:
+            imgs, captions, cap_lens, class_ids, keys = slot_step.load(as_batch(data))
+            slot_step.train()
+        else:
+            imgs, captions, cap_lens, class_ids, keys = as_batch(data)
+            out = optimizer.step(imgs[-1], captions, cap_lens, class_ids)
+            w0 += float(out['w_loss0']); w1 += float(out['w_loss1'])
+            s0 += float(out['s_loss0']); s1 += float(out['s_loss1'])
         if step % UPDATE_INTERVAL == 0:
             count = epoch * len(dataloader) + step
+            if slot_step is not None:       # means over the batches since the last line (the only host sync)
+                m = slot_step.read_losses()
+                means = m['s_loss0'], m['s_loss1'], m['w_loss0'], m['w_loss1']
+            else:
+                means = s0 / UPDATE_INTERVAL, s1 / UPDATE_INTERVAL, w0 / UPDATE_INTERVAL, w1 / UPDATE_INTERVAL
             elapsed = time.time() - start_time
             print('| epoch {:3d} | {:5d}/{:5d} batches | ms/batch {:5.2f} | s_loss {:5.2f} {:5.2f} | '
                   'w_loss {:5.2f} {:5.2f}'.format(epoch, step, len(dataloader), elapsed * 1000. / UPDATE_INTERVAL,
-                                                  s0 / UPDATE_INTERVAL, s1 / UPDATE_INTERVAL, w0 / UPDATE_INTERVAL,
-                                                  w1 / UPDATE_INTERVAL))
+                                                  *means))
             s0 = s1 = w0 = w1 = 0.0
             if attention_maps:
                 save_attention_maps(cnn_model, rnn_model, imgs[-1], captions, cap_lens, ixtoword,
@@ -122,9 +135,10 @@ def build_models(n_words, batch_size):
     return text_encoder.to(dev), image_encoder.to(dev), labels.to(dev), start_epoch
 
 
-def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=None):
+def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=None, make_step=None):
     """`args` / `dataset_cls` / `build` (n_words, batch_size -> text encoder, image encoder, labels, start epoch): the
-    BERT entry point (pretrain_DAMSM_bert.py) passes its own; the defaults are this script's."""
+    BERT entry point (pretrain_DAMSM_bert.py) passes its own; the defaults are this script's.  `make_step`: with --replay,
+    what builds the slot step (sbagan.damsm.DAMSMSlotStep's signature; the tests pass eager=True through it)."""
     args = parse_args(argv) if args is None else args
     build = build_models if build is None else build
     cli.configure(args)
@@ -149,8 +163,20 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
         dataloader = device_data.from_cfg(dataset, imsize, args.manualSeed, args.device_data_gb)
         dataloader_val = device_data.from_cfg(dataset_val, imsize, args.manualSeed + 1, args.device_data_gb)
     text_encoder, image_encoder, labels, start_epoch = build(dataset.n_words, batch_size)
-    from sbagan.damsm import DAMSMStep
-    damsm = DAMSMStep(text_encoder, image_encoder, batch_size, lr=cfg.TRAIN.ENCODER_LR)
+    from sbagan.damsm import DAMSMSlotStep, DAMSMStep
+    from sbagan.encoders import BertEncoder
+    replay = bool(getattr(args, 'replay', False)) and cfg.TRAIN.FLAG
+    if replay and isinstance(text_encoder, BertEncoder):
+        print('--replay is ignored by DAMSM pre-training with the BERT text side (its dropout offset is a host argument)')
+        replay = False
+    if replay:      # the update as one recording over a static batch slot
+        make_step = DAMSMSlotStep if make_step is None else make_step
+        damsm = make_step(text_encoder, image_encoder, batch_size, imsize, lr=cfg.TRAIN.ENCODER_LR,
+                          levels=cfg.TREE.BRANCH_NUM)
+        if hasattr(dataloader, 'bind'):
+            dataloader.bind(damsm.slot)     # the device loader writes every training batch straight into the slot
+    else:
+        damsm = DAMSMStep(text_encoder, image_encoder, batch_size, lr=cfg.TRAIN.ENCODER_LR)
     try:
         lr = cfg.TRAIN.ENCODER_LR
         for epoch in range(start_epoch, cfg.TRAIN.MAX_EPOCH):
@@ -173,6 +199,9 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
     except KeyboardInterrupt:
         print('-' * 89)
         print('Exiting from training early')
+    finally:
+        if getattr(dataloader, 'slot', None) is not None:
+            dataloader.bind(None)
     return model_dir
 
 

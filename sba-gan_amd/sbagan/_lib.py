@@ -150,6 +150,11 @@ SIGNATURES = {
     'sba_prdc_ball_counts': [P, I, I, P, I, I, I, P, P, I, P, P, P, L, P],
     'sba_batch_pyramid': [P, P, P, I, P, I, I, I, P, P, P, P, P, P, P],
     'sba_batch_masks': [P, P, P, P, I, I, P],
+    'sba_embed_dropout_fwd': [P, P, P, F, P, I, I, I, P],
+    'sba_embed_dropout_bwd': [P, P, F, P, P, I, I, I, P],
+    'sba_sqnorm_partials': [P, L, P, I, P],
+    'sba_clip_adam_prepare': [P, P, I, P, F, F, F, P, P],
+    'sba_adam_step_dscale': [P, P, P, P, P, P, P, L, F, F, F, P, P],
     'sba_set_deterministic': [I, P, L],
     'sba_set_reduce_scratch': [P, L],
     'sba_det_reset': [],

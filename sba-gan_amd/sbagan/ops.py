@@ -1890,6 +1890,44 @@ class LstmBidirTrainFn(torch.autograd.Function):
         return dx, None, dw_ih, dw_hh, db, db, None, None, None
 
 
+class EmbedDropoutFn(torch.autograd.Function):
+    """Embedding -> Dropout of RNN_ENCODER's training path with the keep mask as a tensor (sba_embed_dropout_fwd / _bwd):
+    out[b][t][c] = keep[b][t][c] ? weight[captions[b][t]][c] * scale : 0.  `keep` (uint8 [B][T][ninput]) is drawn by the
+    caller per batch, so the launch holds no random state and can be recorded (sbagan.damsm.DAMSMSlotStep).  The
+    backward ADDS the weight's gradient straight into weight.grad (the parameter's view of its flat gradient buffer,
+    cleared by zero_grad) and hands autograd nothing for it."""
+
+    @staticmethod
+    def forward(ctx, captions, weight, keep, scale):
+        _need_gpu(captions)
+        B, T = captions.shape
+        ntoken, ninput = weight.shape
+        if captions.dtype != torch.int64 or not captions.is_contiguous():
+            raise ValueError('EmbedDropoutFn: captions must be contiguous int64 [B][T]')
+        if weight.dtype != torch.float32 or not weight.is_contiguous() or ninput % 4:
+            raise ValueError('EmbedDropoutFn: weight must be contiguous f32 [ntoken][ninput], ninput % 4 == 0')
+        if keep.dtype != torch.uint8 or tuple(keep.shape) != (B, T, ninput) or not keep.is_contiguous():
+            raise ValueError('EmbedDropoutFn: keep must be contiguous uint8 [%d][%d][%d]' % (B, T, ninput))
+        out = torch.empty((B, T, ninput), dtype=torch.float32, device=captions.device)
+        call('sba_embed_dropout_fwd', _p(captions), _p(weight), _p(keep), float(scale), _p(out), B * T, ntoken, ninput,
+             _stream())
+        ctx.captions, ctx.weight, ctx.keep, ctx.scale = captions, weight, keep, float(scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        captions, weight, keep = ctx.captions, ctx.weight, ctx.keep
+        B, T = captions.shape
+        ntoken, ninput = weight.shape
+        dW = param_grad(weight)
+        if dW.dtype != torch.float32 or not dW.is_contiguous():
+            raise ValueError('EmbedDropoutFn: weight.grad must be contiguous f32')
+        dout = dout.float().contiguous()
+        call('sba_embed_dropout_bwd', _p(captions), _p(keep), ctx.scale, _p(dout), _p(dW), B * T, ntoken, ninput,
+             _stream())
+        return None, None, None, None
+
+
 # ----------------------------------------------------------------------------
 # evaluation: R-precision ranking (sbagan/rprecision.py)
 def rprec_rank(cnn, true_emb, pool, idx, eps=1e-8, want_scores=False):
