@@ -715,6 +715,30 @@ int sba_prdc_ball_counts(const float* a, int na, int lda, const float* b, int nb
                          const double* radius_b, int splits, int32_t* in_b, int32_t* in_own, void* ws, int64_t ws_bytes,
                          void* stream);
 
+/* Kernel Inception Distance (evaluation; sbagan/kid.py): sums of the polynomial kernel
+ *     k(x, y) = (x . y / D + 1)^3
+ * over pairs of gathered f32 feature rows (rows as for the k-NN metrics above), one sum per subset, in float64:
+ *     sums[s] = sum over positions i < ma, j < mb (and i != j when exclude_diag) of k(a[idx_a[s][i]], b[idx_b[s][j]])
+ * The dot product runs on the f64 matrix instruction over the feature axis in ascending order (the f32 values are widened
+ * in registers, every product is exact); t = g / (double)D + 1.0, k = (t * t) * t.  The kernel matrix is never written.
+ * idx_a [subsets][ma] / idx_b [subsets][mb]: int32 row numbers into a [na][lda] / b [nb][ldb]; a null vector means the
+ *   rows 0 .. m - 1 for every subset.  An index outside [0, n) is never turned into an address: its row reads as zeros
+ *   and every pair it belongs to is left out of the sum, like a position past m in the last tile.
+ * exclude_diag: the pairs of EQUAL POSITION are left out (by position, never by value or by subtraction); ma == mb.
+ * One launch covers all subsets: grid (blocks of 64 A positions, column splits, subsets); every workgroup adds its
+ *   elements in a fixed order and writes one partial to `ws`, and a second small launch adds the partials of a subset in
+ *   (block, split) order.  splits: 0 = the library's choice (enough for 512 workgroups), capped at 32 and at the number
+ *   of 64-position B tiles.  ws: 8-byte aligned, at least sba_kid_workspace_bytes(ma, mb, subsets, splits) bytes (-1 for
+ *   bad arguments; 0 when a subset has a single partial, which then goes to sums directly and ws may be null).
+ *   The same arguments give the same bits; no atomics, no memset, no allocation.
+ * SBA_E_ARG before any launch unless D >= 64, D % 64 == 0, rows 16-byte aligned, ld >= D, ld % 4 == 0, na, nb, ma, mb
+ *   >= 1, 1 <= subsets <= 1024, 0 <= splits <= 32, exclude_diag only with ma == mb, sums non-null and 8-byte aligned,
+ *   index vectors 4-byte aligned, and the workspace large enough. */
+int64_t sba_kid_workspace_bytes(int ma, int mb, int subsets, int splits);
+int sba_kid_kernel_sums(const float* a, int na, int lda, const int32_t* idx_a, int ma, const float* b, int nb, int ldb,
+                        const int32_t* idx_b, int mb, int D, int subsets, int exclude_diag, int splits, double* sums,
+                        void* ws, int64_t ws_bytes, void* stream);
+
 /* Training batches from the device-resident image cache (sbagan/device_data.py): gather, crop, mirror,
  * every scale of the image pyramid and the normalisation in ONE launch, bit-identical to the PIL data path.
  * cache: all images back to back, each HWC uint8 [H_i][W_i][3]; offset[i] (int64): byte offset of image i; hw[i] = {H_i,

@@ -1,6 +1,7 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
+    [--kid]  [--kid_subsets N]  [--kid_subset_size M]
     [--device_data]  [--device_data_gb G]  [--replay]
     [--bert_dir DIR: the BERT entry points]
 
@@ -35,6 +36,20 @@ def _prdc(text):
     return k
 
 
+def _kid_subsets(text):
+    n = int(text)
+    if n < 1 or n > 1024:
+        raise argparse.ArgumentTypeError('N must be a subset count from 1 to 1024')
+    return n
+
+
+def _kid_subset_size(text):
+    m = int(text)
+    if m < 2:
+        raise argparse.ArgumentTypeError('M must be at least 2 rows a side')
+    return m
+
+
 def options(what, default_cfg, argv=None, bert=False):
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
@@ -64,6 +79,16 @@ def options(what, default_cfg, argv=None, bert=False):
                          'metrics, sbagan.prdc) between the real images of the split and the generated ones on the same '
                          'trunk features as --fid and write prdc.json; 0 = off, K from 1 to 8, 5 = the usual setting.  '
                          'On this project\'s own trunk and compute dtype: not comparable with published numbers')
+    ap.add_argument('--kid', dest='kid', action='store_true', default=False,
+                    help='sampling: also take the Kernel Inception Distance (the unbiased MMD^2 estimate under the '
+                         'kernel (x.y / D + 1)^3 with its standard deviation over subsets, sbagan.kid) between the real '
+                         'images of the split and the generated ones on the same trunk features as --fid and write '
+                         'kid.json.  On this project\'s own trunk and compute dtype: not comparable with published '
+                         'numbers')
+    ap.add_argument('--kid_subsets', dest='kid_subsets', type=_kid_subsets, default=100, metavar='N',
+                    help='with --kid: the number of subsets, 1 to 1024')
+    ap.add_argument('--kid_subset_size', dest='kid_subset_size', type=_kid_subset_size, default=1000, metavar='M',
+                    help='with --kid: rows per subset and side (at least 2); clamped to the smaller side')
     ap.add_argument('--device_data', dest='device_data', action='store_true', default=False,
                     help='training: decode the split once into a device-resident uint8 cache and make every batch '
                          'there -- crop, flip, every scale of the pyramid and the normalisation in one HIP launch '

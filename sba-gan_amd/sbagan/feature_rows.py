@@ -1,0 +1,60 @@
+"""The feature rows of the real and the generated images on the device, as the evaluators that need every row keep them
+(sbagan/prdc.py, sbagan/kid.py): per side one f32 [capacity][D] buffer that grows by doubling, appended to without a
+host-device sync per batch."""
+import torch
+
+from . import ops
+
+SIDES = ('real', 'fake')
+
+
+class FeatureRows(object):
+    """owner: the evaluator's name, for the messages"""
+
+    def __init__(self, owner, D, capacity=256):
+        if D < 64 or D % 64:
+            raise ValueError('%s: D must be a positive multiple of 64 (got %d)' % (owner, D))
+        if capacity < 1:
+            raise ValueError('%s: capacity must be >= 1 (got %d)' % (owner, capacity))
+        self.owner, self.D, self.capacity = owner, int(D), int(capacity)
+        self._rows = {}                             # side -> [buffer [capacity][D], rows held]
+
+    def _side(self, side):
+        if side not in SIDES:
+            raise ValueError("%s: side must be 'real' or 'fake' (got %r)" % (self.owner, side))
+        return side
+
+    def append(self, side, feats):
+        """one batch of feature rows [B][D] (f32, on the device); no host-device sync"""
+        side = self._side(side)
+        if not torch.is_tensor(feats) or feats.dim() != 2 or feats.shape[1] != self.D:
+            raise ValueError('%s: features must be a [B][%d] tensor (got %s)'
+                             % (self.owner, self.D, tuple(feats.shape) if torch.is_tensor(feats) else type(feats)))
+        ops._need_gpu(feats)
+        if feats.dtype != torch.float32:
+            raise TypeError('%s: features must be float32 (got %s)' % (self.owner, feats.dtype))
+        held = self._rows.get(side)
+        if held is None:
+            held = self._rows[side] = [torch.empty((self.capacity, self.D), dtype=torch.float32, device=feats.device), 0]
+        buf, n, B = held[0], held[1], feats.shape[0]
+        if n + B > buf.shape[0]:
+            cap = buf.shape[0]
+            while cap < n + B:
+                cap *= 2
+            grown = torch.empty((cap, self.D), dtype=torch.float32, device=buf.device)
+            grown[:n].copy_(buf[:n])
+            buf = held[0] = grown
+        buf[n:n + B].copy_(feats)
+        held[1] = n + B
+
+    def count(self, side):
+        """rows held for a side"""
+        held = self._rows.get(self._side(side))
+        return held[1] if held else 0
+
+    def rows(self, side):
+        """the rows held for a side: f32 [n][D] on the device (a view of the buffer)"""
+        held = self._rows.get(self._side(side))
+        if held is None:
+            raise RuntimeError('%s: the %s side holds no rows' % (self.owner, side))
+        return held[0][:held[1]]

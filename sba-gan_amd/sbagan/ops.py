@@ -2246,6 +2246,66 @@ def prdc_ball_counts(a, b, radius_a=None, radius_b=None, splits=0):
 
 
 # ----------------------------------------------------------------------------
+# evaluation: Kernel Inception Distance (sbagan/kid.py)
+KID_MAX_SUBSETS, KID_MAX_SPLITS = 1024, 32
+
+
+def _kid_indices(name, idx, what, n):
+    """the host int32 [subsets][m] array of an index argument, every entry checked against [0, n)"""
+    if torch.is_tensor(idx):
+        if idx.device.type != 'cpu':
+            raise ValueError('%s: %s must be on the CPU: it is range-checked there before the upload' % (name, what))
+        idx = idx.numpy()
+    idx = np.asarray(idx)
+    if idx.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise TypeError('%s: %s must be int32 or int64 (got %s)' % (name, what, idx.dtype))
+    if idx.ndim != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise ValueError('%s: %s must be [subsets >= 1][m >= 1] (got %s)' % (name, what, idx.shape))
+    if idx.min() < 0 or idx.max() >= n:
+        raise ValueError('%s: %s holds a row number outside [0, %d)' % (name, what, n))
+    return np.array(idx, dtype=np.int32, order='C')         # (a copy: the caller's array may be read-only)
+
+
+def kid_kernel_sums(a, b, idx_a=None, idx_b=None, exclude_diag=False, splits=0):
+    """sums [subsets] f64 on the device (sba_kid_kernel_sums): for every subset s the sum over the positions i < ma,
+    j < mb of k(a[idx_a[s][i]], b[idx_b[s][j]]), k(x, y) = (x . y / D + 1)^3 in float64 on the f64 matrix instruction;
+    with exclude_diag (ma == mb) the pairs of equal POSITION are left out.  a [na][D], b [nb][D]: f32 rows on the device
+    as for prdc_knn_radius.  idx_a [subsets][ma], idx_b [subsets][mb]: int32 / int64 row numbers on the HOST (numpy or
+    CPU tensors), range-checked here against na / nb and then uploaded; None = the rows 0 .. n - 1 for every subset
+    (both None: one subset).  splits: column parts of the launch (0 = the library's choice); the sums of different
+    values differ by rounding only, the same value gives the same bits.  The workspace is a torch allocation on the
+    current stream; no host sync.  Everything is checked before the launch: TypeError for a dtype, ValueError for a
+    shape, a stride, an alignment, an index, exclude_diag or splits."""
+    name = 'kid_kernel_sums'
+    na, D, lda = _prdc_rows(name, a, 'a')
+    nb, _, ldb = _prdc_rows(name, b, 'b', a.device, D)
+    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits <= KID_MAX_SPLITS:
+        raise ValueError('%s: splits must be an integer in [0, %d], 0 = the library\'s choice (got %r)'
+                         % (name, KID_MAX_SPLITS, splits))
+    ia = _kid_indices(name, idx_a, 'idx_a', na) if idx_a is not None else None
+    ib = _kid_indices(name, idx_b, 'idx_b', nb) if idx_b is not None else None
+    if ia is not None and ib is not None and ia.shape[0] != ib.shape[0]:
+        raise ValueError('%s: idx_a holds %d subsets, idx_b %d' % (name, ia.shape[0], ib.shape[0]))
+    subsets = ia.shape[0] if ia is not None else ib.shape[0] if ib is not None else 1
+    ma = ia.shape[1] if ia is not None else na
+    mb = ib.shape[1] if ib is not None else nb
+    if subsets > KID_MAX_SUBSETS:
+        raise ValueError('%s: at most %d subsets a launch (got %d)' % (name, KID_MAX_SUBSETS, subsets))
+    if exclude_diag and ma != mb:
+        raise ValueError('%s: exclude_diag pairs equal positions: ma (%d) must equal mb (%d)' % (name, ma, mb))
+    nbytes = int(_lib.lib.sba_kid_workspace_bytes(ma, mb, subsets, splits))
+    if nbytes < 0:
+        raise ValueError('%s: no workspace size for %d x %d rows, %d subsets, %d splits' % (name, ma, mb, subsets, splits))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device) if nbytes else None
+    ia_dev = torch.from_numpy(ia).to(a.device) if ia is not None else None
+    ib_dev = torch.from_numpy(ib).to(a.device) if ib is not None else None
+    sums = torch.empty(subsets, dtype=torch.float64, device=a.device)
+    call('sba_kid_kernel_sums', _p(a), na, lda, _p(ia_dev), ma, _p(b), nb, ldb, _p(ib_dev), mb, D, subsets,
+         1 if exclude_diag else 0, splits, _p(sums), _p(ws), nbytes, _stream())
+    return sums
+
+
+# ----------------------------------------------------------------------------
 # training batches from the device-resident image cache (sbagan/device_data.py)
 def check_pyramid_shape(T, levels):
     """ValueError unless sba_batch_pyramid takes a T px crop at `levels` scales"""

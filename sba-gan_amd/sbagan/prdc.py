@@ -3,7 +3,8 @@ precision and recall, Kynkaanniemi et al. 2019; density and coverage, Naeem et a
 trunk -- the same f32 2048-d pooled Mixed_7c rows FID uses (`InceptionHIP.last_pooled` / `pooled_features`).
 
 Per side ('real', 'fake') the rows are appended to a device buffer that grows by doubling, without a host-device sync per
-batch.  result() runs four launches of the f64 matrix-core distance kernel of csrc/prdc.hip and reads back once:
+batch (sbagan/feature_rows.py).  result() runs four launches of the f64 matrix-core distance kernel of csrc/prdc.hip and
+reads back once:
 
     r_real = ops.prdc_knn_radius(real, k)     r_fake = ops.prdc_knn_radius(fake, k)
         the squared distance from a row to its k-th nearest OTHER row of its own side (self excluded by index, so a
@@ -25,8 +26,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .feature_rows import SIDES, FeatureRows
 
-SIDES = ('real', 'fake')
 FIELDS = ('precision', 'recall', 'density', 'coverage', 'k', 'n_real', 'n_fake', 'dtype')
 
 
@@ -55,20 +56,11 @@ class PRDC(object):
     key: a description of the run, kept for the caller; dtype: the compute-dtype name reported in the result."""
 
     def __init__(self, features, D=2048, k=5, key='', dtype=None, capacity=256):
-        if D < 64 or D % 64:
-            raise ValueError('PRDC: D must be a positive multiple of 64 (got %d)' % D)
+        self.store = FeatureRows('PRDC', D, capacity)       # (sbagan.kid.KID(rows=<this>) reads it too)
         if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.PRDC_MAX_K:
             raise ValueError('PRDC: k must be an integer in [1, %d] (got %r)' % (ops.PRDC_MAX_K, k))
-        if capacity < 1:
-            raise ValueError('PRDC: capacity must be >= 1 (got %d)' % capacity)
         self.features, self.D, self.k, self.key, self.capacity = features, int(D), k, str(key), int(capacity)
         self.dtype = str(dtype if dtype is not None else ops.compute_dtype()).replace('torch.', '')
-        self._rows = {}                             # side -> [buffer [capacity][D], rows held]
-
-    def _side(self, side):
-        if side not in SIDES:
-            raise ValueError("PRDC: side must be 'real' or 'fake' (got %r)" % (side,))
-        return side
 
     def update(self, side, images):
         """one batch of images of either side"""
@@ -78,38 +70,15 @@ class PRDC(object):
 
     def update_features(self, side, feats):
         """one batch of feature rows [B][D] (f32, on the device); no host-device sync"""
-        side = self._side(side)
-        if not torch.is_tensor(feats) or feats.dim() != 2 or feats.shape[1] != self.D:
-            raise ValueError('PRDC: features must be a [B][%d] tensor (got %s)'
-                             % (self.D, tuple(feats.shape) if torch.is_tensor(feats) else type(feats)))
-        ops._need_gpu(feats)
-        if feats.dtype != torch.float32:
-            raise TypeError('PRDC: features must be float32 (got %s)' % feats.dtype)
-        held = self._rows.get(side)
-        if held is None:
-            held = self._rows[side] = [torch.empty((self.capacity, self.D), dtype=torch.float32, device=feats.device), 0]
-        buf, n, B = held[0], held[1], feats.shape[0]
-        if n + B > buf.shape[0]:
-            cap = buf.shape[0]
-            while cap < n + B:
-                cap *= 2
-            grown = torch.empty((cap, self.D), dtype=torch.float32, device=buf.device)
-            grown[:n].copy_(buf[:n])
-            buf = held[0] = grown
-        buf[n:n + B].copy_(feats)
-        held[1] = n + B
+        self.store.append(side, feats)
 
     def count(self, side):
         """rows held for a side"""
-        held = self._rows.get(self._side(side))
-        return held[1] if held else 0
+        return self.store.count(side)
 
     def rows(self, side):
         """the rows held for a side: f32 [n][D] on the device (a view of the buffer)"""
-        held = self._rows.get(self._side(side))
-        if held is None:
-            raise RuntimeError('PRDC: the %s side holds no rows' % side)
-        return held[0][:held[1]]
+        return self.store.rows(side)
 
     def result(self):
         for side in SIDES:

@@ -436,6 +436,22 @@ class condGANTrainer(object):
         dtype = str(ops.compute_dtype()).replace('torch.', '')
         return PRDC(image_encoder.pooled_features, D=2048, k=self.prdc, dtype=dtype)
 
+    kid = False                 # --kid: sampling() also takes the Kernel Inception Distance
+    kid_subsets = 100           # --kid_subsets N
+    kid_subset_size = 1000      # --kid_subset_size M: rows per subset and side, clamped to the smaller side
+    kid_seed = 100              # of the evaluator's own generator for the subset draws
+    kid_result = None           # the result dict of the last sampling() with kid on
+    kid_evaluator = None
+
+    def _kid_evaluator(self, image_encoder, prdc):
+        """sbagan.kid.KID on the pooled trunk feature of `image_encoder` (an InceptionHIP); with a PRDC evaluator it
+        reads that one's rows and stores none"""
+        from sbagan import ops
+        from sbagan.kid import KID
+        dtype = str(ops.compute_dtype()).replace('torch.', '')
+        return KID(image_encoder.pooled_features, D=2048, subsets=self.kid_subsets, subset_size=self.kid_subset_size,
+                   seed=self.kid_seed, dtype=dtype, rows=prdc)
+
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
         root = self._output_root()
@@ -445,14 +461,20 @@ class condGANTrainer(object):
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
         evaluator = self._r_precision_evaluator(text_encoder) if self.r_precision else None
-        fid = fid_real = prdc = None
-        if self.fid or self.prdc:       # one image encoder serves the three evaluators
+        fid = fid_real = prdc = kid = None
+        if self.fid or self.prdc or self.kid:       # one image encoder serves the four evaluators
             image_encoder = evaluator.image_encoder if evaluator is not None else self._load_image_encoder()
         if self.fid:
             fid = self._fid_evaluator(image_encoder, split_dir)
             fid_real = not fid.is_loaded('real')
         if self.prdc:
             prdc = self._prdc_evaluator(image_encoder)
+        if self.kid:
+            kid = self._kid_evaluator(image_encoder, prdc)
+        # who takes the fake rows and who the real ones: FID its moments, PRDC the rows, KID the rows unless PRDC has them
+        keeps = [ev for ev in (prdc, kid if prdc is None else None) if ev is not None]
+        takes_fake = ([fid] if fid is not None else []) + keeps
+        takes_real = ([fid] if fid_real else []) + keeps
         noise = torch.empty(self._noise_shape(self.batch_size), device=self.device)
         made = set()
         for nbatch, data in enumerate(self.data_loader):
@@ -463,18 +485,15 @@ class condGANTrainer(object):
             last = fake_imgs[-1]
             if evaluator is not None:
                 evaluator.update(last, sent_emb, class_ids)
-            if fid is not None or prdc is not None:     # each batch goes through the trunk once, for all of them
+            if takes_fake:                      # each batch goes through the trunk once, for all of them
                 if evaluator is None:           # (R-precision has otherwise just run this batch through it)
                     image_encoder.pooled_features(last)
-                for ev in (fid, prdc):
-                    if ev is not None:
-                        ev.update_features('fake', image_encoder.last_pooled)
-                if fid_real or prdc is not None:        # with cached FID statistics: encoded for PRDC alone
+                for ev in takes_fake:
+                    ev.update_features('fake', image_encoder.last_pooled)
+                if takes_real:                  # with cached FID statistics: encoded for PRDC and KID alone
                     real_feats = image_encoder.pooled_features(real_imgs[-1])
-                    if fid_real:
-                        fid.update_features('real', real_feats)
-                    if prdc is not None:
-                        prdc.update_features('real', real_feats)
+                    for ev in takes_real:
+                        ev.update_features('real', real_feats)
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
         if evaluator is not None:
@@ -503,6 +522,14 @@ class condGANTrainer(object):
                   'coverage %.4f' % (res['k'], res['n_real'], res['n_fake'], res['dtype'], res['precision'],
                                      res['recall'], res['density'], res['coverage']))
             with open(os.path.join(out_dir, 'prdc.json'), 'w') as f:
+                json.dump(res, f, indent=1, sort_keys=True)
+        if kid is not None:
+            self.kid_evaluator = kid
+            res = self.kid_result = kid.result()
+            print('KID (%d subsets of %d, %d real, %d generated images, %s trunk): %.6g +- %.6g'
+                  % (res['subsets'], res['subset_size'], res['n_real'], res['n_fake'], res['dtype'], res['kid'],
+                     res['kid_std']))
+            with open(os.path.join(out_dir, 'kid.json'), 'w') as f:
                 json.dump(res, f, indent=1, sort_keys=True)
         return out_dir
 
