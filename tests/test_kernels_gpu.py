@@ -1362,7 +1362,9 @@ def test_word_attention_matrix_core_backward(dev, shape):
     cores with hi + lo split keys, softmax backward in-lane, dh with hi + lo split dS, dsrc over the query axis through
     LDS -- against torch autograd in f32 on the same bf16 inputs.  dh is a bf16 tensor (2^-9 per element); dsrc contracts
     bf16-rounded dS / probabilities (as the VALU kernel does).  Ragged query counts, L up to 32, both mask modes, dctx
-    read from a channel slice, dh accumulated onto an existing gradient, several tiles per wave (20 x 4096 queries)."""
+    read from a channel slice, dh accumulated onto an existing gradient.  Every shape here selects ONE tile per wave (the
+    largest, 20 x 4096 queries, is 2560 tiles, below the 4096 at which the host picks two); two and four tiles per wave,
+    the VALU arms and every edge are in tests/test_attention_kernels_gpu.py, element by element against float64."""
     from sbagan._lib import call
     B, L, Q, mode, accumulate = shape
     idf = 32
@@ -1399,8 +1401,9 @@ def test_word_attention_matrix_core_forward(dev, shape):
     """The bf16 forward runs both contractions (GlobalAttention.py:103,117) on v_mfma_f32_32x32x16_bf16 with the keys
     and the probabilities split into hi + lo bf16 parts: it must agree with an f32 evaluation of the same bf16 inputs to
     f32 rounding (NOT to bf16 rounding: only the stored context is rounded), for ragged query counts, L up to 32, both
-    mask modes, an output written into a channel slice, and the optional attention map; a fully masked row gives NaN
-    exactly where the reference's softmax does."""
+    mask modes, an output written into a channel slice, and the optional attention map.  No row is fully masked here
+    (word 0 is always live); that a fully masked row gives NaN exactly where the reference's softmax does is checked by
+    tests/test_attention_kernels_gpu.py (test_fully_masked_row), with every other arm of the dispatch."""
     from sbagan._lib import call
     B, idf, L, Q, mode = shape
     g = torch.Generator().manual_seed(5)
