@@ -2,14 +2,13 @@
 // of f32 feature rows on the f64 matrix instruction (v_mfma_f64_16x16x4_f64), and the mean / covariance / trace from them.
 // The f32 inputs are widened in registers: a product of two f32 values is exact in f64, so the only rounding is the f64
 // accumulation.  No atomics, no workspace, a fixed summation order.
-#include "common.h"
+#include "f64_tile.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;    // accumulator of one 16x16x4 f64 MFMA
-
-constexpr int FID_TILE = 64;                    // gram tile edge: one workgroup per tile pair (ti <= tj)
-constexpr int FID_THREADS = 256;                // four waves, each a 32 x 32 quadrant as 2 x 2 MFMA tiles
+constexpr int FID_TILE = F64T_TILE;             // gram tile edge: one workgroup per tile pair (ti <= tj)
+constexpr int FID_THREADS = F64T_THREADS;       // (lane map and MFMA step of f64_tile.h; the rows are the reduction axis
+                                                // here, so the row-major staging below is this file's own)
 constexpr int FID_KC = 32;                      // feature rows staged per chunk
 constexpr int FID_LD = 2 * FID_TILE + 16;       // LDS row stride in floats: the 4 rows of one MFMA operand read fall
                                                 // into 4 distinct groups of 16 banks
@@ -36,9 +35,8 @@ __device__ __forceinline__ void fid_stage(float* __restrict__ buf, const float4 
 }
 
 // gram[i0 .. i0 + 63][j0 .. j0 + 63] += X[:, i0 ..]^T X[:, j0 ..] for the upper-triangular tile pair of this workgroup;
-// the diagonal workgroups also add their 64 column sums.  MFMA operands (f32 16x16x4 lane map, one f64 per lane):
-// A[i = lane & 15][k = lane >> 4] = x[k][i], B[k = lane >> 4][j = lane & 15] = x[k][j], so both are the same kind of
-// read of staged row k.  C/D of the f64 instruction: col = lane & 15, row = (lane >> 4) + 4 * reg.
+// the diagonal workgroups also add their 64 column sums.  MFMA operands (lane map of f64_tile.h): A[i][k] = x[k][i],
+// B[k][j] = x[k][j], so both are the same kind of read of staged row k.
 __global__ __launch_bounds__(FID_THREADS) void fid_accumulate_kernel(const float* __restrict__ x, int n, int D, int64_t ldx,
                                                                      double* __restrict__ sum, double* __restrict__ gram) {
     __shared__ __attribute__((aligned(16))) float sh[2][FID_KC * FID_LD];
@@ -54,9 +52,7 @@ __global__ __launch_bounds__(FID_THREADS) void fid_accumulate_kernel(const float
     const int i0 = ti * FID_TILE, j0 = tj * FID_TILE;
     const bool diag = ti == tj;
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;      // quadrant of this wave inside the tile
-    const int lc = lane & 15, lk = lane >> 4;
+    const F64Lanes l = f64t_lanes();
 
     f64x4_t acc[2][2];
 #pragma unroll
@@ -79,13 +75,9 @@ __global__ __launch_bounds__(FID_THREADS) void fid_accumulate_kernel(const float
         const int steps = (rows + 3) >> 2;                      // (rows past n inside the last step are staged zeros)
         // (rolled on purpose: the fully unrolled K loop measured 9 % slower, profiles/fid_bench.json)
         for (int s = 0; s < steps; ++s) {
-            const float* __restrict__ row = buf + (4 * s + lk) * FID_LD;
-            const double a0 = (double)row[wi + lc], a1 = (double)row[wi + 16 + lc];
-            const double b0 = (double)row[FID_TILE + wj + lc], b1 = (double)row[FID_TILE + wj + 16 + lc];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+            const float* __restrict__ row = buf + (4 * s + l.lk) * FID_LD;
+            f64t_mfma((double)row[l.wi + l.lc], (double)row[l.wi + 16 + l.lc], (double)row[FID_TILE + l.wj + l.lc],
+                      (double)row[FID_TILE + l.wj + 16 + l.lc], acc);
         }
         if (diag) {
 #pragma unroll
@@ -95,15 +87,7 @@ __global__ __launch_bounds__(FID_THREADS) void fid_accumulate_kernel(const float
         __syncthreads();
     }
 
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double* g = gram + (int64_t)(i0 + wi + 16 * a + lk + 4 * r) * D + (j0 + wj + 16 * b + lc);
-                *g += acc[a][b][r];
-            }
+    f64t_each(l, acc, [&](int i, int j, double g) { gram[(int64_t)(i0 + i) * D + (j0 + j)] += g; });
     if (diag) {
         sh_sum[threadIdx.x] = csum;
         __syncthreads();
@@ -149,14 +133,12 @@ __global__ __launch_bounds__(256) void fid_mu_trace_kernel(const double* __restr
     if (threadIdx.x == 0) *trace = sh[0];
 }
 
-inline bool fid_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int sba_fid_accumulate(const float* x, int n, int D, int ldx, double* sum, double* gram, void* stream) {
     if (!x || !sum || !gram) return SBA_E_ARG;
     if (n < 1 || D < FID_TILE || D % FID_TILE || ldx < D || ldx % 4) return SBA_E_ARG;
-    if (!fid_aligned(x, 16) || !fid_aligned(sum, 8) || !fid_aligned(gram, 8)) return SBA_E_ARG;
+    if (!f64t_aligned(x, 16) || !f64t_aligned(sum, 8) || !f64t_aligned(gram, 8)) return SBA_E_ARG;
     const int T = D / FID_TILE;
     SBA_LAUNCH(fid_accumulate_kernel, dim3(T * (T + 1) / 2), dim3(FID_THREADS), 0, (hipStream_t)stream, x, n, D,
                (int64_t)ldx, sum, gram);
@@ -167,8 +149,8 @@ extern "C" int sba_fid_finalize(const double* sum, const double* gram, int64_t n
                                 double* trace, void* stream) {
     if (!sum || !gram || !mu || !sigma || !trace) return SBA_E_ARG;
     if (n < 2 || D < FID_TILE || D % FID_TILE) return SBA_E_ARG;
-    if (!fid_aligned(sum, 8) || !fid_aligned(gram, 8) || !fid_aligned(mu, 8) || !fid_aligned(sigma, 8) ||
-        !fid_aligned(trace, 8))
+    if (!f64t_aligned(sum, 8) || !f64t_aligned(gram, 8) || !f64t_aligned(mu, 8) || !f64t_aligned(sigma, 8) ||
+        !f64t_aligned(trace, 8))
         return SBA_E_ARG;
     const hipStream_t st = (hipStream_t)stream;
     SBA_LAUNCH(fid_sigma_kernel, dim3(D / 64, D / 64), dim3(256), 0, st, sum, gram, (double)n, D, sigma);

@@ -6,52 +6,12 @@
 // d2(i, j) has the same bits whichever tile or column split computed it, and d2(i, j) == d2(j, i) bitwise for A = B.
 // No atomics, no memset, no allocation: partial results of column splits go to a caller-provided workspace and a second
 // small launch merges them in split order.
-#include "common.h"
+#include "f64_tile.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;    // accumulator of one 16x16x4 f64 MFMA
-
-constexpr int PRDC_TILE = 64;                   // A rows per workgroup and B rows per tile
-constexpr int PRDC_THREADS = 256;               // four waves, each a 32 x 32 quadrant as 2 x 2 MFMA tiles
-constexpr int PRDC_KC = 32;                     // features staged per chunk
-constexpr int PRDC_LD = PRDC_KC + 2;            // LDS row stride in floats: the 4-byte operand reads of a 32-lane group (16
-                                                // rows x 2 features) fall on bank (2 row + feature) mod 32, all distinct;
-                                                // a staged row is 8-byte aligned, so it is stored as two float2
-constexpr int PRDC_VEC = 2 * PRDC_TILE * PRDC_KC / 4 / PRDC_THREADS;   // float4 loads per thread and chunk (4)
-constexpr int PRDC_TLD = PRDC_TILE + 1;         // row stride of the finished d2 tile in doubles
+constexpr int PRDC_TLD = F64T_TILE + 1;         // row stride of the finished d2 tile in doubles
 constexpr int PRDC_K = 8;                       // the longest neighbour list
-constexpr int PRDC_MAX_SPLITS = 32;
-constexpr int PRDC_FILL = 512;                  // workgroups the library's own split choice aims at (2 per CU)
-
-// features d0 .. d0 + KC - 1 of the A rows i0 .. i0 + 63 and the B rows j0 .. j0 + 63 -> registers; a row past the end of
-// its set reads as zeros.  Slot e: staged row e >> 3 (0 .. 63 of A, 64 .. 127 of B), features 4 (e & 7) .. + 3.
-__device__ __forceinline__ void prdc_fetch(float4 (&v)[PRDC_VEC], const float* __restrict__ a, int na, int64_t lda, int i0,
-                                           const float* __restrict__ b, int nb, int64_t ldb, int j0, int d0) {
-#pragma unroll
-    for (int s = 0; s < PRDC_VEC; ++s) {
-        const int e = threadIdx.x + PRDC_THREADS * s;
-        const int r = e >> 3, c = (e & 7) << 2;
-        const bool isa = r < PRDC_TILE;
-        const int row = isa ? i0 + r : j0 + r - PRDC_TILE;
-        const bool ok = row < (isa ? na : nb);
-        const float* __restrict__ p = (isa ? a + (int64_t)row * lda : b + (int64_t)row * ldb) + d0 + c;
-        v[s] = ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-// registers -> LDS, and the squared norm of the staged rows: slot s of this thread always holds the same 4 features of the
-// same row, so nrm[s] adds those features over the chunks in ascending order
-__device__ __forceinline__ void prdc_stage(float* __restrict__ buf, const float4 (&v)[PRDC_VEC], double (&nrm)[PRDC_VEC]) {
-#pragma unroll
-    for (int s = 0; s < PRDC_VEC; ++s) {
-        const int e = threadIdx.x + PRDC_THREADS * s;
-        float* __restrict__ p = buf + (e >> 3) * PRDC_LD + ((e & 7) << 2);
-        *reinterpret_cast<float2*>(p) = make_float2(v[s].x, v[s].y);
-        *reinterpret_cast<float2*>(p + 2) = make_float2(v[s].z, v[s].w);
-        const double x0 = (double)v[s].x, x1 = (double)v[s].y, x2 = (double)v[s].z, x3 = (double)v[s].w;
-        nrm[s] = fma(x3, x3, fma(x2, x2, fma(x1, x1, fma(x0, x0, nrm[s]))));
-    }
-}
 
 // ascending list of the PRDC_K smallest values seen
 __device__ __forceinline__ void prdc_insert(double (&l)[PRDC_K], double v) {
@@ -70,32 +30,32 @@ __device__ __forceinline__ void prdc_insert(double (&l)[PRDC_K], double v) {
 // columns, ascending, +inf where there are fewer; with `direct` (one split) radius2[i] = entry k - 1 instead.
 // MODE 1, ball counts: out_i[(split * na + i) * 2 ..] = #{j : d2 <= rb[j]}, #{j : d2 <= ra[i]} over this split's columns;
 // with `direct` they go to in_b[i] / in_own[i].  A null radius vector makes its count 0 (and `direct` skips the write).
-// blockIdx.x: block of 64 A rows; blockIdx.y: column split, B tiles [y T / S, (y + 1) T / S).
-// MFMA operands (f32 16x16x4 lane map, one f64 per lane): A[i = lane & 15][k = lane >> 4] = a[i][d + k],
-// B[k = lane >> 4][j = lane & 15] = b[j][d + k]: both the same kind of read of a staged row.  C/D of the f64 instruction:
-// col = lane & 15, row = (lane >> 4) + 4 * reg.
+// blockIdx.x: block of 64 A rows; blockIdx.y: column split (f64t_split_range).
 template <int MODE>
-__global__ __launch_bounds__(PRDC_THREADS) void prdc_kernel(const float* __restrict__ a, int na, int64_t lda,
+__global__ __launch_bounds__(F64T_THREADS) void prdc_kernel(const float* __restrict__ a, int na, int64_t lda,
                                                             const float* __restrict__ b, int nb, int64_t ldb, int D,
                                                             const double* __restrict__ ra, const double* __restrict__ rb,
                                                             int k, int direct, double* __restrict__ out_d,
                                                             int32_t* __restrict__ out_i0, int32_t* __restrict__ out_i1) {
-    __shared__ __attribute__((aligned(16))) float sh[2][2 * PRDC_TILE * PRDC_LD];
-    __shared__ double sh_part[2 * PRDC_TILE][8];        // per staged row: the norm partials of its 8 feature groups
-    __shared__ double sh_norm[2 * PRDC_TILE];
-    static_assert(sizeof(double) * PRDC_TILE * PRDC_TLD <= sizeof(sh), "the d2 tile lives in the staging buffers");
+    __shared__ __attribute__((aligned(16))) float sh[2][F64T_STAGE];
+    __shared__ double sh_part[2 * F64T_TILE][8];        // per staged row: the norm partials of its 8 feature groups
+    __shared__ double sh_norm[2 * F64T_TILE];
+    static_assert(sizeof(double) * F64T_TILE * PRDC_TLD <= sizeof(sh), "the d2 tile lives in the staging buffers");
     double* sh_d2 = reinterpret_cast<double*>(&sh[0][0]);      // the finished tile, afterwards the lists / counts
                                                         // of a row: over the staging buffers, which are idle by then
 
-    const int i0 = blockIdx.x * PRDC_TILE;
-    const int tiles = (nb + PRDC_TILE - 1) / PRDC_TILE, S = gridDim.y;
-    const int t0 = (int)((int64_t)blockIdx.y * tiles / S), t1 = (int)((int64_t)(blockIdx.y + 1) * tiles / S);
+    const int i0 = blockIdx.x * F64T_TILE;
+    int t0, t1;
+    f64t_split_range(nb, t0, t1);
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;      // quadrant of this wave inside the tile
-    const int lc = lane & 15, lk = lane >> 4;
-    const int er = lane, eq = wave;                             // epilogue: row of the tile, 16-column quarter
+    const F64Lanes l = f64t_lanes();
+    const int er = threadIdx.x & 63, eq = threadIdx.x >> 6;     // epilogue: row of the tile, 16-column quarter
     const int gi = i0 + er;
+    const int sr = threadIdx.x >> 3;                            // staged row of slot 0; slot v: + 32 v
+
+    const float* row[F64T_VEC];
+    row[0] = f64t_row(a, na, lda, nullptr, na, i0 + sr);
+    row[1] = f64t_row(a, na, lda, nullptr, na, i0 + sr + 32);
 
     double best[PRDC_K];
 #pragma unroll
@@ -103,62 +63,51 @@ __global__ __launch_bounds__(PRDC_THREADS) void prdc_kernel(const float* __restr
     int cnt_b = 0, cnt_own = 0;
     const double r_own = (MODE == 1 && ra && gi < na) ? ra[gi] : 0.0;
 
-    const int chunks = D / PRDC_KC;
+    const int chunks = D / F64T_KC;
     for (int t = t0; t < t1; ++t) {
-        const int j0 = t * PRDC_TILE;
+        const int j0 = t * F64T_TILE;
+        row[2] = f64t_row(b, nb, ldb, nullptr, nb, j0 + sr);
+        row[3] = f64t_row(b, nb, ldb, nullptr, nb, j0 + sr + 32);
         f64x4_t acc[2][2];
 #pragma unroll
         for (int x = 0; x < 2; ++x)
 #pragma unroll
             for (int y = 0; y < 2; ++y) acc[x][y] = f64x4_t{0.0, 0.0, 0.0, 0.0};
-        double nrm[PRDC_VEC];
+        double nrm[F64T_VEC];
 #pragma unroll
-        for (int s = 0; s < PRDC_VEC; ++s) nrm[s] = 0.0;
+        for (int s = 0; s < F64T_VEC; ++s) nrm[s] = 0.0;
+        // the squared norm of the staged rows: slot s of this thread always holds the same 4 features of the same row, so
+        // nrm[s] adds those features over the chunks in ascending order
+        const auto norms = [&](int s, const float4& x) {
+            const double x0 = (double)x.x, x1 = (double)x.y, x2 = (double)x.z, x3 = (double)x.w;
+            nrm[s] = fma(x3, x3, fma(x2, x2, fma(x1, x1, fma(x0, x0, nrm[s]))));
+        };
 
-        float4 v[PRDC_VEC];
-        prdc_fetch(v, a, na, lda, i0, b, nb, ldb, j0, 0);
+        float4 v[F64T_VEC];
+        f64t_fetch(v, row, 0);
         __syncthreads();                // the previous tile's epilogue has read the d2 tile these buffers held
-        prdc_stage(sh[0], v, nrm);
+        f64t_stage(sh[0], v, norms);
         __syncthreads();
         for (int c = 0; c < chunks; ++c) {
-            const float* __restrict__ buf = sh[c & 1];
             const bool more = c + 1 < chunks;
-            if (more) prdc_fetch(v, a, na, lda, i0, b, nb, ldb, j0, (c + 1) * PRDC_KC);
-            for (int s = 0; s < PRDC_KC / 4; ++s) {
-                const int d = 4 * s + lk;
-                const double a0 = (double)buf[(wi + lc) * PRDC_LD + d], a1 = (double)buf[(wi + 16 + lc) * PRDC_LD + d];
-                const double b0 = (double)buf[(PRDC_TILE + wj + lc) * PRDC_LD + d];
-                const double b1 = (double)buf[(PRDC_TILE + wj + 16 + lc) * PRDC_LD + d];
-                acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-            }
-            if (more) prdc_stage(sh[(c + 1) & 1], v, nrm);    // last read in iteration c - 1, which every wave has left
+            if (more) f64t_fetch(v, row, (c + 1) * F64T_KC);
+            f64t_chunk(sh[c & 1], l, acc);
+            if (more) f64t_stage(sh[(c + 1) & 1], v, norms);  // last read in iteration c - 1, which every wave has left
             __syncthreads();
         }
 
         // squared norms of the 128 staged rows: 8 partials per row, added in feature order
 #pragma unroll
-        for (int s = 0; s < PRDC_VEC; ++s) {
-            const int e = threadIdx.x + PRDC_THREADS * s;
-            sh_part[e >> 3][e & 7] = nrm[s];
-        }
+        for (int s = 0; s < F64T_VEC; ++s) sh_part[sr + 32 * s][threadIdx.x & 7] = nrm[s];
         __syncthreads();
-        if (threadIdx.x < 2 * PRDC_TILE) {
+        if (threadIdx.x < 2 * F64T_TILE) {
             const double* __restrict__ p = sh_part[threadIdx.x];
             sh_norm[threadIdx.x] = ((((((p[0] + p[1]) + p[2]) + p[3]) + p[4]) + p[5]) + p[6]) + p[7];
         }
         __syncthreads();
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int y = 0; y < 2; ++y)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int i = wi + 16 * x + lk + 4 * r, j = wj + 16 * y + lc;
-                    sh_d2[i * PRDC_TLD + j] = fmax((sh_norm[i] + sh_norm[PRDC_TILE + j]) - 2.0 * acc[x][y][r], 0.0);
-                }
+        f64t_each(l, acc, [&](int i, int j, double g) {
+            sh_d2[i * PRDC_TLD + j] = fmax((sh_norm[i] + sh_norm[F64T_TILE + j]) - 2.0 * g, 0.0);
+        });
         __syncthreads();
 
         // row-wise epilogue: thread (er, eq) takes columns 16 eq .. 16 eq + 15 of row er
@@ -188,7 +137,7 @@ __global__ __launch_bounds__(PRDC_THREADS) void prdc_kernel(const float* __restr
         reinterpret_cast<int*>(sh_d2)[(er * 4 + eq) * 2 + 1] = cnt_own;
     }
     __syncthreads();
-    if (threadIdx.x < PRDC_TILE && gi < na) {
+    if (threadIdx.x < F64T_TILE && gi < na) {
         if (MODE == 0) {
             for (int m = PRDC_K; m < 4 * PRDC_K; ++m) prdc_insert(best, sh_d2[er * 4 * PRDC_K + m]);
             if (direct) {
@@ -245,36 +194,26 @@ __global__ __launch_bounds__(256) void prdc_merge_counts_kernel(const int32_t* _
     if (in_own) in_own[i] = co;
 }
 
-inline bool prdc_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-// the column splits of a launch: the caller's, or enough to put PRDC_FILL workgroups on the chip; never more than B tiles
 inline int prdc_splits(int na, int nb, int splits) {
-    const int blocks = cdiv(na, PRDC_TILE), tiles = cdiv(nb, PRDC_TILE);
-    int s = splits > 0 ? splits : cdiv(PRDC_FILL, blocks);
-    s = s < PRDC_MAX_SPLITS ? s : PRDC_MAX_SPLITS;
-    return s < tiles ? s : tiles;
-}
-
-inline bool prdc_rows_ok(const float* x, int n, int D, int ld) {
-    return x && n >= 1 && D >= PRDC_TILE && D % PRDC_TILE == 0 && ld >= D && ld % 4 == 0 && prdc_aligned(x, 16);
+    return f64t_splits(cdiv(na, F64T_TILE), cdiv(nb, F64T_TILE), splits);
 }
 
 }  // namespace
 
 extern "C" int64_t sba_prdc_workspace_bytes(int na, int nb, int splits) {
-    if (na < 1 || nb < 1 || splits < 0 || splits > PRDC_MAX_SPLITS) return -1;
+    if (na < 1 || nb < 1 || splits < 0 || splits > F64T_MAX_SPLITS) return -1;
     const int s = prdc_splits(na, nb, splits);
     return s == 1 ? 0 : (int64_t)s * na * PRDC_K * (int64_t)sizeof(double);
 }
 
 extern "C" int sba_prdc_knn_radius(const float* x, int n, int D, int ld, int k, int splits, double* radius2, void* ws,
                                    int64_t ws_bytes, void* stream) {
-    if (!radius2 || !prdc_aligned(radius2, 8) || !prdc_rows_ok(x, n, D, ld)) return SBA_E_ARG;
-    if (k < 1 || k > PRDC_K || n < k + 1 || splits < 0 || splits > PRDC_MAX_SPLITS) return SBA_E_ARG;
+    if (!radius2 || !f64t_aligned(radius2, 8) || !f64t_rows_ok(x, n, D, ld)) return SBA_E_ARG;
+    if (k < 1 || k > PRDC_K || n < k + 1 || splits < 0 || splits > F64T_MAX_SPLITS) return SBA_E_ARG;
     const int S = prdc_splits(n, n, splits);
-    if (S > 1 && (!ws || !prdc_aligned(ws, 8) || ws_bytes < sba_prdc_workspace_bytes(n, n, splits))) return SBA_E_ARG;
+    if (S > 1 && (!ws || !f64t_aligned(ws, 8) || ws_bytes < sba_prdc_workspace_bytes(n, n, splits))) return SBA_E_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    SBA_LAUNCH(prdc_kernel<0>, dim3(cdiv(n, PRDC_TILE), S), dim3(PRDC_THREADS), 0, st, x, n, (int64_t)ld, x, n, (int64_t)ld,
+    SBA_LAUNCH(prdc_kernel<0>, dim3(cdiv(n, F64T_TILE), S), dim3(F64T_THREADS), 0, st, x, n, (int64_t)ld, x, n, (int64_t)ld,
                D, (const double*)nullptr, (const double*)nullptr, k, S == 1 ? 1 : 0, S == 1 ? radius2 : (double*)ws,
                (int32_t*)nullptr, (int32_t*)nullptr);
     if (SBA_CHECK_LAUNCH() != SBA_OK) return SBA_E_LAUNCH;
@@ -286,18 +225,18 @@ extern "C" int sba_prdc_knn_radius(const float* x, int n, int D, int ld, int k, 
 extern "C" int sba_prdc_ball_counts(const float* a, int na, int lda, const float* b, int nb, int ldb, int D,
                                     const double* radius_a, const double* radius_b, int splits, int32_t* in_b,
                                     int32_t* in_own, void* ws, int64_t ws_bytes, void* stream) {
-    if (!prdc_rows_ok(a, na, D, lda) || !prdc_rows_ok(b, nb, D, ldb)) return SBA_E_ARG;
+    if (!f64t_rows_ok(a, na, D, lda) || !f64t_rows_ok(b, nb, D, ldb)) return SBA_E_ARG;
     // a count goes with its radius vector: without the vector it is not written, with it it needs somewhere to go
     if ((radius_a && !in_own) || (radius_b && !in_b) || (!radius_a && !radius_b)) return SBA_E_ARG;
     if (!radius_a) in_own = nullptr;
     if (!radius_b) in_b = nullptr;
-    if (!prdc_aligned(radius_a, 8) || !prdc_aligned(radius_b, 8) || !prdc_aligned(in_b, 4) || !prdc_aligned(in_own, 4))
+    if (!f64t_aligned(radius_a, 8) || !f64t_aligned(radius_b, 8) || !f64t_aligned(in_b, 4) || !f64t_aligned(in_own, 4))
         return SBA_E_ARG;
-    if (splits < 0 || splits > PRDC_MAX_SPLITS) return SBA_E_ARG;
+    if (splits < 0 || splits > F64T_MAX_SPLITS) return SBA_E_ARG;
     const int S = prdc_splits(na, nb, splits);
-    if (S > 1 && (!ws || !prdc_aligned(ws, 8) || ws_bytes < sba_prdc_workspace_bytes(na, nb, splits))) return SBA_E_ARG;
+    if (S > 1 && (!ws || !f64t_aligned(ws, 8) || ws_bytes < sba_prdc_workspace_bytes(na, nb, splits))) return SBA_E_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    SBA_LAUNCH(prdc_kernel<1>, dim3(cdiv(na, PRDC_TILE), S), dim3(PRDC_THREADS), 0, st, a, na, (int64_t)lda, b, nb,
+    SBA_LAUNCH(prdc_kernel<1>, dim3(cdiv(na, F64T_TILE), S), dim3(F64T_THREADS), 0, st, a, na, (int64_t)lda, b, nb,
                (int64_t)ldb, D, radius_a, radius_b, 0, S == 1 ? 1 : 0, (double*)nullptr, S == 1 ? in_b : (int32_t*)ws,
                S == 1 ? in_own : (int32_t*)nullptr);
     if (SBA_CHECK_LAUNCH() != SBA_OK) return SBA_E_LAUNCH;

@@ -1,11 +1,42 @@
 """The feature rows of the real and the generated images on the device, as the evaluators that need every row keep them
 (sbagan/prdc.py, sbagan/kid.py): per side one f32 [capacity][D] buffer that grows by doubling, appended to without a
-host-device sync per batch."""
+host-device sync per batch.  Also the few lines those evaluators share with sbagan/fid.py."""
 import torch
 
 from . import ops
 
 SIDES = ('real', 'fake')
+
+
+def dtype_name(dtype=None):
+    """the name the evaluators report a compute dtype by ('bfloat16'); None: the current compute dtype"""
+    return str(dtype if dtype is not None else ops.compute_dtype()).replace('torch.', '')
+
+
+def check_side(owner, side):
+    if side not in SIDES:
+        raise ValueError("%s: side must be 'real' or 'fake' (got %r)" % (owner, side))
+    return side
+
+
+def check_features(owner, feats, D):
+    """feats is a batch of feature rows [B][D], f32, on the device"""
+    if not torch.is_tensor(feats) or feats.dim() != 2 or feats.shape[1] != D:
+        raise ValueError('%s: features must be a [B][%d] tensor (got %s)'
+                         % (owner, D, tuple(feats.shape) if torch.is_tensor(feats) else type(feats)))
+    ops._need_gpu(feats)
+    if feats.dtype != torch.float32:
+        raise TypeError('%s: features must be float32 (got %s)' % (owner, feats.dtype))
+
+
+class Evaluator(object):
+    """what FID, PRDC and KID do alike with their `features` callable"""
+
+    def update(self, side, images):
+        """one batch of images of either side"""
+        with torch.no_grad():
+            feats = self.features(images)
+        self.update_features(side, feats)
 
 
 class FeatureRows(object):
@@ -20,19 +51,12 @@ class FeatureRows(object):
         self._rows = {}                             # side -> [buffer [capacity][D], rows held]
 
     def _side(self, side):
-        if side not in SIDES:
-            raise ValueError("%s: side must be 'real' or 'fake' (got %r)" % (self.owner, side))
-        return side
+        return check_side(self.owner, side)
 
     def append(self, side, feats):
         """one batch of feature rows [B][D] (f32, on the device); no host-device sync"""
         side = self._side(side)
-        if not torch.is_tensor(feats) or feats.dim() != 2 or feats.shape[1] != self.D:
-            raise ValueError('%s: features must be a [B][%d] tensor (got %s)'
-                             % (self.owner, self.D, tuple(feats.shape) if torch.is_tensor(feats) else type(feats)))
-        ops._need_gpu(feats)
-        if feats.dtype != torch.float32:
-            raise TypeError('%s: features must be float32 (got %s)' % (self.owner, feats.dtype))
+        check_features(self.owner, feats, self.D)
         held = self._rows.get(side)
         if held is None:
             held = self._rows[side] = [torch.empty((self.capacity, self.D), dtype=torch.float32, device=feats.device), 0]

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .feature_rows import SIDES, Evaluator, check_features, check_side, dtype_name
 
-SIDES = ('real', 'fake')
 FIELDS = ('fid', 'n_real', 'n_fake', 'trace_real', 'trace_fake', 'mean_term', 'dtype')
 
 
@@ -58,7 +58,7 @@ def summarize(real, fake, dtype):
             'trace_fake': float(t2), 'mean_term': float(d @ d), 'dtype': str(dtype)}
 
 
-class FID(object):
+class FID(Evaluator):
     """Accumulates the feature moments of real and generated images.  features(images) -> f32 [B][D] on the device (an
     InceptionHIP's pooled_features, or any callable of that shape); chunk: rows of the device staging buffer per
     accumulate launch; key: stats_key() of this run, stored with saved real statistics and checked on loading;
@@ -70,33 +70,20 @@ class FID(object):
         if chunk < 1:
             raise ValueError('FID: chunk must be >= 1 (got %d)' % chunk)
         self.features, self.D, self.chunk, self.key = features, int(D), int(chunk), str(key)
-        self.dtype = str(dtype if dtype is not None else ops.compute_dtype()).replace('torch.', '')
+        self.dtype = dtype_name(dtype)
         self._acc = {}                              # side -> [staging, rows staged, rows in all, sum, gram]
         self._stats = {}                            # side -> (n, mu, sigma, trace) in numpy, once finalized or loaded
         self._loaded = set()
 
     def _side(self, side):
-        if side not in SIDES:
-            raise ValueError("FID: side must be 'real' or 'fake' (got %r)" % (side,))
-        return side
-
-    def update(self, side, images):
-        """one batch of images of either side"""
-        with torch.no_grad():
-            feats = self.features(images)
-        self.update_features(side, feats)
+        return check_side('FID', side)
 
     def update_features(self, side, feats):
         """one batch of feature rows [B][D] (f32, on the device); no host-device sync"""
         side = self._side(side)
         if side in self._loaded:
             raise RuntimeError('FID: the %s side was loaded from a file and takes no more rows' % side)
-        if not torch.is_tensor(feats) or feats.dim() != 2 or feats.shape[1] != self.D:
-            raise ValueError('FID: features must be a [B][%d] tensor (got %s)'
-                             % (self.D, tuple(feats.shape) if torch.is_tensor(feats) else type(feats)))
-        ops._need_gpu(feats)
-        if feats.dtype != torch.float32:
-            raise TypeError('FID: features must be float32 (got %s)' % feats.dtype)
+        check_features('FID', feats, self.D)
         acc = self._acc.get(side)
         if acc is None:
             dev = feats.device

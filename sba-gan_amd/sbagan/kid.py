@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .feature_rows import SIDES, FeatureRows
+from .feature_rows import SIDES, Evaluator, FeatureRows, dtype_name
 
 FIELDS = ('kid', 'kid_std', 'subsets', 'subset_size', 'n_real', 'n_fake', 'degree', 'coef0', 'gamma', 'dtype', 'seed')
 
@@ -59,7 +59,7 @@ def kid_from_sums(sxx, syy, sxy, m, n_real=None, n_fake=None, D=2048, dtype='', 
             'seed': None if seed is None else int(seed)}
 
 
-class KID(object):
+class KID(Evaluator):
     """Collects the feature rows of real and generated images.  features(images) -> f32 [B][D] on the device (an
     InceptionHIP's pooled_features, or any callable of that shape); subsets (1 .. 1024) of at most subset_size (>= 2)
     rows a side; seed: of the subset draws; key: a description of the run, kept for the caller; dtype: the
@@ -79,13 +79,7 @@ class KID(object):
         self.store = rows.store if self.shared else FeatureRows('KID', D, capacity)
         self.features, self.D, self.subsets, self.subset_size = features, int(D), subsets, subset_size
         self.seed, self.key = int(seed), str(key)
-        self.dtype = str(dtype if dtype is not None else ops.compute_dtype()).replace('torch.', '')
-
-    def update(self, side, images):
-        """one batch of images of either side"""
-        with torch.no_grad():
-            feats = self.features(images)
-        self.update_features(side, feats)
+        self.dtype = dtype_name(dtype)
 
     def update_features(self, side, feats):
         """one batch of feature rows [B][D] (f32, on the device); no host-device sync"""

@@ -2103,6 +2103,47 @@ def vis_compose(V, band, desc, par, band_rgb, expanded=None, imgs0=None, imgs1=N
 
 
 # ----------------------------------------------------------------------------
+# evaluation (sbagan/fid.py, sbagan/prdc.py, sbagan/kid.py): what the three kernel families check alike
+EVAL_MAX_SPLITS = 32
+PRDC_MAX_SPLITS = KID_MAX_SPLITS = EVAL_MAX_SPLITS
+
+
+def _feature_tensor(name, x, what):
+    """an f32 2-D tensor on the device"""
+    if not torch.is_tensor(x):
+        raise TypeError('%s: %s must be a tensor' % (name, what))
+    _need_gpu(x)
+    if x.dtype != torch.float32:
+        raise TypeError('%s: %s must be float32 (got %s)' % (name, what, x.dtype))
+    if x.dim() != 2:
+        raise ValueError('%s: %s must be 2-D (got %s)' % (name, what, tuple(x.shape)))
+
+
+def _feature_rows(name, x, what, device=None, D=None):
+    """(n, D, row stride) of an f32 [n][D] feature-row tensor the evaluation kernels can read"""
+    _feature_tensor(name, x, what)
+    if device is not None and x.device != device:
+        raise ValueError('%s: %s is on %s, not on %s' % (name, what, x.device, device))
+    n, d = x.shape
+    if n < 1 or d < 64 or d % 64 or (D is not None and d != D):
+        raise ValueError('%s: %s must be [n >= 1][%s] (got %s)'
+                         % (name, what, D if D is not None else 'a positive multiple of 64', tuple(x.shape)))
+    ld = x.stride(0) if n > 1 else d        # (a single row has no meaningful row stride)
+    if x.stride(1) != 1 or ld < d or ld % 4:
+        raise ValueError('%s: %s needs unit column stride and a row stride >= D that is a multiple of 4 (got strides '
+                         '%s)' % (name, what, tuple(x.stride())))
+    if x.data_ptr() % 16:
+        raise ValueError('%s: %s must be 16-byte aligned' % (name, what))
+    return n, d, ld
+
+
+def _eval_splits(name, splits):
+    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits <= EVAL_MAX_SPLITS:
+        raise ValueError('%s: splits must be an integer in [0, %d], 0 = the library\'s choice (got %r)'
+                         % (name, EVAL_MAX_SPLITS, splits))
+
+
+# ----------------------------------------------------------------------------
 # evaluation: FID statistics (sbagan/fid.py)
 def _fid_need_moments(name, x_device, sum, gram):
     for what, t, dim in (('sum', sum, 1), ('gram', gram, 2)):
@@ -2124,24 +2165,9 @@ def fid_accumulate(x, sum, gram):
     same device, D % 64 == 0, n >= 1.  Only the upper-triangular 64 x 64 tiles of gram are updated.  No atomics, a fixed
     summation order.  Everything is checked before the launch: TypeError for a dtype, ValueError for a shape, a stride
     or an alignment."""
-    if not torch.is_tensor(x):
-        raise TypeError('fid_accumulate: x must be a tensor')
-    _need_gpu(x)
-    if x.dtype != torch.float32:
-        raise TypeError('fid_accumulate: x must be float32 (got %s)' % x.dtype)
-    if x.dim() != 2:
-        raise ValueError('fid_accumulate: x must be 2-D (got %s)' % (tuple(x.shape),))
+    _feature_tensor('fid_accumulate', x, 'x')           # (what x is comes before the moments, its shape after them)
     D = _fid_need_moments('fid_accumulate', x.device, sum, gram)
-    n, ldx = x.shape[0], x.stride(0)
-    if n < 1 or x.shape[1] != D:
-        raise ValueError('fid_accumulate: x must be [n >= 1][%d] (got %s)' % (D, tuple(x.shape)))
-    if n == 1:
-        ldx = D                     # (a single row has no meaningful row stride)
-    if x.stride(1) != 1 or ldx < D or ldx % 4:
-        raise ValueError('fid_accumulate: x needs unit column stride and a row stride >= D that is a multiple of 4 '
-                         '(got strides %s)' % (tuple(x.stride()),))
-    if x.data_ptr() % 16:
-        raise ValueError('fid_accumulate: x must be 16-byte aligned')
+    n, _, ldx = _feature_rows('fid_accumulate', x, 'x', D=D)
     call('sba_fid_accumulate', _p(x), n, D, ldx, _p(sum), _p(gram), _stream())
 
 
@@ -2162,38 +2188,12 @@ def fid_finalize(sum, gram, n):
 
 # ----------------------------------------------------------------------------
 # evaluation: k-NN manifold metrics (sbagan/prdc.py)
-PRDC_MAX_K, PRDC_MAX_SPLITS = 8, 32
-
-
-def _prdc_rows(name, x, what, device=None, D=None):
-    """(n, D, row stride) of an f32 [n][D] feature-row tensor the prdc kernels can read"""
-    if not torch.is_tensor(x):
-        raise TypeError('%s: %s must be a tensor' % (name, what))
-    _need_gpu(x)
-    if x.dtype != torch.float32:
-        raise TypeError('%s: %s must be float32 (got %s)' % (name, what, x.dtype))
-    if x.dim() != 2:
-        raise ValueError('%s: %s must be 2-D (got %s)' % (name, what, tuple(x.shape)))
-    if device is not None and x.device != device:
-        raise ValueError('%s: %s is on %s, not on %s' % (name, what, x.device, device))
-    n, d = x.shape
-    if n < 1 or d < 64 or d % 64 or (D is not None and d != D):
-        raise ValueError('%s: %s must be [n >= 1][%s] (got %s)'
-                         % (name, what, D if D is not None else 'a positive multiple of 64', tuple(x.shape)))
-    ld = x.stride(0) if n > 1 else d        # (a single row has no meaningful row stride)
-    if x.stride(1) != 1 or ld < d or ld % 4:
-        raise ValueError('%s: %s needs unit column stride and a row stride >= D that is a multiple of 4 (got strides '
-                         '%s)' % (name, what, tuple(x.stride())))
-    if x.data_ptr() % 16:
-        raise ValueError('%s: %s must be 16-byte aligned' % (name, what))
-    return n, d, ld
+PRDC_MAX_K = 8
 
 
 def _prdc_workspace(name, na, nb, splits, device):
     """(workspace tensor or None, its size in bytes) for a launch over na x nb rows"""
-    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits <= PRDC_MAX_SPLITS:
-        raise ValueError('%s: splits must be an integer in [0, %d], 0 = the library\'s choice (got %r)'
-                         % (name, PRDC_MAX_SPLITS, splits))
+    _eval_splits(name, splits)
     nbytes = int(_lib.lib.sba_prdc_workspace_bytes(na, nb, splits))
     if nbytes < 0:
         raise ValueError('%s: no workspace size for %d x %d rows in %d splits' % (name, na, nb, splits))
@@ -2209,7 +2209,7 @@ def prdc_knn_radius(x, k, splits=0):
     splits: column parts of the launch (0 = the library's choice); the result has the same bits for every value.  The
     workspace is a torch allocation on the current stream; no host sync.  Everything is checked before the launch:
     TypeError for a dtype, ValueError for a shape, a stride, an alignment, k or splits."""
-    n, D, ld = _prdc_rows('prdc_knn_radius', x, 'x')
+    n, D, ld = _feature_rows('prdc_knn_radius', x, 'x')
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= PRDC_MAX_K:
         raise ValueError('prdc_knn_radius: k must be an integer in [1, %d] (got %r)' % (PRDC_MAX_K, k))
     if n < k + 1:
@@ -2227,8 +2227,8 @@ def prdc_ball_counts(a, b, radius_a=None, radius_b=None, splits=0):
     device; a count whose radius vector is None is not computed and comes back as None (one of the two is needed).
     Rows, splits, workspace and refusals as in prdc_knn_radius."""
     name = 'prdc_ball_counts'
-    na, D, lda = _prdc_rows(name, a, 'a')
-    nb, _, ldb = _prdc_rows(name, b, 'b', a.device, D)
+    na, D, lda = _feature_rows(name, a, 'a')
+    nb, _, ldb = _feature_rows(name, b, 'b', a.device, D)
     if radius_a is None and radius_b is None:
         raise ValueError('%s: one of radius_a and radius_b is needed' % name)
     for what, r, n in (('radius_a', radius_a, na), ('radius_b', radius_b, nb)):
@@ -2247,7 +2247,7 @@ def prdc_ball_counts(a, b, radius_a=None, radius_b=None, splits=0):
 
 # ----------------------------------------------------------------------------
 # evaluation: Kernel Inception Distance (sbagan/kid.py)
-KID_MAX_SUBSETS, KID_MAX_SPLITS = 1024, 32
+KID_MAX_SUBSETS = 1024
 
 
 def _kid_indices(name, idx, what, n):
@@ -2277,11 +2277,9 @@ def kid_kernel_sums(a, b, idx_a=None, idx_b=None, exclude_diag=False, splits=0):
     current stream; no host sync.  Everything is checked before the launch: TypeError for a dtype, ValueError for a
     shape, a stride, an alignment, an index, exclude_diag or splits."""
     name = 'kid_kernel_sums'
-    na, D, lda = _prdc_rows(name, a, 'a')
-    nb, _, ldb = _prdc_rows(name, b, 'b', a.device, D)
-    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits <= KID_MAX_SPLITS:
-        raise ValueError('%s: splits must be an integer in [0, %d], 0 = the library\'s choice (got %r)'
-                         % (name, KID_MAX_SPLITS, splits))
+    na, D, lda = _feature_rows(name, a, 'a')
+    nb, _, ldb = _feature_rows(name, b, 'b', a.device, D)
+    _eval_splits(name, splits)
     ia = _kid_indices(name, idx_a, 'idx_a', na) if idx_a is not None else None
     ib = _kid_indices(name, idx_b, 'idx_b', nb) if idx_b is not None else None
     if ia is not None and ib is not None and ia.shape[0] != ib.shape[0]:

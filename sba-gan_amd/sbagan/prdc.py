@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .feature_rows import SIDES, FeatureRows
+from .feature_rows import SIDES, Evaluator, FeatureRows, dtype_name
 
 FIELDS = ('precision', 'recall', 'density', 'coverage', 'k', 'n_real', 'n_fake', 'dtype')
 
@@ -50,7 +50,7 @@ def prdc_from_counts(fake_in_real, real_in_fake, real_own, k, dtype=''):
             'k': k, 'n_real': n_real, 'n_fake': n_fake, 'dtype': str(dtype)}
 
 
-class PRDC(object):
+class PRDC(Evaluator):
     """Collects the feature rows of real and generated images.  features(images) -> f32 [B][D] on the device (an
     InceptionHIP's pooled_features, or any callable of that shape); k: the neighbour that sets a ball's radius (1 .. 8);
     key: a description of the run, kept for the caller; dtype: the compute-dtype name reported in the result."""
@@ -60,13 +60,7 @@ class PRDC(object):
         if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.PRDC_MAX_K:
             raise ValueError('PRDC: k must be an integer in [1, %d] (got %r)' % (ops.PRDC_MAX_K, k))
         self.features, self.D, self.k, self.key, self.capacity = features, int(D), k, str(key), int(capacity)
-        self.dtype = str(dtype if dtype is not None else ops.compute_dtype()).replace('torch.', '')
-
-    def update(self, side, images):
-        """one batch of images of either side"""
-        with torch.no_grad():
-            feats = self.features(images)
-        self.update_features(side, feats)
+        self.dtype = dtype_name(dtype)
 
     def update_features(self, side, feats):
         """one batch of feature rows [B][D] (f32, on the device); no host-device sync"""

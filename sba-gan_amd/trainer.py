@@ -413,9 +413,9 @@ class condGANTrainer(object):
         """sbagan.fid.FID on the pooled trunk feature of `image_encoder` (an InceptionHIP); the real side comes from
         fid_stats when that file exists"""
         from miscc import cli
-        from sbagan import ops
+        from sbagan.feature_rows import dtype_name
         from sbagan.fid import FID, stats_key
-        dtype = str(ops.compute_dtype()).replace('torch.', '')
+        dtype = dtype_name()
         key = stats_key(cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder'), dtype, split_dir, cli.image_size())
         evaluator = FID(image_encoder.pooled_features, D=2048, key=key, dtype=dtype)
         if self.fid_stats and os.path.exists(self.fid_stats):
@@ -429,12 +429,12 @@ class condGANTrainer(object):
     def _prdc_evaluator(self, image_encoder):
         """sbagan.prdc.PRDC on the pooled trunk feature of `image_encoder` (an InceptionHIP)"""
         from sbagan import ops
+        from sbagan.feature_rows import dtype_name
         from sbagan.prdc import PRDC
         if isinstance(self.prdc, bool) or not isinstance(self.prdc, int) or not 1 <= self.prdc <= ops.PRDC_MAX_K:
             raise ValueError('prdc must be 0 (off) or a neighbour count from 1 to %d (got %r)'
                              % (ops.PRDC_MAX_K, self.prdc))
-        dtype = str(ops.compute_dtype()).replace('torch.', '')
-        return PRDC(image_encoder.pooled_features, D=2048, k=self.prdc, dtype=dtype)
+        return PRDC(image_encoder.pooled_features, D=2048, k=self.prdc, dtype=dtype_name())
 
     kid = False                 # --kid: sampling() also takes the Kernel Inception Distance
     kid_subsets = 100           # --kid_subsets N
@@ -446,11 +446,10 @@ class condGANTrainer(object):
     def _kid_evaluator(self, image_encoder, prdc):
         """sbagan.kid.KID on the pooled trunk feature of `image_encoder` (an InceptionHIP); with a PRDC evaluator it
         reads that one's rows and stores none"""
-        from sbagan import ops
+        from sbagan.feature_rows import dtype_name
         from sbagan.kid import KID
-        dtype = str(ops.compute_dtype()).replace('torch.', '')
         return KID(image_encoder.pooled_features, D=2048, subsets=self.kid_subsets, subset_size=self.kid_subset_size,
-                   seed=self.kid_seed, dtype=dtype, rows=prdc)
+                   seed=self.kid_seed, dtype=dtype_name(), rows=prdc)
 
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
@@ -496,41 +495,30 @@ class condGANTrainer(object):
                         ev.update_features('real', real_feats)
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
-        if evaluator is not None:
-            self.r_precision_evaluator = evaluator
-            res = self.r_precision_result = evaluator.result()
-            print('R-precision (R = %d, %d images): R@1 %.4f  R@5 %.4f  R@10 %.4f  R@1 over %d splits %.4f +- %.4f'
-                  % (res['R'], res['n'], res['r_at_1'], res['r_at_5'], res['r_at_10'], res['splits'],
-                     res['r_at_1_splits_mean'], res['r_at_1_splits_std']))
-            with open(os.path.join(out_dir, 'r_precision.json'), 'w') as f:
+        # (attribute stem and file name, evaluator, the printed line, the result fields it shows)
+        reports = (
+            ('r_precision', evaluator,
+             'R-precision (R = %d, %d images): R@1 %.4f  R@5 %.4f  R@10 %.4f  R@1 over %d splits %.4f +- %.4f',
+             ('R', 'n', 'r_at_1', 'r_at_5', 'r_at_10', 'splits', 'r_at_1_splits_mean', 'r_at_1_splits_std')),
+            ('fid', fid, 'FID (%d real, %d generated images, %s trunk): %.6g  (mean term %.6g, tr real %.6g, tr fake %.6g)',
+             ('n_real', 'n_fake', 'dtype', 'fid', 'mean_term', 'trace_real', 'trace_fake')),
+            ('prdc', prdc, 'PRDC (k = %d, %d real, %d generated images, %s trunk): precision %.4f  recall %.4f  '
+             'density %.4f  coverage %.4f',
+             ('k', 'n_real', 'n_fake', 'dtype', 'precision', 'recall', 'density', 'coverage')),
+            ('kid', kid, 'KID (%d subsets of %d, %d real, %d generated images, %s trunk): %.6g +- %.6g',
+             ('subsets', 'subset_size', 'n_real', 'n_fake', 'dtype', 'kid', 'kid_std')))
+        for stem, ev, line, fields in reports:
+            if ev is None:
+                continue
+            setattr(self, stem + '_evaluator', ev)
+            res = ev.result()
+            setattr(self, stem + '_result', res)
+            print(line % tuple(res[f] for f in fields))
+            with open(os.path.join(out_dir, stem + '.json'), 'w') as f:
                 json.dump(res, f, indent=1, sort_keys=True)
-        if fid is not None:
-            self.fid_evaluator = fid
-            res = self.fid_result = fid.result()
-            print('FID (%d real, %d generated images, %s trunk): %.6g  (mean term %.6g, tr real %.6g, tr fake %.6g)'
-                  % (res['n_real'], res['n_fake'], res['dtype'], res['fid'], res['mean_term'], res['trace_real'],
-                     res['trace_fake']))
-            with open(os.path.join(out_dir, 'fid.json'), 'w') as f:
-                json.dump(res, f, indent=1, sort_keys=True)
-            if self.fid_stats and fid_real:
+            if ev is fid and self.fid_stats and fid_real:
                 fid.save_real(self.fid_stats)
                 print('Save real FID statistics to:', self.fid_stats)
-        if prdc is not None:
-            self.prdc_evaluator = prdc
-            res = self.prdc_result = prdc.result()
-            print('PRDC (k = %d, %d real, %d generated images, %s trunk): precision %.4f  recall %.4f  density %.4f  '
-                  'coverage %.4f' % (res['k'], res['n_real'], res['n_fake'], res['dtype'], res['precision'],
-                                     res['recall'], res['density'], res['coverage']))
-            with open(os.path.join(out_dir, 'prdc.json'), 'w') as f:
-                json.dump(res, f, indent=1, sort_keys=True)
-        if kid is not None:
-            self.kid_evaluator = kid
-            res = self.kid_result = kid.result()
-            print('KID (%d subsets of %d, %d real, %d generated images, %s trunk): %.6g +- %.6g'
-                  % (res['subsets'], res['subset_size'], res['n_real'], res['n_fake'], res['dtype'], res['kid'],
-                     res['kid_std']))
-            with open(os.path.join(out_dir, 'kid.json'), 'w') as f:
-                json.dump(res, f, indent=1, sort_keys=True)
         return out_dir
 
     def gen_example(self, data_dic):
