@@ -739,6 +739,32 @@ int sba_kid_kernel_sums(const float* a, int na, int lda, const int32_t* idx_a, i
                         const int32_t* idx_b, int mb, int D, int subsets, int exclude_diag, int splits, double* sums,
                         void* ws, int64_t ws_bytes, void* stream);
 
+/* Multi-scale structural similarity of image pairs (evaluation; sbagan/msssim.py): per pair, channel and
+ * scale the MEAN SSIM and the MEAN contrast-structure term (cs) over the valid window positions, in float64.
+ * imgs  [n][3][H][W] uint8, planar, dense, on the device;  pairs [P][2] int32 image numbers, on the device;
+ * out   [P][3][scales][2] f64: {mean ssim, mean cs}.
+ * Pixel values are the bytes 0 .. 255: L = 255, C1 = (0.01 L)^2, C2 = (0.03 L)^2.  The window is
+ *   g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0 .. 10, normalised to sum 1 in double on the host, applied separably
+ *   (along the rows, then down the columns, taps in ascending order) with NO padding.
+ * Scale s (0-based) works on the image pooled s times by a 2 x 2 mean, a trailing odd row or column dropped: Hs = H >> s,
+ *   Ws = W >> s.  The kernel pools from the bytes while it stages a tile (the mean of a 2^s x 2^s block of bytes is
+ *   exact); no pyramid is stored.
+ * Per position: mx, my, sxx = E[xx] - mx^2, syy = E[yy] - my^2, sxy = E[xy] - mx my,
+ *   cs = (2 sxy + C2) / (sxx + syy + C2),  ssim = cs * (2 mx my + C1) / (mx^2 + my^2 + C1);
+ *   the mean is the sum over the (Hs - 10) x (Ws - 10) positions divided by their count.
+ * A pair with an image number outside [0, n) reads nothing; its 6 * scales outputs are NaN.
+ * One launch per scale, grid (P * tiles of 16 x 32 positions, 3); every workgroup adds its positions in a fixed order
+ *   and writes one {ssim, cs} partial to `ws`; a last small launch adds the partials of a (pair, channel, scale) in tile
+ *   order and divides.  ws: 8-byte aligned, at least sba_msssim_workspace_bytes(H, W, P, scales) bytes (it does not
+ *   depend on n; -1 for a refused shape).  All arithmetic is f64; the same arguments give the same bits; no atomics,
+ *   no memset, no allocation.
+ * SBA_E_ARG before any launch unless 1 <= scales <= 5, min(H, W) >> (scales - 1) >= 11, H, W <= 1024, n >= 1,
+ *   1 <= P <= 2^20 (and P * tiles of scale 0 < 2^31), imgs non-null, pairs 4-byte aligned, out and ws 8-byte aligned and
+ *   non-null, and the workspace large enough. */
+int64_t sba_msssim_workspace_bytes(int H, int W, int P, int scales);
+int sba_msssim_pairs(const uint8_t* imgs, int n, int H, int W, const int32_t* pairs, int P, int scales, double* out,
+                     void* ws, int64_t ws_bytes, void* stream);
+
 /* Training batches from the device-resident image cache (sbagan/device_data.py): gather, crop, mirror,
  * every scale of the image pyramid and the normalisation in ONE launch, bit-identical to the PIL data path.
  * cache: all images back to back, each HWC uint8 [H_i][W_i][3]; offset[i] (int64): byte offset of image i; hw[i] = {H_i,

@@ -1,7 +1,7 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
-    [--kid]  [--kid_subsets N]  [--kid_subset_size M]
+    [--kid]  [--kid_subsets N]  [--kid_subset_size M]  [--ms_ssim N]
     [--device_data]  [--device_data_gb G]  [--replay]
     [--bert_dir DIR: the BERT entry points]
 
@@ -50,6 +50,13 @@ def _kid_subset_size(text):
     return m
 
 
+def _ms_ssim(text):
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError('N must be 0 (off) or a number of pairs per class')
+    return n
+
+
 def options(what, default_cfg, argv=None, bert=False):
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
@@ -89,6 +96,12 @@ def options(what, default_cfg, argv=None, bert=False):
                     help='with --kid: the number of subsets, 1 to 1024')
     ap.add_argument('--kid_subset_size', dest='kid_subset_size', type=_kid_subset_size, default=1000, metavar='M',
                     help='with --kid: rows per subset and side (at least 2); clamped to the smaller side')
+    ap.add_argument('--ms_ssim', dest='ms_ssim', type=_ms_ssim, default=0, metavar='N',
+                    help='sampling: also take the mean multi-scale structural similarity (MS-SSIM, the within-class '
+                         'diversity measure of the AC-GAN paper, sbagan.msssim) over N random pairs of images per class, '
+                         'for the generated images and for the real images of the same pairs, and write ms_ssim.json; '
+                         '0 = off, 100 = the AC-GAN setting.  In pixel space on the written uint8 images: it uses no '
+                         'trunk; images of at least 176 px')
     ap.add_argument('--device_data', dest='device_data', action='store_true', default=False,
                     help='training: decode the split once into a device-resident uint8 cache and make every batch '
                          'there -- crop, flip, every scale of the pyramid and the normalisation in one HIP launch '

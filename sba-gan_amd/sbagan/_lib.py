@@ -149,6 +149,7 @@ SIGNATURES = {
     'sba_prdc_knn_radius': [P, I, I, I, I, I, P, P, L, P],
     'sba_prdc_ball_counts': [P, I, I, P, I, I, I, P, P, I, P, P, P, L, P],
     'sba_kid_kernel_sums': [P, I, I, P, I, P, I, I, P, I, I, I, I, I, P, P, L, P],
+    'sba_msssim_pairs': [P, I, I, I, P, I, I, P, P, L, P],
     'sba_batch_pyramid': [P, P, P, I, P, I, I, I, P, P, P, P, P, P, P],
     'sba_batch_masks': [P, P, P, P, I, I, P],
     'sba_embed_dropout_fwd': [P, P, P, F, P, I, I, I, P],
@@ -186,6 +187,8 @@ lib.sba_prdc_workspace_bytes.restype = c_int64
 lib.sba_prdc_workspace_bytes.argtypes = [I, I, I]
 lib.sba_kid_workspace_bytes.restype = c_int64
 lib.sba_kid_workspace_bytes.argtypes = [I, I, I, I]
+lib.sba_msssim_workspace_bytes.restype = c_int64
+lib.sba_msssim_workspace_bytes.argtypes = [I, I, I, I]
 
 _ERR = {-1: 'SBA_E_ARG (unsupported shape/alignment/enum)', -2: 'SBA_E_LAUNCH (HIP launch failed)',
         -3: 'SBA_E_UNSUPPORTED (graph node kind the replayer cannot re-issue)'}

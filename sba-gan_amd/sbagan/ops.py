@@ -2304,6 +2304,64 @@ def kid_kernel_sums(a, b, idx_a=None, idx_b=None, exclude_diag=False, splits=0):
 
 
 # ----------------------------------------------------------------------------
+# evaluation: multi-scale structural similarity of image pairs (sbagan/msssim.py)
+MSSSIM_MAX_SCALES, MSSSIM_MAX_SIDE, MSSSIM_MAX_PAIRS, MSSSIM_WINDOW = 5, 1024, 1 << 20, 11
+
+
+def msssim_pairs(imgs, pairs, scales=5):
+    """out [P][3][scales][2] f64 on the device (sba_msssim_pairs): per pair, channel and scale the mean SSIM and the mean
+    contrast-structure term over the valid positions of the 11-tap Gaussian window, all arithmetic in float64.
+    imgs [n][3][H][W]: uint8, contiguous, on the device.  pairs [P][2]: image numbers, int32 or int64, a numpy array /
+    CPU tensor (uploaded here) or an int32 tensor on the device of imgs; a pair that names an image outside [0, n)
+    reads nothing and gives NaN.  scales: 1 .. 5, and min(H, W) >> (scales - 1) >= 11; H, W <= 1024.  The workspace
+    (the workgroups' partial sums; its size does not depend on n) is a torch allocation on the current stream; no host
+    sync.  Everything is checked before the launch: TypeError for a dtype, ValueError for a shape or a stride."""
+    name = 'msssim_pairs'
+    if not torch.is_tensor(imgs):
+        raise TypeError('%s: imgs must be a tensor (got %s)' % (name, type(imgs)))
+    _need_gpu(imgs)
+    if imgs.dtype != torch.uint8:
+        raise TypeError('%s: imgs must be uint8 (got %s)' % (name, imgs.dtype))
+    if imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.shape[0] < 1:
+        raise ValueError('%s: imgs must be [n >= 1][3][H][W] (got %s)' % (name, tuple(imgs.shape)))
+    if not imgs.is_contiguous():
+        raise ValueError('%s: imgs must be contiguous (strides %s)' % (name, imgs.stride()))
+    n, _, H, W = imgs.shape
+    if isinstance(scales, bool) or not isinstance(scales, int) or not 1 <= scales <= MSSSIM_MAX_SCALES:
+        raise ValueError('%s: scales must be an integer in [1, %d] (got %r)' % (name, MSSSIM_MAX_SCALES, scales))
+    if max(H, W) > MSSSIM_MAX_SIDE or min(H, W) >> (scales - 1) < MSSSIM_WINDOW:
+        raise ValueError('%s: %d x %d images do not hold the %d-tap window at %d scales (at most %d a side)'
+                         % (name, H, W, MSSSIM_WINDOW, scales, MSSSIM_MAX_SIDE))
+    if torch.is_tensor(pairs) and pairs.device.type != 'cpu':
+        if pairs.device != imgs.device:
+            raise ValueError('%s: pairs are on %s, imgs on %s' % (name, pairs.device, imgs.device))
+        if pairs.dtype != torch.int32:
+            raise TypeError('%s: pairs on the device must be int32 (got %s)' % (name, pairs.dtype))
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+            raise ValueError('%s: pairs must be contiguous [P][2] (got %s)' % (name, tuple(pairs.shape)))
+        pairs_dev = pairs
+    else:
+        host = np.asarray(pairs.numpy() if torch.is_tensor(pairs) else pairs)
+        if host.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise TypeError('%s: pairs must be int32 or int64 (got %s)' % (name, host.dtype))
+        if host.ndim != 2 or host.shape[1] != 2:
+            raise ValueError('%s: pairs must be [P][2] (got %s)' % (name, host.shape))
+        lim = np.iinfo(np.int32)
+        host = np.clip(host, lim.min, lim.max) if host.dtype != np.int32 else host   # (outside [0, n) either way)
+        pairs_dev = torch.from_numpy(np.array(host, dtype=np.int32, order='C')).to(imgs.device)
+    P = pairs_dev.shape[0]
+    if not 1 <= P <= MSSSIM_MAX_PAIRS:
+        raise ValueError('%s: 1 to %d pairs a launch (got %d)' % (name, MSSSIM_MAX_PAIRS, P))
+    nbytes = int(_lib.lib.sba_msssim_workspace_bytes(H, W, P, scales))
+    if nbytes < 0:
+        raise ValueError('%s: no workspace size for %d pairs of %d x %d images at %d scales' % (name, P, H, W, scales))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=imgs.device)
+    out = torch.empty((P, 3, scales, 2), dtype=torch.float64, device=imgs.device)
+    call('sba_msssim_pairs', _p(imgs), n, H, W, _p(pairs_dev), P, scales, _p(out), _p(ws), nbytes, _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------
 # training batches from the device-resident image cache (sbagan/device_data.py)
 def check_pyramid_shape(T, levels):
     """ValueError unless sba_batch_pyramid takes a T px crop at `levels` scales"""

@@ -451,11 +451,26 @@ class condGANTrainer(object):
         return KID(image_encoder.pooled_features, D=2048, subsets=self.kid_subsets, subset_size=self.kid_subset_size,
                    seed=self.kid_seed, dtype=dtype_name(), rows=prdc)
 
+    ms_ssim = 0                 # --ms_ssim N: sampling() also takes the mean MS-SSIM over N same-class pairs per class
+    ms_ssim_seed = 100          # of the evaluator's own generator for the pair draws
+    ms_ssim_result = None       # the result dict of the last sampling() with ms_ssim != 0
+    ms_ssim_evaluator = None
+
+    def _ms_ssim_evaluator(self):
+        """sbagan.msssim.MSSSIM on the uint8 pixels of the last stage's images; refuses a configuration whose images
+        are too small for five scales"""
+        from miscc import cli
+        from sbagan.msssim import MSSSIM
+        if isinstance(self.ms_ssim, bool) or not isinstance(self.ms_ssim, int) or self.ms_ssim < 1:
+            raise ValueError('ms_ssim must be 0 (off) or a number of pairs per class (got %r)' % (self.ms_ssim,))
+        return MSSSIM(self.ms_ssim, size=cli.image_size(), seed=self.ms_ssim_seed)
+
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
         root = self._output_root()
         if root is None:
             return None
+        ms_ssim = self._ms_ssim_evaluator() if self.ms_ssim else None   # (refused before anything is written)
         out_dir = os.path.join(root, 'valid' if split_dir == 'test' else split_dir)
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
@@ -493,6 +508,9 @@ class condGANTrainer(object):
                     real_feats = image_encoder.pooled_features(real_imgs[-1])
                     for ev in takes_real:
                         ev.update_features('real', real_feats)
+            if ms_ssim is not None:             # the pixels themselves: no trunk
+                ms_ssim.update('fake', last, class_ids)
+                ms_ssim.update('real', real_imgs[-1], class_ids)
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
         # (attribute stem and file name, evaluator, the printed line, the result fields it shows)
@@ -506,7 +524,11 @@ class condGANTrainer(object):
              'density %.4f  coverage %.4f',
              ('k', 'n_real', 'n_fake', 'dtype', 'precision', 'recall', 'density', 'coverage')),
             ('kid', kid, 'KID (%d subsets of %d, %d real, %d generated images, %s trunk): %.6g +- %.6g',
-             ('subsets', 'subset_size', 'n_real', 'n_fake', 'dtype', 'kid', 'kid_std')))
+             ('subsets', 'subset_size', 'n_real', 'n_fake', 'dtype', 'kid', 'kid_std')),
+            ('ms_ssim', ms_ssim, 'MS-SSIM (%d same-class pairs of %d images, %d classes, %d skipped, %d px): generated '
+             '%.6g +- %.6g  real %.6g +- %.6g',
+             ('pairs', 'n_images', 'classes', 'classes_skipped', 'size', 'ms_ssim_fake', 'ms_ssim_fake_std',
+              'ms_ssim_real', 'ms_ssim_real_std')))
         for stem, ev, line, fields in reports:
             if ev is None:
                 continue

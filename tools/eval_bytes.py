@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One SHA-256 per output buffer of every entry point of csrc/fid.hip, csrc/prdc.hip and csrc/kid.hip over a fixed list
+"""One SHA-256 per output buffer of every entry point of csrc/fid.hip, csrc/prdc.hip, csrc/kid.hip and csrc/msssim.hip over a fixed list
 of seeded real-valued inputs, through the C ABI.  Run it once per build of the library, each in a fresh process, and
 diff the two listings -- the summation orders of these kernels are fixed, so a refactor must leave every line equal:
 
@@ -152,6 +152,32 @@ def kid():
                  sums=kid_sums(a, b, ia, ib, m, m, S, diag, splits))
 
 
+def msssim():
+    def images(seed, n, H, W):
+        """uint8 [n][3][H][W]: a smooth pattern per image plus noise"""
+        rng = np.random.RandomState(seed)
+        yy, xx = np.mgrid[0:H, 0:W]
+        x = np.stack([[127.5 + 90.0 * np.sin(xx / (5.0 + i + c)) * np.cos(yy / (7.0 + c)) for c in range(3)] for i in range(n)])
+        return torch.from_numpy(np.clip(x + rng.normal(0.0, 20.0, x.shape), 0, 255).astype(np.uint8)).to(DEV)
+
+    def means(imgs, pairs, scales):
+        n, _, H, W = imgs.shape
+        P = pairs.shape[0]
+        nbytes = int(_lib.lib.sba_msssim_workspace_bytes(H, W, P, scales))
+        ws, out = workspace(nbytes), nans(P, 3, scales, 2)
+        _lib.call('sba_msssim_pairs', p(imgs), n, H, W, p(pairs), P, scales, p(out), p(ws), nbytes, stream())
+        return out
+
+    for H, W, scales in ((11, 11, 1), (12, 27, 1), (22, 23, 2), (45, 47, 3), (176, 176, 5), (177, 208, 5), (256, 256, 5)):
+        imgs = images(900 + H, 6, H, W)
+        pairs = torch.tensor([(0, 1), (2, 3), (4, 4), (5, 0), (1, 0)], dtype=torch.int32, device=DEV)
+        for s in range(1, scales + 1):
+            emit('sba_msssim_pairs', '%dx%d-S%d' % (H, W, s), out=means(imgs, pairs, s))
+        # image numbers outside [0, n) (such a pair reads nothing and gives NaN)
+        pairs[1, 1], pairs[3, 0] = 6, -1
+        emit('sba_msssim_pairs', '%dx%d-S%d-out-of-range' % (H, W, scales), out=means(imgs, pairs, scales))
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit('eval_bytes.py runs the kernels: no device visible')
@@ -159,6 +185,7 @@ def main():
     fid()
     prdc()
     kid()
+    msssim()
 
 
 if __name__ == '__main__':
