@@ -765,6 +765,55 @@ int64_t sba_msssim_workspace_bytes(int H, int W, int P, int scales);
 int sba_msssim_pairs(const uint8_t* imgs, int n, int H, int W, const int32_t* pairs, int P, int scales, double* out,
                      void* ws, int64_t ws_bytes, void* stream);
 
+/* Sliced Wasserstein distance of Laplacian-pyramid patch descriptors (evaluation; sbagan/swd.py), one
+ * pyramid level at a time, all arithmetic in float64.  None of the four uses atomics, a memset or an allocation; the same
+ * arguments give the same bits.  SBA_E_ARG is returned before anything is launched or copied.
+ *
+ * sba_swd_descriptors: the 7 x 7 x 3 patch descriptors of level `level` (0 = the image itself, finest) of n square S px
+ *   images, P patches an image.
+ *   imgs    [n][3][S][S] uint8, planar, dense, on the device (image offsets are 64-bit);  S in {32, 64, 128, 256};
+ *           levels = log2(S / 16) + 1, 0 <= level < levels; the side of the level is Sl = S >> level.
+ *   centres [n * P][2] int32 {x, y} ON THE HOST: descriptor j belongs to image j / P.  Every value must lie in
+ *           [3, Sl - 4]; they are checked here and then copied to `ws` on the stream.
+ *   desc    [n * P][147] f64 on the device, NOT normalised: entry (c * 7 + dy) * 7 + dx = Lap[c][y - 3 + dy][x - 3 + dx].
+ *   stats   [6] f64 on the device: the sums of the n * P * 49 values of channel 0, 1, 2, then the sums of their squared
+ *           deviations from the channel mean stats[c] / (n * P * 49) (taken in a second pass over desc: no cancellation).
+ *   Pyramid: k = (1, 4, 6, 4, 1), K = k k^T / 256; G_{l+1} = conv(G_l, K)[::2, ::2]; up(G) = conv(Z, 4 K) with Z zero
+ *   except Z[::2, ::2] = G; mirror boundary WITHOUT repeating the edge sample (-1 -> 1, n -> n - 2);
+ *   Lap_l = G_l - up(G_{l+1}) for l < levels - 1, Lap_{levels-1} = G_{levels-1}.  The pyramid of one (image, channel) is
+ *   built in LDS as exact integers over a power of two and never written to memory, so desc is EXACT (it equals any
+ *   float64 evaluation of the definition bit for bit).  One workgroup per (image, channel) adds its values in a fixed
+ *   order; a small launch adds the workgroups' partial sums in image order (sums first, then the deviations alike).  All
+ *   these sums carry their rounding errors along (two-sum), so each statistic is within a rounding or two of exact.
+ *   ws: 8-byte aligned, on the device, at least 48 n + 8 n P bytes.
+ *   SBA_E_ARG unless the pointers are non-null, centres 4-byte and desc, stats, ws 8-byte aligned, S in the set,
+ *   0 <= level < levels, 1 <= n < 2^31, 1 <= P <= 4096, every centre in range and the workspace large enough.
+ *
+ * sba_swd_project: out[d][i] = sum_k (desc[i][k] - mu_c) / sigma_c * dirs[k][d], channel c = k / 49, with
+ *   mu_c = stats[c] / (49 m), sigma_c = sqrt(stats[3 + c] / (49 m)) (the population deviation), evaluated as
+ *   sum_k (desc[i][k] - mu_c) dir'[k][d] with dir'[k][d] = dirs[k][d] * (1 / sigma_c), made on the device from `stats`; the
+ *   mean is taken off as a descriptor tile is staged (an offset subtracted after the contraction would cancel a digit or
+ *   two where |mu| > sigma).  The contraction runs on the f64 matrix instruction, k ascending four at a time, K padded
+ *   from 147 to 148 by zeros.  sigma_c = 0 gives non-finite values, never a fault.
+ *   desc [m][147], stats [6], dirs [147][D], out [D][m] (direction-major), all f64 on the device, 8-byte aligned.
+ *   ws: 8-byte aligned, at least 8 * 148 * D bytes.  SBA_E_ARG unless 1 <= D <= 65535, 1 <= m, D * m <= 2^40.
+ *
+ * sba_swd_sort_columns: sorts each of the D columns of length m of data [D][m] (f64) ascending; the result is in `data`.
+ *   tmp: a second [D][m] buffer, needed (non-null, not `data`) when m > 2048, the tile that one workgroup sorts in LDS;
+ *   longer columns are merged pairwise from sorted tiles.  Any m >= 1.  Values compare with <: -0 and +0 are equal and
+ *   the order of NaNs is undefined (nothing is rejected).  Same limits on D and m.
+ *
+ * sba_swd_abs_mean: out[d] = (sum_i |a[d][i] - b[d][i]|) / m for a, b [D][m] f64: one partial sum per workgroup and chunk of
+ *   4096 values, the partials of a column added in chunk order.  ws: 8-byte aligned, at least 8 * D * ceil(m / 4096)
+ *   bytes.  Same limits on D and m. */
+int sba_swd_descriptors(const uint8_t* imgs, int64_t n, int S, int level, const int32_t* centres, int P, double* desc,
+                        double* stats, void* ws, int64_t ws_bytes, void* stream);
+int sba_swd_project(const double* desc, int64_t m, const double* stats, const double* dirs, int D, double* out, void* ws,
+                    int64_t ws_bytes, void* stream);
+int sba_swd_sort_columns(double* data, double* tmp, int D, int64_t m, void* stream);
+int sba_swd_abs_mean(const double* a, const double* b, int D, int64_t m, double* out, void* ws, int64_t ws_bytes,
+                     void* stream);
+
 /* Training batches from the device-resident image cache (sbagan/device_data.py): gather, crop, mirror,
  * every scale of the image pyramid and the normalisation in ONE launch, bit-identical to the PIL data path.
  * cache: all images back to back, each HWC uint8 [H_i][W_i][3]; offset[i] (int64): byte offset of image i; hw[i] = {H_i,

@@ -7,7 +7,9 @@ cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_exampl
 overlay images, sbagan/visualize.py), --fid [--fid_stats PATH] (sampling also writes fid.json, sbagan/fid.py) and --prdc K
 (sampling also writes prdc.json: precision, recall, density and coverage, sbagan/prdc.py), --kid [--kid_subsets N]
 [--kid_subset_size M] (sampling also writes kid.json: the Kernel Inception Distance, sbagan/kid.py), --ms_ssim N
-(sampling also writes ms_ssim.json: the mean MS-SSIM over N same-class image pairs per class, sbagan/msssim.py) and --device_data
+(sampling also writes ms_ssim.json: the mean MS-SSIM over N same-class image pairs per class, sbagan/msssim.py), --swd N
+(sampling also writes swd.json: the sliced Wasserstein distance per resolution between the first N real and the first N
+generated images, sbagan/swd.py) and --device_data
 [--device_data_gb G] (training: the split is decoded once into a device-resident cache and every batch is cropped, flipped,
 resized to every scale and normalised there, sbagan/device_data.py) and --replay (training: every batch through one
 recording of the step, read from a static batch slot, sbagan/static_batch.py) are this project's additions."""
@@ -98,6 +100,7 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo.kid_subsets = int(getattr(args, 'kid_subsets', 100))
     algo.kid_subset_size = int(getattr(args, 'kid_subset_size', 1000))
     algo.ms_ssim = int(getattr(args, 'ms_ssim', 0))
+    algo.swd = int(getattr(args, 'swd', 0))
     algo.replay = bool(getattr(args, 'replay', False)) and training
     if getattr(args, 'replay', False) and not training:
         print('--replay is ignored outside training')

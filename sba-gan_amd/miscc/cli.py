@@ -1,7 +1,7 @@
 """What the two entry points (main.py, pretrain_DAMSM.py) share, written from their command-line contract:
 
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
-    [--kid]  [--kid_subsets N]  [--kid_subset_size M]  [--ms_ssim N]
+    [--kid]  [--kid_subsets N]  [--kid_subset_size M]  [--ms_ssim N]  [--swd N]
     [--device_data]  [--device_data_gb G]  [--replay]
     [--bert_dir DIR: the BERT entry points]
 
@@ -57,6 +57,13 @@ def _ms_ssim(text):
     return n
 
 
+def _swd(text):
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError('N must be 0 (off) or a number of images per side')
+    return n
+
+
 def options(what, default_cfg, argv=None, bert=False):
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
@@ -102,6 +109,11 @@ def options(what, default_cfg, argv=None, bert=False):
                          'for the generated images and for the real images of the same pairs, and write ms_ssim.json; '
                          '0 = off, 100 = the AC-GAN setting.  In pixel space on the written uint8 images: it uses no '
                          'trunk; images of at least 176 px')
+    ap.add_argument('--swd', dest='swd', type=_swd, default=0, metavar='N',
+                    help='sampling: also take the sliced Wasserstein distance (SWD, Karras et al. 2018, sbagan.swd) between '
+                         'the first N real and the first N generated images, per level of a Laplacian pyramid and on '
+                         'average, x 1e3, and write swd.json; 0 = off, 16384 = the setting of the paper.  In pixel '
+                         'space on the written uint8 images: it uses no trunk; square images of 32, 64, 128 or 256 px')
     ap.add_argument('--device_data', dest='device_data', action='store_true', default=False,
                     help='training: decode the split once into a device-resident uint8 cache and make every batch '
                          'there -- crop, flip, every scale of the pyramid and the normalisation in one HIP launch '

@@ -150,6 +150,10 @@ SIGNATURES = {
     'sba_prdc_ball_counts': [P, I, I, P, I, I, I, P, P, I, P, P, P, L, P],
     'sba_kid_kernel_sums': [P, I, I, P, I, P, I, I, P, I, I, I, I, I, P, P, L, P],
     'sba_msssim_pairs': [P, I, I, I, P, I, I, P, P, L, P],
+    'sba_swd_descriptors': [P, L, I, I, P, I, P, P, P, L, P],
+    'sba_swd_project': [P, L, P, P, I, P, P, L, P],
+    'sba_swd_sort_columns': [P, P, I, L, P],
+    'sba_swd_abs_mean': [P, P, I, L, P, P, L, P],
     'sba_batch_pyramid': [P, P, P, I, P, I, I, I, P, P, P, P, P, P, P],
     'sba_batch_masks': [P, P, P, P, I, I, P],
     'sba_embed_dropout_fwd': [P, P, P, F, P, I, I, I, P],

@@ -2362,6 +2362,151 @@ def msssim_pairs(imgs, pairs, scales=5):
 
 
 # ----------------------------------------------------------------------------
+# evaluation: sliced Wasserstein distance of Laplacian-pyramid patch descriptors (sbagan/swd.py)
+SWD_SIZES, SWD_PATCH, SWD_DESC, SWD_MAX_PATCHES, SWD_MAX_DIRS = (32, 64, 128, 256), 7, 147, 4096, 65535
+SWD_SORT_TILE = 2048            # values one workgroup sorts in LDS; longer columns are merged from sorted tiles
+SWD_MEAN_CHUNK = 4096
+
+
+def swd_levels(size):
+    """pyramid levels of a size x size image: log2(size / 16) + 1; ValueError for a size outside SWD_SIZES"""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or int(size) not in SWD_SIZES:
+        raise ValueError('swd: images must be square with a side in %s (got %r)' % (SWD_SIZES, size))
+    return SWD_SIZES.index(int(size)) + 2
+
+
+def _swd_f64(name, what, t, shape, like=None):
+    if not torch.is_tensor(t):
+        raise TypeError('%s: %s must be a tensor (got %s)' % (name, what, type(t)))
+    _need_gpu(t)
+    if t.dtype != torch.float64:
+        raise TypeError('%s: %s must be float64 (got %s)' % (name, what, t.dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError('%s: %s must be %s (got %s)' % (name, what, tuple(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError('%s: %s must be contiguous (strides %s)' % (name, what, t.stride()))
+    if like is not None and t.device != like.device:
+        raise ValueError('%s: %s is on %s, not on %s' % (name, what, t.device, like.device))
+    return t
+
+
+def _swd_columns(name, D, m):
+    if not 1 <= D <= SWD_MAX_DIRS or m < 1 or D * m > 1 << 40:
+        raise ValueError('%s: 1 to %d columns of at least 1 value, at most 2^40 values in all (got %d x %d)'
+                         % (name, SWD_MAX_DIRS, D, m))
+
+
+def swd_descriptors(imgs, level, centres, desc=None):
+    """(desc [n * P][147] f64, stats [6] f64) on the device (sba_swd_descriptors): the un-normalised 7 x 7 x 3 patch
+    descriptors of Laplacian-pyramid level `level` (0 = finest) and, per channel, the sum and the sum of the squared
+    deviations from the channel mean.  imgs
+    [n][3][S][S]: uint8, contiguous, on the device, S in SWD_SIZES.  centres [n * P][2]: {x, y} per descriptor, an
+    integer numpy array on the HOST (descriptor j belongs to image j // P), every value in [3, (S >> level) - 4]; the
+    library checks them and uploads them on the current stream.  desc: an optional buffer to fill, [n * P][147] f64.
+    Everything is checked before the launch."""
+    name = 'swd_descriptors'
+    if not torch.is_tensor(imgs):
+        raise TypeError('%s: imgs must be a tensor (got %s)' % (name, type(imgs)))
+    _need_gpu(imgs)
+    if imgs.dtype != torch.uint8:
+        raise TypeError('%s: imgs must be uint8 (got %s)' % (name, imgs.dtype))
+    if imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.shape[0] < 1 or imgs.shape[2] != imgs.shape[3]:
+        raise ValueError('%s: imgs must be [n >= 1][3][S][S] (got %s)' % (name, tuple(imgs.shape)))
+    if not imgs.is_contiguous():
+        raise ValueError('%s: imgs must be contiguous (strides %s)' % (name, imgs.stride()))
+    n, S = imgs.shape[0], imgs.shape[2]
+    levels = swd_levels(S)
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level < levels:
+        raise ValueError('%s: a %d px image has levels 0 .. %d (got %r)' % (name, S, levels - 1, level))
+    host = np.asarray(centres)
+    if host.dtype.kind not in 'iu':
+        raise TypeError('%s: centres must be integers (got %s)' % (name, host.dtype))
+    if host.ndim != 2 or host.shape[1] != 2 or host.shape[0] < n or host.shape[0] % n:
+        raise ValueError('%s: centres must be [n * P][2] for the %d images (got %s)' % (name, n, host.shape))
+    P = host.shape[0] // n
+    if P > SWD_MAX_PATCHES:
+        raise ValueError('%s: at most %d patches an image (got %d)' % (name, SWD_MAX_PATCHES, P))
+    Sl = S >> int(level)
+    if host.min() < 3 or host.max() > Sl - 4:
+        raise ValueError('%s: patch centres of a %d px level must lie in [3, %d] (got %d .. %d)'
+                         % (name, Sl, Sl - 4, host.min(), host.max()))
+    host = np.ascontiguousarray(host, dtype=np.int32)
+    if desc is None:
+        desc = torch.empty((n * P, SWD_DESC), dtype=torch.float64, device=imgs.device)
+    else:
+        _swd_f64(name, 'desc', desc, (n * P, SWD_DESC), imgs)
+    stats = torch.empty(6, dtype=torch.float64, device=imgs.device)
+    nbytes = 48 * n + 8 * n * P
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=imgs.device)
+    call('sba_swd_descriptors', _p(imgs), n, S, int(level), host.ctypes.data, P, _p(desc), _p(stats), _p(ws), nbytes,
+         _stream())
+    return desc, stats
+
+
+def swd_project(desc, stats, dirs, out=None):
+    """out [D][m] f64 (sba_swd_project): the descriptors desc [m][147], normalised per channel from stats [6] (the
+    population mean and deviation over all m * 49 values of a channel), projected on the directions dirs [147][D]; the
+    result is direction-major.  All f64 on one device; the normalisation is folded into the directions on the device."""
+    name = 'swd_project'
+    _swd_f64(name, 'desc', desc, None)
+    if desc.dim() != 2 or desc.shape[1] != SWD_DESC or desc.shape[0] < 1:
+        raise ValueError('%s: desc must be [m >= 1][%d] (got %s)' % (name, SWD_DESC, tuple(desc.shape)))
+    _swd_f64(name, 'dirs', dirs, None, desc)
+    if dirs.dim() != 2 or dirs.shape[0] != SWD_DESC:
+        raise ValueError('%s: dirs must be [%d][D] (got %s)' % (name, SWD_DESC, tuple(dirs.shape)))
+    _swd_f64(name, 'stats', stats, (6,), desc)
+    m, D = desc.shape[0], dirs.shape[1]
+    _swd_columns(name, D, m)
+    if out is None:
+        out = torch.empty((D, m), dtype=torch.float64, device=desc.device)
+    else:
+        _swd_f64(name, 'out', out, (D, m), desc)
+    nbytes = 8 * (SWD_DESC + 1) * D
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=desc.device)
+    call('sba_swd_project', _p(desc), m, _p(stats), _p(dirs), D, _p(out), _p(ws), nbytes, _stream())
+    return out
+
+
+def swd_sort_columns(data, tmp=None):
+    """sorts every row of data [D][m] f64 (a column of m projections each) ascending, in place (sba_swd_sort_columns),
+    and returns it.  tmp: a second buffer of the same shape, used when m > SWD_SORT_TILE (allocated here when missing).
+    -0 and +0 compare equal; the order of NaNs is undefined."""
+    name = 'swd_sort_columns'
+    _swd_f64(name, 'data', data, None)
+    if data.dim() != 2:
+        raise ValueError('%s: data must be [D][m] (got %s)' % (name, tuple(data.shape)))
+    D, m = data.shape
+    _swd_columns(name, D, m)
+    if m > SWD_SORT_TILE:
+        if tmp is None:
+            tmp = torch.empty_like(data)
+        _swd_f64(name, 'tmp', tmp, (D, m), data)
+        if tmp.data_ptr() == data.data_ptr():
+            raise ValueError('%s: tmp must be a second buffer' % name)
+    call('sba_swd_sort_columns', _p(data), _p(tmp) if m > SWD_SORT_TILE else None, D, m, _stream())
+    return data
+
+
+def swd_abs_mean(a, b, out=None):
+    """out [D] f64 (sba_swd_abs_mean): the mean of |a - b| along every row of a, b [D][m] f64, added in a fixed order"""
+    name = 'swd_abs_mean'
+    _swd_f64(name, 'a', a, None)
+    if a.dim() != 2:
+        raise ValueError('%s: a must be [D][m] (got %s)' % (name, tuple(a.shape)))
+    D, m = a.shape
+    _swd_columns(name, D, m)
+    _swd_f64(name, 'b', b, (D, m), a)
+    if out is None:
+        out = torch.empty(D, dtype=torch.float64, device=a.device)
+    else:
+        _swd_f64(name, 'out', out, (D,), a)
+    chunks = (m + SWD_MEAN_CHUNK - 1) // SWD_MEAN_CHUNK
+    ws = torch.empty(D * chunks, dtype=torch.float64, device=a.device)
+    call('sba_swd_abs_mean', _p(a), _p(b), D, m, _p(out), _p(ws), 8 * D * chunks, _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------
 # training batches from the device-resident image cache (sbagan/device_data.py)
 def check_pyramid_shape(T, levels):
     """ValueError unless sba_batch_pyramid takes a T px crop at `levels` scales"""

@@ -465,12 +465,28 @@ class condGANTrainer(object):
             raise ValueError('ms_ssim must be 0 (off) or a number of pairs per class (got %r)' % (self.ms_ssim,))
         return MSSSIM(self.ms_ssim, size=cli.image_size(), seed=self.ms_ssim_seed)
 
+    swd = 0                     # --swd N: sampling() also takes the sliced Wasserstein distance per resolution between the
+    #                             first N real and the first N generated images (0 = off)
+    swd_seed = 100              # of the evaluator's own generator for the patch positions and the directions
+    swd_result = None           # the result dict of the last sampling() with swd != 0
+    swd_evaluator = None
+
+    def _swd_evaluator(self, ms_ssim=None):
+        """sbagan.swd.SWD on the uint8 pixels of the last stage's images; refuses an image size it has no pyramid for.
+        ms_ssim: the MS-SSIM evaluator of the same run, whose stored images it then reads instead of keeping its own"""
+        from miscc import cli
+        from sbagan.swd import SWD
+        if isinstance(self.swd, bool) or not isinstance(self.swd, int) or self.swd < 1:
+            raise ValueError('swd must be 0 (off) or a number of images per side (got %r)' % (self.swd,))
+        return SWD(self.swd, size=cli.image_size(), seed=self.swd_seed, images=ms_ssim)
+
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
         root = self._output_root()
         if root is None:
             return None
         ms_ssim = self._ms_ssim_evaluator() if self.ms_ssim else None   # (refused before anything is written)
+        swd = self._swd_evaluator(ms_ssim) if self.swd else None        # (likewise)
         out_dir = os.path.join(root, 'valid' if split_dir == 'test' else split_dir)
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
@@ -511,9 +527,13 @@ class condGANTrainer(object):
             if ms_ssim is not None:             # the pixels themselves: no trunk
                 ms_ssim.update('fake', last, class_ids)
                 ms_ssim.update('real', real_imgs[-1], class_ids)
+            if swd is not None:                 # (stores nothing of its own beside an MS-SSIM evaluator)
+                swd.update('fake', last)
+                swd.update('real', real_imgs[-1])
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
-        # (attribute stem and file name, evaluator, the printed line, the result fields it shows)
+        # (attribute stem and file name, evaluator, the printed line, the result fields it shows: a name, or a function
+        # of the result)
         reports = (
             ('r_precision', evaluator,
              'R-precision (R = %d, %d images): R@1 %.4f  R@5 %.4f  R@10 %.4f  R@1 over %d splits %.4f +- %.4f',
@@ -528,14 +548,17 @@ class condGANTrainer(object):
             ('ms_ssim', ms_ssim, 'MS-SSIM (%d same-class pairs of %d images, %d classes, %d skipped, %d px): generated '
              '%.6g +- %.6g  real %.6g +- %.6g',
              ('pairs', 'n_images', 'classes', 'classes_skipped', 'size', 'ms_ssim_fake', 'ms_ssim_fake_std',
-              'ms_ssim_real', 'ms_ssim_real_std')))
+              'ms_ssim_real', 'ms_ssim_real_std')),
+            ('swd', swd, 'SWD x 1e3 (%d real and %d generated images, %d patches each, %d directions): %s  average %.6g',
+             ('n_images', 'n_images', 'patches_per_image', lambda r: r['dir_repeats'] * r['dirs_per_repeat'],
+              lambda r: '  '.join('%d px %.6g' % v for v in zip(r['resolutions'], r['swd_x1e3'])), 'swd_avg_x1e3')))
         for stem, ev, line, fields in reports:
             if ev is None:
                 continue
             setattr(self, stem + '_evaluator', ev)
             res = ev.result()
             setattr(self, stem + '_result', res)
-            print(line % tuple(res[f] for f in fields))
+            print(line % tuple(f(res) if callable(f) else res[f] for f in fields))
             with open(os.path.join(out_dir, stem + '.json'), 'w') as f:
                 json.dump(res, f, indent=1, sort_keys=True)
             if ev is fid and self.fid_stats and fid_real:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One SHA-256 per output buffer of every entry point of csrc/fid.hip, csrc/prdc.hip, csrc/kid.hip and csrc/msssim.hip over a fixed list
+"""One SHA-256 per output buffer of every entry point of csrc/fid.hip, csrc/prdc.hip, csrc/kid.hip, csrc/msssim.hip and csrc/swd.hip over a fixed list
 of seeded real-valued inputs, through the C ABI.  Run it once per build of the library, each in a fresh process, and
 diff the two listings -- the summation orders of these kernels are fixed, so a refactor must leave every line equal:
 
@@ -178,6 +178,26 @@ def msssim():
         emit('sba_msssim_pairs', '%dx%d-S%d-out-of-range' % (H, W, scales), out=means(imgs, pairs, scales))
 
 
+def swd():
+    from sbagan import ops
+    for S, n, P in ((32, 1, 1), (64, 3, 5), (256, 2, 128)):
+        rng = np.random.RandomState(700 + S)
+        imgs = torch.from_numpy(rng.randint(0, 256, (n, 3, S, S)).astype(np.uint8)).to(DEV)
+        dirs = torch.from_numpy(rng.randn(147, 130)).to(DEV)
+        for level in range(ops.swd_levels(S)):
+            Sl = S >> level
+            centres = rng.randint(3, Sl - 3, (n * P, 2)).astype(np.int32)
+            desc, stats = ops.swd_descriptors(imgs, level, centres)
+            emit('sba_swd_descriptors', '%dpx-n%d-P%d-L%d' % (S, n, P, level), desc=desc, stats=stats)
+            proj = ops.swd_project(desc, stats, dirs)
+            emit('sba_swd_project', '%dpx-n%d-P%d-L%d' % (S, n, P, level), out=proj)
+    for m in (1, 2047, 2048, 2049, 6161):
+        x = torch.from_numpy(np.random.RandomState(m).randn(130, m)).to(DEV)
+        y = torch.from_numpy(np.random.RandomState(m + 1).randn(130, m)).to(DEV)
+        emit('sba_swd_sort_columns', 'm%d' % m, data=ops.swd_sort_columns(x))
+        emit('sba_swd_abs_mean', 'm%d' % m, out=ops.swd_abs_mean(x, ops.swd_sort_columns(y)))
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit('eval_bytes.py runs the kernels: no device visible')
@@ -186,6 +206,7 @@ def main():
     prdc()
     kid()
     msssim()
+    swd()
 
 
 if __name__ == '__main__':
