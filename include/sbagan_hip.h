@@ -449,7 +449,18 @@ int sba_kl_loss(const float* mu, const float* logvar, float* loss, float* dmu, f
 /* DAMSM word loss (losses.py:62-132 with func_attention GlobalAttention.py:31-69).
  * feat[B][nef][R] f32 (R = 17*17), words[B][nef][L] f32, cap_lens int64[B].
  * sim[j][i] (image j, caption i) = log sum_t exp(g2 * cos(word_t, attended context)).
- * Saves attn[B*B][Lmax][R] and attn1 (first softmax) for the backward. */
+ * Saves attn[B*B][Lmax][R] and attn1 (first softmax) for the backward.
+ * nef % 32 == 0, R <= 320, L <= 32, B <= 1024; cap_lens is clamped to [1, L] on the device (T below).
+ * Which outputs are STORED and which are ADDED TO (tests/test_damsm_kernels_gpu.py holds the kernels to this):
+ *   forward (both families): sim[B][B], attn and attn1 [B*B][L][R], wctx [B*B][L][nef] are stored -- for the words
+ *     t < T only; the elements of attn, attn1 and wctx at t >= T are left UNWRITTEN, and no backward reads them.
+ *   sba_damsm_words_bwd: dfeat[B][nef][R] and dwords[B][nef][L] (may be NULL) are ADDED TO (f32 atomics): the caller
+ *     clears them -- also in deterministic mode, where the ordered fold adds the pairs' sum onto what is there.
+ *   sba_damsm_words_bwd_mfma: dfeat is stored with accumulate = 0 and added to with accumulate = 1 (one owner per
+ *     element either way); dwords (may be NULL) is added to, as above.
+ *   sba_damsm_sent_fwd: s[B][B] is stored.  sba_damsm_sent_bwd: dcnn and drnn (each may be NULL) are ADDED TO, in
+ *     both modes.  sba_damsm_sent_direct: loss_out[0] and dcnn (may be NULL) are stored.
+ *   sba_ce_pair, sba_ce_pair_direct, sba_combine2: every output is stored. */
 int sba_damsm_words_fwd(const float* feat, const float* words, const int64_t* cap_lens, float* sim,
                         float* attn, float* attn1, float* wctx, int B, int nef, int R, int L,
                         float gamma1, float gamma2, void* stream);
@@ -458,8 +469,10 @@ int sba_damsm_words_bwd(const float* feat, const float* words, const int64_t* ca
                         const float* dsim, float* dfeat, float* dwords, int B, int nef, int R, int L,
                         float gamma1, float gamma2, void* stream);
 /* sentence similarity matrix (losses.py:41-47): s[j][i] = cos(cnn[j], rnn[i]) * g3. */
-/* The same loss on the bf16 MATRIX CORES (csrc/damsm_mfma.hip; nef % 64 == 0, R <= 384, L <= 32 -- sba_damsm_prep_bytes
- * returns -1 otherwise and the callers keep the f32 kernels above).  Every product is formed from bf16 hi + lo parts of its
+/* The same loss on the bf16 MATRIX CORES (csrc/damsm_mfma.hip; nef % 64 == 0, nef <= 1024, R <= 384, L <= 32, and
+ * 128 (nef + R rounded up to 32) + 4096 bytes of LDS per pair within 160 KB -- sba_damsm_prep_bytes and
+ * sba_damsm_bwd_bytes return -1 otherwise and the callers keep the f32 kernels above; a positive size means that
+ * sba_damsm_prep and both kernels below accept the shape).  Every product is formed from bf16 hi + lo parts of its
  * f32 factors (xh yh + xl yh + xh yl, f32 sums): results agree with the f32 kernels to ~1e-5 relative.
  *   sba_damsm_prep: features / words -> hi + lo operands in `prep` (caller-owned scratch of sba_damsm_prep_bytes bytes,
  *     16-byte aligned; read by the forward AND the backward of the same inputs).

@@ -738,10 +738,15 @@ __global__ __launch_bounds__(1024) void damsm_sent_direct_kernel(const float* __
     }
 }
 
-inline bool mf_ok(int B, int nef, int R, int L) {
-    return B > 0 && B <= 1024 && nef > 0 && nef % 64 == 0 && nef <= 1024 && R > 0 && R <= 32 * 4 * MAX_RT && L > 0 && L <= TP;
-}
 inline int round32(int v) { return (v + 31) / 32 * 32; }
+// the shapes the matrix-core path takes: the size queries, the prep pass, the forward and the backward all ask this one
+// question, so a positive sba_damsm_prep_bytes promises that the three entry points accept the shape (the per-pair
+// kernels' LDS, 128 (nef + RP) + 4096 bytes, has to fit the 160 KB of a workgroup)
+inline bool mf_ok(int B, int nef, int R, int L) {
+    if (!(B > 0 && B <= 1024 && nef > 0 && nef % 64 == 0 && nef <= 1024 && R > 0 && R <= 32 * 4 * MAX_RT && L > 0 && L <= TP))
+        return false;
+    return pair_lds_bytes(nef, round32(R)) <= 160 * 1024;
+}
 
 }  // namespace
 
@@ -774,8 +779,7 @@ extern "C" int sba_damsm_words_fwd_mfma(const void* prep, const float* words, co
                                         float gamma1, float gamma2, void* stream) {
     if (!prep || !words || !cap_lens || !sim || !attn || !attn1 || !wctx || !mf_ok(B, nef, R, L)) return SBA_E_ARG;
     const int RP = round32(R);
-    const size_t sh = pair_lds_bytes(nef, RP);
-    if (sh > 160 * 1024) return SBA_E_ARG;
+    const size_t sh = pair_lds_bytes(nef, RP);          // (<= 160 KB: mf_ok)
     (void)hipFuncSetAttribute((const void*)damsm_words_fwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     SBA_LAUNCH(damsm_words_fwd_mfma_kernel, dim3(B, B), dim3(MF_NT), sh, (hipStream_t)stream, prep_views(prep, B, nef, RP),
                words, cap_lens, sim, attn, attn1, wctx, B, nef, R, RP, L, gamma1, gamma2);
@@ -792,8 +796,7 @@ extern "C" int sba_damsm_words_bwd_mfma(const void* prep, const float* words, co
         return SBA_E_ARG;
     if (scratch_bytes < sba_damsm_bwd_bytes(B, nef, R, L) || ((uintptr_t)scratch & 15)) return SBA_E_ARG;
     const int RP = round32(R);
-    const size_t sh = pair_lds_bytes(nef, RP);
-    if (sh > 160 * 1024) return SBA_E_ARG;
+    const size_t sh = pair_lds_bytes(nef, RP);          // (<= 160 KB: mf_ok)
     hipStream_t st = (hipStream_t)stream;
     float* pw = nullptr;
     if (sba_det_on() && dwords) {
