@@ -728,6 +728,34 @@ int sba_prdc_ball_counts(const float* a, int na, int lda, const float* b, int nb
                          const double* radius_b, int splits, int32_t* in_b, int32_t* in_own, void* ws, int64_t ws_bytes,
                          void* stream);
 
+/* Cross-modal retrieval ranks (evaluation of the DAMSM encoders; sbagan/retrieval.py): all-pairs cosine
+ * scores between two sets of f32 code rows (rows as for the k-NN metrics above) with a row-wise selection fused behind
+ * them; the na x nb matrix is never written.  All score arithmetic is float64:
+ *     s(i, j) = g(i, j) / max(sqrt(na[i] * nb[j]), eps)
+ * g the dot product on the f64 matrix instruction over the feature axis in ascending order (the f32 values are widened in
+ * registers, every product is exact), na / nb the squared norms in f64 in one fixed order, square root and division the
+ * IEEE operations.  s(i, j) has the same bits whichever tile, column split or launch computed it and whichever of the
+ * two sets is `a`: a threshold taken by one launch compares exactly in the next.
+ * key_a [na] / key_b [nb], cls_a / cls_b: int32 vectors that are only ever compared, never used as addresses.
+ * sba_retrieval_own_best: best[i] (f64) = the largest s(i, j) over the rows j of b with key_b[j] == key_a[i]; -inf when
+ *   there is none, NaN when any such score is NaN.
+ * sba_retrieval_counts: above[i] = #{j : key_b[j] != key_a[i] and NOT (s(i, j) < best[i])} as int32 -- a tie counts, and
+ *   so does a NaN on either side; above_masked[i] = the same count over the rows j whose class also differs
+ *   (cls_b[j] != cls_a[i]).  cls_a, cls_b and above_masked may be null together; then only `above` is written.
+ * splits, ws: as for the k-NN metrics (whole 64-row tiles of b, 0 = the library's choice, at most 32; the partials go to
+ *   `ws`, 8-byte aligned, at least sba_retrieval_workspace_bytes(na, nb, splits) bytes, and a second small launch merges
+ *   them in part order: a maximum for best, a sum for the counts).  Results are bit-identical for every split count.  No
+ *   atomics, no memset, no allocation.
+ * SBA_E_ARG before any launch on a null pointer, bad D, strides, alignment, eps <= 0, splits, class arguments given in
+ *   part, or a workspace too small. */
+int64_t sba_retrieval_workspace_bytes(int na, int nb, int splits);
+int sba_retrieval_own_best(const float* a, int na, int lda, const float* b, int nb, int ldb, int D, const int32_t* key_a,
+                           const int32_t* key_b, double eps, int splits, double* best, void* ws, int64_t ws_bytes,
+                           void* stream);
+int sba_retrieval_counts(const float* a, int na, int lda, const float* b, int nb, int ldb, int D, const int32_t* key_a,
+                         const int32_t* key_b, const int32_t* cls_a, const int32_t* cls_b, const double* best, double eps,
+                         int splits, int32_t* above, int32_t* above_masked, void* ws, int64_t ws_bytes, void* stream);
+
 /* Kernel Inception Distance (evaluation; sbagan/kid.py): sums of the polynomial kernel
  *     k(x, y) = (x . y / D + 1)^3
  * over pairs of gathered f32 feature rows (rows as for the k-NN metrics above), one sum per subset, in float64:

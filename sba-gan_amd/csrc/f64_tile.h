@@ -1,8 +1,8 @@
-// Shared by the evaluation units fid.hip, prdc.hip and kid.hip: the 64 x 64 float64 tile on the f64 matrix instruction
-// (v_mfma_f64_16x16x4_f64) that 256 threads compute as four waves of 2 x 2 MFMA tiles.  All three use the lane map and the
-// MFMA step; prdc.hip and kid.hip also the feature-major pair tile (dot products of 64 A rows with 64 B rows, the f32
-// rows widened in registers, features in ascending order) and the host side of its column splits.  Internal linkage, as
-// common.h.
+// Shared by the evaluation units fid.hip, prdc.hip, retrieval.hip and kid.hip: the 64 x 64 float64 tile on the f64 matrix
+// instruction (v_mfma_f64_16x16x4_f64) that 256 threads compute as four waves of 2 x 2 MFMA tiles.  All use the lane map
+// and the MFMA step; prdc.hip, retrieval.hip and kid.hip also the feature-major pair tile (dot products of 64 A rows with
+// 64 B rows, the f32 rows widened in registers, features in ascending order) and the host side of its column splits.
+// Internal linkage, as common.h.
 #pragma once
 #include "common.h"
 

@@ -3,6 +3,7 @@
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
     [--kid]  [--kid_subsets N]  [--kid_subset_size M]  [--ms_ssim N]  [--swd N]
     [--device_data]  [--device_data_gb G]  [--replay]
+    [--retrieval E]  [--retrieval_only: DAMSM pre-training]
     [--bert_dir DIR: the BERT entry points]
 
 the yml file is merged into miscc.config.cfg, --gpu / --data_dir override it, the seed is 100 outside training (the
@@ -62,6 +63,13 @@ def _swd(text):
     if n < 0:
         raise argparse.ArgumentTypeError('N must be 0 (off) or a number of images per side')
     return n
+
+
+def _retrieval(text):
+    e = int(text)
+    if e < 0:
+        raise argparse.ArgumentTypeError('E must be 0 (off) or an interval in epochs')
+    return e
 
 
 def options(what, default_cfg, argv=None, bert=False):
@@ -130,6 +138,16 @@ def options(what, default_cfg, argv=None, bert=False):
                          '(sbagan.damsm.DAMSMSlotStep), the dropout mask is drawn per batch outside it and the losses '
                          'are read only where the interval line is printed.  Ignored by pretrain_DAMSM_bert.py and '
                          'outside training')
+    ap.add_argument('--retrieval', dest='retrieval', type=_retrieval, default=0, metavar='E',
+                    help='DAMSM pre-training: after the validation pass of every E-th epoch and of the last one, rank '
+                         'every image of the validation split against every caption and every caption against every '
+                         'image with the two encoders (sbagan.retrieval: float64 cosine scores on the matrix cores, the '
+                         'score matrix never written), print R@1 / R@5 / R@10 and the median rank for both directions, '
+                         'instance-level and class-masked, and append them to Model/retrieval.jsonl; 0 = off.  It draws '
+                         'no random numbers and leaves the training untouched.  Ignored by main.py and main_bert.py')
+    ap.add_argument('--retrieval_only', dest='retrieval_only', action='store_true', default=False,
+                    help='DAMSM pre-training: load the encoder pair of TRAIN.NET_E, rank the validation split once, '
+                         'print the figures, write retrieval.json and return without training')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')

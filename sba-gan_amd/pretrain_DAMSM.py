@@ -7,7 +7,11 @@ train / evaluate / build_models keep the reference's signatures; the per-batch w
 wherever the interval log line is printed.  --device_data [--device_data_gb G]: both splits are decoded once into a
 device-resident cache and every batch is cropped, flipped and normalised there (sbagan.device_data).  --replay (training
 only): the update is ONE recording over a static batch slot (sbagan.damsm.DAMSMSlotStep), the losses are
-read only where the interval line is printed."""
+read only where the interval line is printed.  --retrieval E: after the validation pass of every E-th epoch and of the
+last one, the whole validation split is ranked both ways (sbagan.retrieval): one printed line and one JSON
+line in Model/retrieval.jsonl.  --retrieval_only: the pair of TRAIN.NET_E is ranked once, retrieval.json is written and
+nothing is trained."""
+import json
 import os
 import sys
 import time
@@ -117,6 +121,15 @@ def evaluate(dataloader, cnn_model, rnn_model, batch_size, damsm=None):
     return s_total / n, w_total / n
 
 
+def retrieval(dataset_val, dataloader_val, cnn_model, rnn_model, imsize):
+    """the retrieval figures of the encoder pair over the whole validation split, every caption of every image
+    (sbagan.retrieval.Retrieval.result).  Images are centre-cropped, from the device cache when the validation loader has
+    one; no global generator is consumed and both encoders go back to the mode they were in."""
+    from sbagan.retrieval import evaluate_split
+    return evaluate_split(dataset_val, cnn_model, rnn_model, cfg.TRAIN.BATCH_SIZE, imsize, int(imsize * 76 / 64),
+                          cache=getattr(dataloader_val, 'cache', None), workers=cfg.WORKERS).result()
+
+
 def build_models(n_words, batch_size):
     """pretrain_DAMSM.py:166-193."""
     text_encoder = RNN_ENCODER(n_words, nhidden=cfg.TEXT.EMBEDDING_DIM)
@@ -142,6 +155,9 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
     args = parse_args(argv) if args is None else args
     build = build_models if build is None else build
     cli.configure(args)
+    retrieval_only = bool(getattr(args, 'retrieval_only', False))
+    if retrieval_only and cfg.TRAIN.NET_E == '':
+        raise RuntimeError('--retrieval_only ranks a trained pair: set TRAIN.NET_E to its text_encoder<N>.pth')
     output_dir = cli.output_dir()
     model_dir, image_dir = os.path.join(output_dir, 'Model'), os.path.join(output_dir, 'Image')
     mkdir_p(model_dir)
@@ -160,9 +176,17 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
                                                  num_workers=int(cfg.WORKERS))
     if getattr(args, 'device_data', False):      # both splits cached on the device, batches made there
         from sbagan import device_data
-        dataloader = device_data.from_cfg(dataset, imsize, args.manualSeed, args.device_data_gb)
+        if not retrieval_only:
+            dataloader = device_data.from_cfg(dataset, imsize, args.manualSeed, args.device_data_gb)
         dataloader_val = device_data.from_cfg(dataset_val, imsize, args.manualSeed + 1, args.device_data_gb)
     text_encoder, image_encoder, labels, start_epoch = build(dataset.n_words, batch_size)
+    if retrieval_only:      # the loaded pair, ranked once: no training, no checkpoint
+        result = retrieval(dataset_val, dataloader_val, image_encoder, text_encoder, imsize)
+        from sbagan.retrieval import format_line
+        print(format_line(start_epoch - 1, result))
+        with open(os.path.join(output_dir, 'retrieval.json'), 'w') as f:
+            json.dump(dict(result, net_e=cfg.TRAIN.NET_E), f, indent=1, sort_keys=True)
+        return output_dir
     from sbagan.damsm import DAMSMSlotStep, DAMSMStep
     from sbagan.encoders import BertEncoder
     replay = bool(getattr(args, 'replay', False)) and cfg.TRAIN.FLAG
@@ -177,6 +201,7 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
             dataloader.bind(damsm.slot)     # the device loader writes every training batch straight into the slot
     else:
         damsm = DAMSMStep(text_encoder, image_encoder, batch_size, lr=cfg.TRAIN.ENCODER_LR)
+    retrieval_every = int(getattr(args, 'retrieval', 0) or 0)
     try:
         lr = cfg.TRAIN.ENCODER_LR
         for epoch in range(start_epoch, cfg.TRAIN.MAX_EPOCH):
@@ -187,6 +212,13 @@ def main(argv=None, max_steps=None, args=None, dataset_cls=TextDataset, build=No
             if len(dataloader_val) > 0:
                 s_loss, w_loss = evaluate(dataloader_val, image_encoder, text_encoder, batch_size, damsm)
                 print('| end epoch {:3d} | valid loss {:5.2f} {:5.2f} | lr {:.5f}|'.format(epoch, s_loss, w_loss, lr))
+            last = epoch + 1 >= cfg.TRAIN.MAX_EPOCH or max_steps is not None
+            if retrieval_every and len(dataset_val) > 0 and (epoch % retrieval_every == 0 or last):
+                from sbagan.retrieval import format_line
+                result = retrieval(dataset_val, dataloader_val, image_encoder, text_encoder, imsize)
+                print(format_line(epoch, result))
+                with open(os.path.join(model_dir, 'retrieval.jsonl'), 'a') as f:
+                    f.write(json.dumps(dict(result, epoch=epoch, lr=lr), sort_keys=True) + '\n')
             print('-' * 89)
             if lr > cfg.TRAIN.ENCODER_LR / 10.:
                 lr *= 0.98

@@ -10,7 +10,7 @@ import os
 import torch  # noqa: F401  -- FIRST: PyTorch-ROCm brings its own libamdhip64; if this library is loaded before
 #                     it, it binds /opt/rocm's copy and its kernels are registered with a HIP runtime that does
 #                     not own torch's streams (every launch then fails)
-from ctypes import (POINTER, Structure, byref, c_char_p, c_float, c_int, c_int8, c_int32, c_int64,
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int8, c_int32, c_int64,
                     c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -148,6 +148,8 @@ SIGNATURES = {
     'sba_fid_finalize': [P, P, L, I, P, P, P, P],
     'sba_prdc_knn_radius': [P, I, I, I, I, I, P, P, L, P],
     'sba_prdc_ball_counts': [P, I, I, P, I, I, I, P, P, I, P, P, P, L, P],
+    'sba_retrieval_own_best': [P, I, I, P, I, I, I, P, P, c_double, I, P, P, L, P],
+    'sba_retrieval_counts': [P, I, I, P, I, I, I, P, P, P, P, P, c_double, I, P, P, P, L, P],
     'sba_kid_kernel_sums': [P, I, I, P, I, P, I, I, P, I, I, I, I, I, P, P, L, P],
     'sba_msssim_pairs': [P, I, I, I, P, I, I, P, P, L, P],
     'sba_swd_descriptors': [P, L, I, I, P, I, P, P, P, L, P],
@@ -189,6 +191,8 @@ lib.sba_damsm_bwd_bytes.restype = c_int64
 lib.sba_damsm_bwd_bytes.argtypes = [I, I, I, I]
 lib.sba_prdc_workspace_bytes.restype = c_int64
 lib.sba_prdc_workspace_bytes.argtypes = [I, I, I]
+lib.sba_retrieval_workspace_bytes.restype = c_int64
+lib.sba_retrieval_workspace_bytes.argtypes = [I, I, I]
 lib.sba_kid_workspace_bytes.restype = c_int64
 lib.sba_kid_workspace_bytes.argtypes = [I, I, I, I]
 lib.sba_msssim_workspace_bytes.restype = c_int64

@@ -239,6 +239,16 @@ class DeviceBatchLoader(object):
         return Draws(index, x1[order], y1[order], flip[order], which[order], np.stack(captions)[order], lengths[order],
                      np.asarray([ds.class_id[int(i)] for i in index]), [ds.filenames[int(i)] for i in index])
 
+    def center_batch(self, indices):
+        """float32 [n][3][crop][crop] on the device: the given images through the same sba_batch_pyramid launch, each
+        with the window in the middle, ((W - crop) // 2, (H - crop) // 2), and not flipped (sbagan.retrieval).  It
+        draws nothing, touches neither `last_draws` nor a bound slot, and returns fresh tensors."""
+        index = np.asarray(list(indices), dtype=np.int64)
+        hw = self.cache.hw_host[index].astype(np.int64)
+        x1, y1 = (hw[:, 1] - self.crop) // 2, (hw[:, 0] - self.crop) // 2
+        params = np.stack([index, x1, y1, np.zeros_like(index)], axis=1).astype(np.int32)
+        return ops.batch_pyramid(self.cache, params, self.crop, 1)[0]
+
     def bind(self, slot):
         """Write every further batch straight into `slot` (sbagan.static_batch.StaticBatch; None: back to fresh
         tensors per batch): captions, lengths, CLASS IDS and params go up in the loader's single upload, into the

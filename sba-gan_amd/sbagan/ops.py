@@ -2103,7 +2103,7 @@ def vis_compose(V, band, desc, par, band_rgb, expanded=None, imgs0=None, imgs1=N
 
 
 # ----------------------------------------------------------------------------
-# evaluation (sbagan/fid.py, sbagan/prdc.py, sbagan/kid.py): what the three kernel families check alike
+# evaluation (sbagan/fid.py, sbagan/prdc.py, sbagan/retrieval.py, sbagan/kid.py): what the kernel families check alike
 EVAL_MAX_SPLITS = 32
 PRDC_MAX_SPLITS = KID_MAX_SPLITS = EVAL_MAX_SPLITS
 
@@ -2243,6 +2243,75 @@ def prdc_ball_counts(a, b, radius_a=None, radius_b=None, splits=0):
     call('sba_prdc_ball_counts', _p(a), na, lda, _p(b), nb, ldb, D, _p(radius_a), _p(radius_b), splits, _p(in_b),
          _p(in_own), _p(ws), nbytes, _stream())
     return in_b, in_own
+
+
+# ----------------------------------------------------------------------------
+# evaluation: cross-modal retrieval ranks of the DAMSM encoders (sbagan/retrieval.py)
+def _retrieval_workspace(name, na, nb, splits, device):
+    """(workspace tensor or None, its size in bytes) for a launch over na x nb rows"""
+    _eval_splits(name, splits)
+    nbytes = int(_lib.lib.sba_retrieval_workspace_bytes(na, nb, splits))
+    if nbytes < 0:
+        raise ValueError('%s: no workspace size for %d x %d rows in %d splits' % (name, na, nb, splits))
+    if nbytes == 0:
+        return None, 0
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), nbytes
+
+
+def _retrieval_rows(name, a, b, key_a, key_b, eps):
+    na, D, lda = _feature_rows(name, a, 'a')
+    nb, _, ldb = _feature_rows(name, b, 'b', a.device, D)
+    for what, v, n in (('key_a', key_a, na), ('key_b', key_b, nb)):
+        _retrieval_vector(name, v, what, torch.int32, n, a.device)
+    eps = float(eps)
+    if not eps > 0.0:
+        raise ValueError('%s: eps must be positive (got %r)' % (name, eps))
+    return na, nb, D, lda, ldb, eps
+
+
+def _retrieval_vector(name, v, what, dtype, n, device):
+    _vis_need(name, v, what, dtype, 1)
+    if v.shape[0] != n or v.device != device:
+        raise ValueError('%s: %s must be [%d] on %s (got %s on %s)' % (name, what, n, device, tuple(v.shape), v.device))
+
+
+def retrieval_own_best(a, b, key_a, key_b, eps=1e-8, splits=0):
+    """best [na] f64 (sba_retrieval_own_best): for every row i of a [na][D] the largest float64 cosine score
+    s(i, j) = a_i . b_j / max(sqrt(|a_i|^2 |b_j|^2), eps) over the rows j of b [nb][D] with key_b[j] == key_a[i]; -inf
+    when there is none, NaN when any such score is NaN.  a, b: f32 rows on the device, unit column stride, row stride >= D
+    and a multiple of 4, 16-byte aligned, D % 64 == 0; key_a [na], key_b [nb]: contiguous int32 on the same device (only
+    compared).  s(i, j) has the same bits for every split count and whichever set is `a`.  The workspace is a torch
+    allocation on the current stream; no host sync.  Everything is checked before the launch: TypeError for a dtype,
+    ValueError for a shape, a stride, an alignment, eps or splits."""
+    name = 'retrieval_own_best'
+    na, nb, D, lda, ldb, eps = _retrieval_rows(name, a, b, key_a, key_b, eps)
+    ws, nbytes = _retrieval_workspace(name, na, nb, splits, a.device)
+    best = torch.empty(na, dtype=torch.float64, device=a.device)
+    call('sba_retrieval_own_best', _p(a), na, lda, _p(b), nb, ldb, D, _p(key_a), _p(key_b), eps, splits, _p(best), _p(ws),
+         nbytes, _stream())
+    return best
+
+
+def retrieval_counts(a, b, key_a, key_b, best, cls_a=None, cls_b=None, eps=1e-8, splits=0):
+    """(above, above_masked), int32 [na] each (sba_retrieval_counts): above[i] = #{j : key_b[j] != key_a[i] and
+    NOT (s(i, j) < best[i])} over the rows j of b -- a tie counts and so does a NaN on either side -- and above_masked[i]
+    the same count over the rows whose class differs as well (cls_b[j] != cls_a[i]); None when cls_a and cls_b are None
+    (they go together).  best [na]: contiguous f64, retrieval_own_best's.  Rows, keys, splits, workspace and refusals as
+    in retrieval_own_best."""
+    name = 'retrieval_counts'
+    na, nb, D, lda, ldb, eps = _retrieval_rows(name, a, b, key_a, key_b, eps)
+    _retrieval_vector(name, best, 'best', torch.float64, na, a.device)
+    if (cls_a is None) != (cls_b is None):
+        raise ValueError('%s: cls_a and cls_b go together' % name)
+    if cls_a is not None:
+        _retrieval_vector(name, cls_a, 'cls_a', torch.int32, na, a.device)
+        _retrieval_vector(name, cls_b, 'cls_b', torch.int32, nb, a.device)
+    ws, nbytes = _retrieval_workspace(name, na, nb, splits, a.device)
+    above = torch.empty(na, dtype=torch.int32, device=a.device)
+    above_masked = torch.empty(na, dtype=torch.int32, device=a.device) if cls_a is not None else None
+    call('sba_retrieval_counts', _p(a), na, lda, _p(b), nb, ldb, D, _p(key_a), _p(key_b), _p(cls_a), _p(cls_b), _p(best),
+         eps, splits, _p(above), _p(above_masked), _p(ws), nbytes, _stream())
+    return above, above_masked
 
 
 # ----------------------------------------------------------------------------

@@ -95,7 +95,11 @@ class StreamAudit(object):
     def start(self):
         assert not self._active
         torch.cuda.synchronize()
-        self._marker = torch.cuda.Stream(device=self.device)
+        # a stream of the HIGH-priority pool, which nothing else here draws from: torch hands its streams out round robin
+        # from 32 per priority, so a default-priority marker can be the very stream a long-lived side stream (the
+        # weight-gradient companions of ops, made once per process) already is, depending on how many streams the
+        # process has made before -- and that stream's own small allocations would then be read as markers
+        self._marker = torch.cuda.Stream(device=self.device, priority=-1)
         self._busy = False
         # live blocks at the start (everything allocated before the audit): address ranges and their pool's stream
         self._initial = []
