@@ -728,6 +728,21 @@ int sba_prdc_ball_counts(const float* a, int na, int lda, const float* b, int nb
                          const double* radius_b, int splits, int32_t* in_b, int32_t* in_own, void* ws, int64_t ws_bytes,
                          void* stream);
 
+/* Nearest rows of another set (evaluation; sbagan/nearest.py): for every row i of a [na][D] the k rows j of
+ * b [nb][D] with the smallest (d2(i, j), j) in lexicographic order, ascending: d2 [na][k] float64 and idx [na][k] int32.
+ * Rows and d2(i, j) are those of sba_prdc_* above, bit for bit (one shared tile function computes both).  A tie in d2
+ * goes to the smaller j.  A NaN d2 is never listed, nor is a d2 of +inf; where b has fewer than k listable rows the tail
+ * is d2 = +inf, idx = -1, so a query row that holds a NaN comes back all +inf / -1.  The key is a total order, so the
+ * result has the same bits and the same indices for every tile, split count and launch.  1 <= k <= 8, na >= 1, nb >= 1.
+ * splits, ws as above: with more than one part the per-part lists go to `ws` (8-byte aligned, at least
+ * sba_knn_workspace_bytes(na, nb, k, splits) bytes; -1 for bad arguments, 0 when one part is used and ws may be null)
+ * and a second small launch merges them under the same key.  No atomics, no memset, no allocation.
+ * SBA_E_ARG before any launch, and nothing written, on a null pointer, bad D, k, n, strides, alignment (d2 8 bytes, idx
+ * 4), splits or a workspace too small. */
+int64_t sba_knn_workspace_bytes(int na, int nb, int k, int splits);
+int sba_knn_topk(const float* a, int na, int lda, const float* b, int nb, int ldb, int D, int k, int splits, double* d2,
+                 int32_t* idx, void* ws, int64_t ws_bytes, void* stream);
+
 /* Cross-modal retrieval ranks (evaluation of the DAMSM encoders; sbagan/retrieval.py): all-pairs cosine
  * scores between two sets of f32 code rows (rows as for the k-NN metrics above) with a row-wise selection fused behind
  * them; the na x nb matrix is never written.  All score arithmetic is float64:

@@ -1,7 +1,8 @@
-// Shared by the evaluation units fid.hip, prdc.hip, retrieval.hip and kid.hip: the 64 x 64 float64 tile on the f64 matrix
-// instruction (v_mfma_f64_16x16x4_f64) that 256 threads compute as four waves of 2 x 2 MFMA tiles.  All use the lane map
-// and the MFMA step; prdc.hip, retrieval.hip and kid.hip also the feature-major pair tile (dot products of 64 A rows with
-// 64 B rows, the f32 rows widened in registers, features in ascending order) and the host side of its column splits.
+// Shared by the evaluation units fid.hip, prdc.hip, knn.hip, retrieval.hip and kid.hip: the 64 x 64 float64 tile on the f64
+// matrix instruction (v_mfma_f64_16x16x4_f64) that 256 threads compute as four waves of 2 x 2 MFMA tiles.  All use the lane
+// map and the MFMA step; prdc.hip and knn.hip (through d2_tile.h), retrieval.hip and kid.hip also the feature-major pair
+// tile (dot products of 64 A rows with 64 B rows, the f32 rows widened in registers, features in ascending order) and the
+// host side of its column splits.
 // Internal linkage, as common.h.
 #pragma once
 #include "common.h"
@@ -93,7 +94,7 @@ __device__ __forceinline__ void f64t_stage(float* __restrict__ buf, const float4
     }
 }
 // acc += the dot products of the tile over the chunk of features staged in buf.  The chunk loop around it (fetch the next
-// chunk, this, stage the next chunk, one barrier) stays written out in prdc_kernel and kid_kernel: as a function here,
+// chunk, this, stage the next chunk, one barrier) stays written out in d2t_tile (d2_tile.h) and kid_kernel: as a function here,
 // the compiler stopped hoisting the stage and epilogue addresses out of the tile loop, and kid_kernel measured 0.3 - 0.6 %
 // slower (profiles/eval_tile_refactor.txt).
 __device__ __forceinline__ void f64t_chunk(const float* __restrict__ buf, const F64Lanes& l, f64x4_t (&acc)[2][2]) {

@@ -6,11 +6,11 @@
 // d2(i, j) has the same bits whichever tile or column split computed it, and d2(i, j) == d2(j, i) bitwise for A = B.
 // No atomics, no memset, no allocation: partial results of column splits go to a caller-provided workspace and a second
 // small launch merges them in split order.
-#include "f64_tile.h"
+#include "d2_tile.h"
 
 namespace {
 
-constexpr int PRDC_TLD = F64T_TILE + 1;         // row stride of the finished d2 tile in doubles
+constexpr int PRDC_TLD = D2T_LD;
 constexpr int PRDC_K = 8;                       // the longest neighbour list
 
 // ascending list of the PRDC_K smallest values seen
@@ -37,12 +37,8 @@ __global__ __launch_bounds__(F64T_THREADS) void prdc_kernel(const float* __restr
                                                             const double* __restrict__ ra, const double* __restrict__ rb,
                                                             int k, int direct, double* __restrict__ out_d,
                                                             int32_t* __restrict__ out_i0, int32_t* __restrict__ out_i1) {
-    __shared__ __attribute__((aligned(16))) float sh[2][F64T_STAGE];
-    __shared__ double sh_part[2 * F64T_TILE][8];        // per staged row: the norm partials of its 8 feature groups
-    __shared__ double sh_norm[2 * F64T_TILE];
-    static_assert(sizeof(double) * F64T_TILE * PRDC_TLD <= sizeof(sh), "the d2 tile lives in the staging buffers");
-    double* sh_d2 = reinterpret_cast<double*>(&sh[0][0]);      // the finished tile, afterwards the lists / counts
-                                                        // of a row: over the staging buffers, which are idle by then
+    __shared__ D2TShared sh;
+    double* sh_d2 = d2t_tile_of(sh);                    // the finished tile, afterwards the lists / counts of a row
 
     const int i0 = blockIdx.x * F64T_TILE;
     int t0, t1;
@@ -68,47 +64,7 @@ __global__ __launch_bounds__(F64T_THREADS) void prdc_kernel(const float* __restr
         const int j0 = t * F64T_TILE;
         row[2] = f64t_row(b, nb, ldb, nullptr, nb, j0 + sr);
         row[3] = f64t_row(b, nb, ldb, nullptr, nb, j0 + sr + 32);
-        f64x4_t acc[2][2];
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int y = 0; y < 2; ++y) acc[x][y] = f64x4_t{0.0, 0.0, 0.0, 0.0};
-        double nrm[F64T_VEC];
-#pragma unroll
-        for (int s = 0; s < F64T_VEC; ++s) nrm[s] = 0.0;
-        // the squared norm of the staged rows: slot s of this thread always holds the same 4 features of the same row, so
-        // nrm[s] adds those features over the chunks in ascending order
-        const auto norms = [&](int s, const float4& x) {
-            const double x0 = (double)x.x, x1 = (double)x.y, x2 = (double)x.z, x3 = (double)x.w;
-            nrm[s] = fma(x3, x3, fma(x2, x2, fma(x1, x1, fma(x0, x0, nrm[s]))));
-        };
-
-        float4 v[F64T_VEC];
-        f64t_fetch(v, row, 0);
-        __syncthreads();                // the previous tile's epilogue has read the d2 tile these buffers held
-        f64t_stage(sh[0], v, norms);
-        __syncthreads();
-        for (int c = 0; c < chunks; ++c) {
-            const bool more = c + 1 < chunks;
-            if (more) f64t_fetch(v, row, (c + 1) * F64T_KC);
-            f64t_chunk(sh[c & 1], l, acc);
-            if (more) f64t_stage(sh[(c + 1) & 1], v, norms);  // last read in iteration c - 1, which every wave has left
-            __syncthreads();
-        }
-
-        // squared norms of the 128 staged rows: 8 partials per row, added in feature order
-#pragma unroll
-        for (int s = 0; s < F64T_VEC; ++s) sh_part[sr + 32 * s][threadIdx.x & 7] = nrm[s];
-        __syncthreads();
-        if (threadIdx.x < 2 * F64T_TILE) {
-            const double* __restrict__ p = sh_part[threadIdx.x];
-            sh_norm[threadIdx.x] = ((((((p[0] + p[1]) + p[2]) + p[3]) + p[4]) + p[5]) + p[6]) + p[7];
-        }
-        __syncthreads();
-        f64t_each(l, acc, [&](int i, int j, double g) {
-            sh_d2[i * PRDC_TLD + j] = fmax((sh_norm[i] + sh_norm[F64T_TILE + j]) - 2.0 * g, 0.0);
-        });
-        __syncthreads();
+        d2t_tile<false>(sh, row, l, chunks);
 
         // row-wise epilogue: thread (er, eq) takes columns 16 eq .. 16 eq + 15 of row er
         if (gi < na) {

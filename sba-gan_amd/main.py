@@ -9,7 +9,9 @@ overlay images, sbagan/visualize.py), --fid [--fid_stats PATH] (sampling also wr
 [--kid_subset_size M] (sampling also writes kid.json: the Kernel Inception Distance, sbagan/kid.py), --ms_ssim N
 (sampling also writes ms_ssim.json: the mean MS-SSIM over N same-class image pairs per class, sbagan/msssim.py), --swd N
 (sampling also writes swd.json: the sliced Wasserstein distance per resolution between the first N real and the first N
-generated images, sbagan/swd.py) and --device_data
+generated images, sbagan/swd.py), --nearest K [--nearest_stats PATH] [--nearest_show M] (sampling also writes nearest.json
+and nearest.png: every generated image's K nearest training images and the memorisation figures, sbagan/nearest.py) and
+--device_data
 [--device_data_gb G] (training: the split is decoded once into a device-resident cache and every batch is cropped, flipped,
 resized to every scale and normalised there, sbagan/device_data.py) and --replay (training: every batch through one
 recording of the step, read from a static batch slot, sbagan/static_batch.py) are this project's additions."""
@@ -101,6 +103,9 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo.kid_subset_size = int(getattr(args, 'kid_subset_size', 1000))
     algo.ms_ssim = int(getattr(args, 'ms_ssim', 0))
     algo.swd = int(getattr(args, 'swd', 0))
+    algo.nearest = int(getattr(args, 'nearest', 0))
+    algo.nearest_stats = getattr(args, 'nearest_stats', None)
+    algo.nearest_show = int(getattr(args, 'nearest_show', 16))
     algo.replay = bool(getattr(args, 'replay', False)) and training
     if getattr(args, 'replay', False) and not training:
         print('--replay is ignored outside training')

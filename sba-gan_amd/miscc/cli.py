@@ -2,6 +2,7 @@
 
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
     [--kid]  [--kid_subsets N]  [--kid_subset_size M]  [--ms_ssim N]  [--swd N]
+    [--nearest K]  [--nearest_stats PATH]  [--nearest_show M]
     [--device_data]  [--device_data_gb G]  [--replay]
     [--retrieval E]  [--retrieval_only: DAMSM pre-training]
     [--bert_dir DIR: the BERT entry points]
@@ -65,6 +66,20 @@ def _swd(text):
     return n
 
 
+def _nearest(text):
+    k = int(text)
+    if k < 0 or k > 8:
+        raise argparse.ArgumentTypeError('K must be 0 (off) or a neighbour count from 1 to 8')
+    return k
+
+
+def _nearest_show(text):
+    m = int(text)
+    if m < 0:
+        raise argparse.ArgumentTypeError('M must be 0 (no picture) or a number of generated images')
+    return m
+
+
 def _retrieval(text):
     e = int(text)
     if e < 0:
@@ -122,6 +137,21 @@ def options(what, default_cfg, argv=None, bert=False):
                          'the first N real and the first N generated images, per level of a Laplacian pyramid and on '
                          'average, x 1e3, and write swd.json; 0 = off, 16384 = the setting of the paper.  In pixel '
                          'space on the written uint8 images: it uses no trunk; square images of 32, 64, 128 or 256 px')
+    ap.add_argument('--nearest', dest='nearest', type=_nearest, default=0, metavar='K',
+                    help='sampling: also list the K nearest TRAINING images of every generated image on the same trunk '
+                         'features as --fid (float64 distances on the matrix cores, sbagan.nearest) and take the '
+                         'memorisation figures the other evaluations cannot see: authenticity (Alaa et al. 2022) with its '
+                         'baseline on the split\'s real images, the nearest-training-image distance of generated against '
+                         'unseen real images, the share of near-copies and how many distinct training images are hit; '
+                         'writes nearest.json and nearest.png; 0 = off, K from 1 to 8.  The training split is encoded '
+                         'once after the generation loop.  On this project\'s own trunk and compute dtype: not '
+                         'comparable with published numbers.  Ignored by the DAMSM entry points and in training')
+    ap.add_argument('--nearest_stats', dest='nearest_stats', type=str, default=None, metavar='PATH',
+                    help='with --nearest: an .npz of the training images\' feature rows and keys; read instead of the '
+                         'training pass when it exists, written after the run when it does not')
+    ap.add_argument('--nearest_show', dest='nearest_show', type=_nearest_show, default=16, metavar='M',
+                    help='with --nearest: the M generated images closest to a training image are listed in nearest.json '
+                         'and shown in nearest.png, one row each beside their K training images; 0 = no picture')
     ap.add_argument('--device_data', dest='device_data', action='store_true', default=False,
                     help='training: decode the split once into a device-resident uint8 cache and make every batch '
                          'there -- crop, flip, every scale of the pyramid and the normalisation in one HIP launch '

@@ -148,6 +148,7 @@ SIGNATURES = {
     'sba_fid_finalize': [P, P, L, I, P, P, P, P],
     'sba_prdc_knn_radius': [P, I, I, I, I, I, P, P, L, P],
     'sba_prdc_ball_counts': [P, I, I, P, I, I, I, P, P, I, P, P, P, L, P],
+    'sba_knn_topk': [P, I, I, P, I, I, I, I, I, P, P, P, L, P],
     'sba_retrieval_own_best': [P, I, I, P, I, I, I, P, P, c_double, I, P, P, L, P],
     'sba_retrieval_counts': [P, I, I, P, I, I, I, P, P, P, P, P, c_double, I, P, P, P, L, P],
     'sba_kid_kernel_sums': [P, I, I, P, I, P, I, I, P, I, I, I, I, I, P, P, L, P],
@@ -191,6 +192,8 @@ lib.sba_damsm_bwd_bytes.restype = c_int64
 lib.sba_damsm_bwd_bytes.argtypes = [I, I, I, I]
 lib.sba_prdc_workspace_bytes.restype = c_int64
 lib.sba_prdc_workspace_bytes.argtypes = [I, I, I]
+lib.sba_knn_workspace_bytes.restype = c_int64
+lib.sba_knn_workspace_bytes.argtypes = [I, I, I, I]
 lib.sba_retrieval_workspace_bytes.restype = c_int64
 lib.sba_retrieval_workspace_bytes.argtypes = [I, I, I]
 lib.sba_kid_workspace_bytes.restype = c_int64

@@ -13,9 +13,9 @@ def dtype_name(dtype=None):
     return str(dtype if dtype is not None else ops.compute_dtype()).replace('torch.', '')
 
 
-def check_side(owner, side):
-    if side not in SIDES:
-        raise ValueError("%s: side must be 'real' or 'fake' (got %r)" % (owner, side))
+def check_side(owner, side, sides=SIDES):
+    if side not in sides:
+        raise ValueError("%s: side must be %s (got %r)" % (owner, ' or '.join(repr(s) for s in sides), side))
     return side
 
 
@@ -40,18 +40,18 @@ class Evaluator(object):
 
 
 class FeatureRows(object):
-    """owner: the evaluator's name, for the messages"""
+    """owner: the evaluator's name, for the messages; sides: the sides it keeps (sbagan/nearest.py adds 'train')"""
 
-    def __init__(self, owner, D, capacity=256):
+    def __init__(self, owner, D, capacity=256, sides=SIDES):
         if D < 64 or D % 64:
             raise ValueError('%s: D must be a positive multiple of 64 (got %d)' % (owner, D))
         if capacity < 1:
             raise ValueError('%s: capacity must be >= 1 (got %d)' % (owner, capacity))
-        self.owner, self.D, self.capacity = owner, int(D), int(capacity)
+        self.owner, self.D, self.capacity, self.sides = owner, int(D), int(capacity), tuple(sides)
         self._rows = {}                             # side -> [buffer [capacity][D], rows held]
 
     def _side(self, side):
-        return check_side(self.owner, side)
+        return check_side(self.owner, side, self.sides)
 
     def append(self, side, feats):
         """one batch of feature rows [B][D] (f32, on the device); no host-device sync"""

@@ -2246,6 +2246,35 @@ def prdc_ball_counts(a, b, radius_a=None, radius_b=None, splits=0):
 
 
 # ----------------------------------------------------------------------------
+# evaluation: nearest rows of another set (sbagan/nearest.py)
+KNN_MAX_K = 8
+
+
+def knn_topk(a, b, k, splits=0):
+    """(d2 f64 [na][k], idx int32 [na][k]) on the device (sba_knn_topk): for every row i of a [na][D] the k rows j of
+    b [nb][D] with the smallest (d2(i, j), j), ascending; d2 the float64 squared distance of prdc_knn_radius, bit for
+    bit.  A tie goes to the smaller j; a NaN (or +inf) d2 is never listed; where b has fewer than k listable rows the
+    tail is d2 = +inf, idx = -1.  a, b: f32 rows on one device, unit column stride, row stride >= D and a multiple of 4,
+    16-byte aligned, D % 64 == 0; 1 <= k <= 8.  splits: column parts of the launch (0 = the library's choice); the result
+    has the same bits and indices for every value.  The workspace is a torch allocation on the current stream; no host
+    sync.  Everything is checked before the launch: TypeError for a dtype, ValueError for a shape, a stride, an
+    alignment, k or splits."""
+    na, D, lda = _feature_rows('knn_topk', a, 'a')
+    nb, _, ldb = _feature_rows('knn_topk', b, 'b', a.device, D)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError('knn_topk: k must be an integer in [1, %d] (got %r)' % (KNN_MAX_K, k))
+    _eval_splits('knn_topk', splits)
+    nbytes = int(_lib.lib.sba_knn_workspace_bytes(na, nb, k, splits))
+    if nbytes < 0:
+        raise ValueError('knn_topk: no workspace size for %d x %d rows, k = %d, in %d splits' % (na, nb, k, splits))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device) if nbytes else None
+    d2 = torch.empty((na, k), dtype=torch.float64, device=a.device)
+    idx = torch.empty((na, k), dtype=torch.int32, device=a.device)
+    call('sba_knn_topk', _p(a), na, lda, _p(b), nb, ldb, D, k, splits, _p(d2), _p(idx), _p(ws), nbytes, _stream())
+    return d2, idx
+
+
+# ----------------------------------------------------------------------------
 # evaluation: cross-modal retrieval ranks of the DAMSM encoders (sbagan/retrieval.py)
 def _retrieval_workspace(name, na, nb, splits, device):
     """(workspace tensor or None, its size in bytes) for a launch over na x nb rows"""

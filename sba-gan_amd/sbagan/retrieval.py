@@ -69,12 +69,24 @@ class _CenterCrops(data.Dataset):
     def __len__(self):
         return len(self.dataset)
 
-    def __getitem__(self, index):
+    def window(self, index):
+        """the PIL image before the normalisation"""
         img = datasets.load_image(self.dataset.image_path(index), self.dataset.image_box(index), self.resize)
         W, H = img.size
         x1, y1 = center_offsets([(H, W)], self.crop)
         x1, y1 = int(x1[0]), int(y1[0])
-        return self.dataset.norm(img.crop((x1, y1, x1 + self.crop, y1 + self.crop)))
+        return img.crop((x1, y1, x1 + self.crop, y1 + self.crop))
+
+    def __getitem__(self, index):
+        return self.dataset.norm(self.window(index))
+
+
+def center_loader(dataset, batch, crop, resize, workers=0):
+    """the images of `dataset` in order as _CenterCrops prepares them, in batches of `batch` (the last may be short).  The
+    loader takes a torch.Generator of its own, so torch's global generator is not consumed (sbagan/nearest.py reads the
+    training split through it too)"""
+    return data.DataLoader(_CenterCrops(dataset, crop, resize), batch_size=int(batch), shuffle=False, drop_last=False,
+                           num_workers=int(workers), generator=torch.Generator())
 
 
 def encode_images(dataset, image_encoder, batch, crop, resize, cache=None, workers=0):
@@ -98,8 +110,7 @@ def encode_images(dataset, image_encoder, batch, crop, resize, cache=None, worke
         loader = DeviceBatchLoader(dataset, cache, batch, crop, 1, 0, shuffle=False, drop_last=False)
         batches = (loader.center_batch(range(lo, min(lo + batch, n))) for lo in range(0, n, batch))
     else:
-        batches = data.DataLoader(_CenterCrops(dataset, crop, resize), batch_size=batch, shuffle=False, drop_last=False,
-                                  num_workers=int(workers), generator=torch.Generator())
+        batches = center_loader(dataset, batch, crop, resize, workers)
     mode = image_encoder.training
     image_encoder.eval()
     codes = []

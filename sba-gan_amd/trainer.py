@@ -32,6 +32,11 @@ from model import CNN_ENCODER, D_NET64, D_NET128, D_NET256, G_NET, RNN_ENCODER
 from sbagan.trainer import GANStep, build_mask, prepare_labels
 
 
+def _figure(value):
+    """a figure that may be missing (sbagan.nearest reports None where no row has a neighbour)"""
+    return 'n/a' if value is None else '%.6g' % value
+
+
 def _to_uint8(img):
     """[-1, 1] CHW float -> HWC uint8 (trainer.py:419-422)."""
     im = (img.detach().float().cpu().numpy() + 1.0) * 127.5
@@ -480,6 +485,56 @@ class condGANTrainer(object):
             raise ValueError('swd must be 0 (off) or a number of images per side (got %r)' % (self.swd,))
         return SWD(self.swd, size=cli.image_size(), seed=self.swd_seed, images=ms_ssim)
 
+    nearest = 0                 # --nearest K: sampling() also lists every generated image's K nearest TRAINING images and takes
+    #                             the memorisation figures of sbagan.nearest (0 = off)
+    nearest_stats = None        # --nearest_stats PATH: the training rows and keys, read when present, written when not
+    nearest_show = 16           # --nearest_show M: suspects in nearest.json and rows of nearest.png (0: no picture)
+    nearest_result = None       # the result dict of the last sampling() with nearest != 0
+    nearest_evaluator = None
+
+    def _nearest_evaluator(self, image_encoder):
+        """sbagan.nearest.Nearest on the pooled trunk feature of `image_encoder` (an InceptionHIP); the training side
+        comes from nearest_stats when that file exists"""
+        from miscc import cli
+        from sbagan import ops
+        from sbagan.feature_rows import dtype_name
+        from sbagan.nearest import Nearest, stats_key
+        if isinstance(self.nearest, bool) or not isinstance(self.nearest, int) or not 1 <= self.nearest <= ops.KNN_MAX_K:
+            raise ValueError('nearest must be 0 (off) or a neighbour count from 1 to %d (got %r)'
+                             % (ops.KNN_MAX_K, self.nearest))
+        dtype = dtype_name()
+        key = stats_key(cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder'), dtype, 'train', cli.image_size())
+        evaluator = Nearest(image_encoder.pooled_features, D=2048, k=self.nearest, show=int(self.nearest_show), key=key,
+                            dtype=dtype)
+        if self.nearest_stats and os.path.exists(self.nearest_stats):
+            evaluator.load_train(self.nearest_stats, self.device)
+            print('Load training rows from:', self.nearest_stats)
+        return evaluator
+
+    def _train_crops(self):
+        """the training split as the nearest-neighbour pass reads it: the data set class of the sampled split on 'train',
+        every image through retrieval._CenterCrops at the size the sampling loader yields for its last scale"""
+        from miscc import cli
+        from sbagan.retrieval import _CenterCrops
+        sampled = self.data_loader.dataset
+        extra = {'bert_dir': sampled.bert_dir} if hasattr(sampled, 'bert_dir') else {}
+        train = type(sampled)(sampled.data_dir, 'train', base_size=cfg.TREE.BASE_SIZE, transform=None, **extra)
+        imsize = cli.image_size()
+        return _CenterCrops(train, imsize, int(imsize * 76 / 64))
+
+    def _nearest_finish(self, nearest, res, out_dir, crops):
+        """after the result: the cache of the training rows, and nearest.png (sbagan.nearest.write_sheet)"""
+        from sbagan.nearest import write_sheet
+        if self.nearest_stats and not nearest.is_loaded():
+            nearest.save_train(self.nearest_stats)
+            print('Save training rows to:', self.nearest_stats)
+        if nearest.show:
+            crops = crops if crops is not None else self._train_crops()
+            if [str(k) for k in crops.dataset.filenames] != nearest.keys['train']:
+                raise RuntimeError('nearest: the cached training keys are not those of the training split')
+            write_sheet(os.path.join(out_dir, 'nearest.png'), res['suspects'], nearest.k,
+                        lambda key: os.path.join(out_dir, 'single', key) + '_s-1.png', crops.window)
+
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split."""
         root = self._output_root()
@@ -491,8 +546,8 @@ class condGANTrainer(object):
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
         evaluator = self._r_precision_evaluator(text_encoder) if self.r_precision else None
-        fid = fid_real = prdc = kid = None
-        if self.fid or self.prdc or self.kid:       # one image encoder serves the four evaluators
+        fid = fid_real = prdc = kid = nearest = None
+        if self.fid or self.prdc or self.kid or self.nearest:       # one image encoder serves the five evaluators
             image_encoder = evaluator.image_encoder if evaluator is not None else self._load_image_encoder()
         if self.fid:
             fid = self._fid_evaluator(image_encoder, split_dir)
@@ -501,6 +556,8 @@ class condGANTrainer(object):
             prdc = self._prdc_evaluator(image_encoder)
         if self.kid:
             kid = self._kid_evaluator(image_encoder, prdc)
+        if self.nearest:
+            nearest = self._nearest_evaluator(image_encoder)
         # who takes the fake rows and who the real ones: FID its moments, PRDC the rows, KID the rows unless PRDC has them
         keeps = [ev for ev in (prdc, kid if prdc is None else None) if ev is not None]
         takes_fake = ([fid] if fid is not None else []) + keeps
@@ -515,15 +572,19 @@ class condGANTrainer(object):
             last = fake_imgs[-1]
             if evaluator is not None:
                 evaluator.update(last, sent_emb, class_ids)
-            if takes_fake:                      # each batch goes through the trunk once, for all of them
+            if takes_fake or nearest is not None:       # each batch goes through the trunk once, for all of them
                 if evaluator is None:           # (R-precision has otherwise just run this batch through it)
                     image_encoder.pooled_features(last)
                 for ev in takes_fake:
                     ev.update_features('fake', image_encoder.last_pooled)
-                if takes_real:                  # with cached FID statistics: encoded for PRDC and KID alone
+                if nearest is not None:         # (its rows go with their keys)
+                    nearest.update_features('fake', image_encoder.last_pooled, keys)
+                if takes_real or nearest is not None:   # with cached FID statistics: encoded for the others alone
                     real_feats = image_encoder.pooled_features(real_imgs[-1])
                     for ev in takes_real:
                         ev.update_features('real', real_feats)
+                    if nearest is not None:
+                        nearest.update_features('real', real_feats)
             if ms_ssim is not None:             # the pixels themselves: no trunk
                 ms_ssim.update('fake', last, class_ids)
                 ms_ssim.update('real', real_imgs[-1], class_ids)
@@ -532,6 +593,14 @@ class condGANTrainer(object):
                 swd.update('real', real_imgs[-1])
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
+        train_crops = None
+        if nearest is not None and not nearest.is_loaded():     # the training split, once, after the generation loop
+            from sbagan.nearest import encode_train
+            train_crops = self._train_crops()
+            rows, train_keys = encode_train(train_crops.dataset, image_encoder.pooled_features, self.batch_size,
+                                            train_crops.crop, train_crops.resize, self.device,
+                                            getattr(self.data_loader, 'num_workers', 0))
+            nearest.update_features('train', rows, train_keys)
         # (attribute stem and file name, evaluator, the printed line, the result fields it shows: a name, or a function
         # of the result)
         reports = (
@@ -551,7 +620,13 @@ class condGANTrainer(object):
               'ms_ssim_real', 'ms_ssim_real_std')),
             ('swd', swd, 'SWD x 1e3 (%d real and %d generated images, %d patches each, %d directions): %s  average %.6g',
              ('n_images', 'n_images', 'patches_per_image', lambda r: r['dir_repeats'] * r['dirs_per_repeat'],
-              lambda r: '  '.join('%d px %.6g' % v for v in zip(r['resolutions'], r['swd_x1e3'])), 'swd_avg_x1e3')))
+              lambda r: '  '.join('%d px %.6g' % v for v in zip(r['resolutions'], r['swd_x1e3'])), 'swd_avg_x1e3')),
+            ('nearest', nearest, 'Nearest training images (K = %d, %d training, %d real, %d generated images, %s trunk, this '
+             'project\'s own features): authenticity %.4f (real %.4f)  median distance %s (real %s, ratio %s)  '
+             'copies %.4f  distinct training images hit %.4f  most hits on one %d',
+             ('k', 'n_train', 'n_real', 'n_fake', 'dtype', 'authenticity', 'authenticity_real',
+              lambda r: _figure(r['nn_dist_fake']['median']), lambda r: _figure(r['nn_dist_real']['median']),
+              lambda r: _figure(r['nn_ratio']), 'copy_fraction', 'train_hit_distinct', 'train_hit_max')))
         for stem, ev, line, fields in reports:
             if ev is None:
                 continue
@@ -564,6 +639,8 @@ class condGANTrainer(object):
             if ev is fid and self.fid_stats and fid_real:
                 fid.save_real(self.fid_stats)
                 print('Save real FID statistics to:', self.fid_stats)
+            if ev is nearest:
+                self._nearest_finish(nearest, res, out_dir, train_crops)
         return out_dir
 
     def gen_example(self, data_dic):
