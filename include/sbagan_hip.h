@@ -929,6 +929,31 @@ int sba_clip_adam_prepare(void* state, const double* partials, int nparts, const
 int sba_adam_step_dscale(float* p, const float* g, float* m, float* v, float* avg, void* shadow, const void* state,
                          int64_t n, float beta1, float beta2, float eps, const float* grad_scale_dev, void* stream);
 
+/* Differentiable Augmentation of the images a discriminator sees (Zhao et al., NeurIPS 2020, policy
+ * color,translation,cutout; csrc/diffaug.hip, sbagan/ops.py: DiffAugFn).  Images are f32 NCHW [n][3][S][S],
+ * contiguous, 16-byte aligned.  params [n][8] f32: row n holds seven uniforms u0..u6 in [0, 1) (column 7 is unused).
+ * flags: 1 color | 2 translation | 4 cutout; a part that is off is skipped.
+ *   color        x + (u0 - 0.5);  (x - mean_c x) * (2 u1) + mean_c x;  (x - mean_chw x) * (u2 + 0.5) + mean_chw x
+ *   translation  shift = int(S / 8 + 0.5), ty = min(int(u3 * (2 shift + 1)), 2 shift) - shift (product in f32), tx from u4;
+ *                out[i][j] = in[i + ty][j + tx] inside the image, +0.0 elsewhere
+ *   cutout       cut = int(S / 2 + 0.5), oy = min(int(u5 * (S + 1 - cut % 2)), S - cut % 2), ox from u6; output rows
+ *                [oy - cut / 2, oy - cut / 2 + cut) and the same columns, intersected with the image, are +0.0
+ * With color off every output element is a bit-exact copy of an input element or +0.0.
+ * sba_diffaug_fwd: out [(nr + nf)] = the transform of [real (nr images) | fake (nf images)] -- the concatenation and the
+ *   augmentation in one pass; real may be NULL with nr = 0.
+ * sba_diffaug_bwd: dx [n] = the gradient of the n inputs for the output gradient dout [n] (the map is affine in x: no saved
+ *   input).  With color off dx is the exact scatter of dout.
+ * workspace: sba_diffaug_workspace_bytes(n, S) bytes (n = nr + nf), 8-byte aligned, needed with color on only: the f64
+ *   partial sums of the per-image reductions, added in a fixed order that depends on S alone.  No atomics; two calls
+ *   give the same bits.  Per-element math is f32.
+ * SBA_E_ARG before any launch unless 8 <= S <= 4096, S even, 1 <= flags <= 7, nr, nf >= 0, 1 <= nr + nf <= 65535, and
+ * on a needed pointer that is NULL or misaligned. */
+int64_t sba_diffaug_workspace_bytes(int n, int S);
+int sba_diffaug_fwd(const float* real, int nr, const float* fake, int nf, const float* params, float* out, int S,
+                    int flags, void* workspace, void* stream);
+int sba_diffaug_bwd(const float* dout, int n, const float* params, float* dx, int S, int flags, void* workspace,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

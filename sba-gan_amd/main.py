@@ -109,6 +109,9 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo.replay = bool(getattr(args, 'replay', False)) and training
     if getattr(args, 'replay', False) and not training:
         print('--replay is ignored outside training')
+    algo.diffaug = getattr(args, 'diffaug', '') if training else ''
+    if getattr(args, 'diffaug', '') and not training:
+        print('--diffaug is ignored outside training')
     start_t = time.time()
     if training:
         algo.train()

@@ -3,7 +3,7 @@
     --cfg FILE  --gpu ID  --data_dir DIR  --manualSeed N  [--fused_inference]  [--r_precision R]  [--attention_maps]  [--fid]  [--fid_stats PATH]  [--prdc K]
     [--kid]  [--kid_subsets N]  [--kid_subset_size M]  [--ms_ssim N]  [--swd N]
     [--nearest K]  [--nearest_stats PATH]  [--nearest_show M]
-    [--device_data]  [--device_data_gb G]  [--replay]
+    [--device_data]  [--device_data_gb G]  [--replay]  [--diffaug POLICY]
     [--retrieval E]  [--retrieval_only: DAMSM pre-training]
     [--bert_dir DIR: the BERT entry points]
 
@@ -78,6 +78,18 @@ def _nearest_show(text):
     if m < 0:
         raise argparse.ArgumentTypeError('M must be 0 (no picture) or a number of generated images')
     return m
+
+
+DIFFAUG_POLICIES = ('color', 'translation', 'cutout')
+
+
+def _diffaug(text):
+    names = [n.strip() for n in text.split(',')] if text else []
+    for n in names:
+        if n not in DIFFAUG_POLICIES:
+            raise argparse.ArgumentTypeError('unknown policy %r; valid names are %s (comma separated)'
+                                             % (n, ', '.join(DIFFAUG_POLICIES)))
+    return ','.join(names)
 
 
 def _retrieval(text):
@@ -168,6 +180,14 @@ def options(what, default_cfg, argv=None, bert=False):
                          '(sbagan.damsm.DAMSMSlotStep), the dropout mask is drawn per batch outside it and the losses '
                          'are read only where the interval line is printed.  Ignored by pretrain_DAMSM_bert.py and '
                          'outside training')
+    ap.add_argument('--diffaug', dest='diffaug', type=_diffaug, default='', metavar='POLICY',
+                    help='GAN training: Differentiable Augmentation (Zhao et al., NeurIPS 2020) of every image a '
+                         'discriminator sees -- real and fake images in the discriminator updates, fake images in the '
+                         'generator\'s adversarial terms, each with its own random draws, gradients flowing through to '
+                         'the generator (sbagan.diffaug, one fused HIP pass in place of the step\'s concatenation).  '
+                         'POLICY: a comma-separated subset of color,translation,cutout; empty = off.  The DAMSM terms, '
+                         'sampling, the image dumps and checkpoints see un-augmented images.  Single GPU only.  Ignored '
+                         'outside training and by the DAMSM pre-training entry points')
     ap.add_argument('--retrieval', dest='retrieval', type=_retrieval, default=0, metavar='E',
                     help='DAMSM pre-training: after the validation pass of every E-th epoch and of the last one, rank '
                          'every image of the validation split against every caption and every caption against every '

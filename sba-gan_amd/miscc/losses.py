@@ -126,7 +126,8 @@ def g_term_heads(n, uncond):
     return (H(0, n, 0, 1., 1., 0),)
 
 
-def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake_labels, real_features=None):
+def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake_labels, real_features=None,
+                       augment=None):
     """losses.py:136-161: the real and the fake.detach() trunk pass, five heads,
     errD = (real + cond_real)/2 + (fake + cond_fake + cond_wrong)/3.
 
@@ -137,7 +138,13 @@ def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake
     real_features (optional, beyond the reference's signature): netD(real_imgs) evaluated AHEAD of this call (the
     data-parallel step runs it beside the generator's gradient exchange: it does not depend on the generator); the
     fake half then runs as its own pass, in the reference's order (real first), with the same per-pass BatchNorm
-    batches and running-statistic updates."""
+    batches and running-statistic updates.
+
+    augment (optional, (rows, flags): f32 uniforms [2n][8] -- n rows for the real images, then n for the fake ones -- and
+    the policy bits of sbagan.diffaug): Differentiable Augmentation of both halves.  ops.diffaug writes the augmented
+    [real | fake] batch in one pass, in place of the concatenation; not available with real_features."""
+    if augment is not None and real_features is not None:
+        raise ValueError('discriminator_loss: augment does not go with real_features (the two-pass layout)')
     if real_features is not None:
         real, fake = real_features, netD(fake_imgs.detach())
     else:
@@ -145,7 +152,10 @@ def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake
     if real.shape != fake.shape:
         raise ValueError('discriminator_loss: real %s and fake %s differ in shape'
                          % (tuple(real.shape), tuple(fake.shape)))
-    feats = torch.cat((real, fake), 0)
+    if augment is not None:
+        feats = ops.diffaug(real, fake, augment[0], augment[1])
+    else:
+        feats = torch.cat((real, fake), 0)
     if real_features is None:
         feats = netD(feats, groups=2)
     return ops.d_heads(netD, feats, conditions, d_term_heads(real.size(0), netD.UNCOND_DNET is not None))
@@ -187,7 +197,7 @@ def _g_term(netD, features, sent_emb):
     return ops.d_heads(netD, features, sent_emb, g_term_heads(features.size(0), netD.UNCOND_DNET is not None))
 
 
-def generator_d_term(netD, fake_img, sent_emb):
+def generator_d_term(netD, fake_img, sent_emb, augment=None):
     """One discriminator's term of generator_loss (losses.py:168-186) on its own, together with its gradient with
     respect to the fake images: returns (g_loss, d g_loss / d fake_img).
 
@@ -196,15 +206,19 @@ def generator_d_term(netD, fake_img, sent_emb):
     optimizer step, while the other discriminators are still updating, and hand the image gradients to the generator's
     single backward pass later (generator_loss(..., d_terms=...), backward_with_image_grads); by linearity the parameter
     gradients are those of the reference's backward pass of errG_total.  The discriminator's parameters must not
-    require gradients (the reference computes and discards them, trainer.py:270,287)."""
+    require gradients (the reference computes and discards them, trainer.py:270,287).
+
+    augment (optional, (rows [n][8], flags)): the discriminator sees the augmented image (ops.diffaug); the returned
+    gradient is with respect to the image itself, through the augmentation."""
     leaf = fake_img.detach().requires_grad_(True)
-    g_loss = _g_term(netD, netD(leaf), sent_emb)
+    seen = leaf if augment is None else ops.diffaug(None, leaf, augment[0], augment[1])
+    g_loss = _g_term(netD, netD(seen), sent_emb)
     (grad,) = torch.autograd.grad(g_loss, leaf)
     return g_loss.detach(), grad
 
 
 def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sent_emb, match_labels,
-                   cap_lens, class_ids, streams=None, damsm=None, d_terms=None):
+                   cap_lens, class_ids, streams=None, damsm=None, d_terms=None, augment=None):
     """losses.py:164-206.  Returns (errG_total, logs) where logs is a dict of device scalars
     {'g_loss0', ..., 'w_loss', 's_loss'} (format with .item() outside the step).
 
@@ -217,7 +231,10 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
     caller back-propagates with `backward_with_image_grad`.
 
     d_terms (optional, the g_loss values of generator_d_term, one per discriminator): likewise for the adversarial
-    terms; the caller back-propagates with `backward_with_image_grads`."""
+    terms; the caller back-propagates with `backward_with_image_grads`.
+
+    augment (optional, one (rows [n][8], flags) per discriminator): each discriminator sees its fake image through
+    ops.diffaug; the ranking terms see the image itself."""
     import contextlib
     numDs = len(netsD)
     batch_size = real_labels.size(0)
@@ -236,7 +253,10 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
             g_loss = d_terms[i]
         else:
             with branch(i):
-                g_loss = _g_term(netsD[i], netsD[i](fake_imgs[i]), sent_emb)
+                seen = fake_imgs[i]
+                if augment is not None:
+                    seen = ops.diffaug(None, seen, augment[i][0], augment[i][1])
+                g_loss = _g_term(netsD[i], netsD[i](seen), sent_emb)
         terms.append(g_loss)
         logs['g_loss%d' % i] = g_loss.detach()
     if damsm is not None:

@@ -164,6 +164,8 @@ SIGNATURES = {
     'sba_sqnorm_partials': [P, L, P, I, P],
     'sba_clip_adam_prepare': [P, P, I, P, F, F, F, P, P],
     'sba_adam_step_dscale': [P, P, P, P, P, P, P, L, F, F, F, P, P],
+    'sba_diffaug_fwd': [P, I, P, I, P, P, I, I, P, P],
+    'sba_diffaug_bwd': [P, I, P, P, I, I, P, P],
     'sba_set_deterministic': [I, P, L],
     'sba_set_reduce_scratch': [P, L],
     'sba_det_reset': [],
@@ -200,6 +202,8 @@ lib.sba_kid_workspace_bytes.restype = c_int64
 lib.sba_kid_workspace_bytes.argtypes = [I, I, I, I]
 lib.sba_msssim_workspace_bytes.restype = c_int64
 lib.sba_msssim_workspace_bytes.argtypes = [I, I, I, I]
+lib.sba_diffaug_workspace_bytes.restype = c_int64
+lib.sba_diffaug_workspace_bytes.argtypes = [I, I]
 
 _ERR = {-1: 'SBA_E_ARG (unsupported shape/alignment/enum)', -2: 'SBA_E_LAUNCH (HIP launch failed)',
         -3: 'SBA_E_UNSUPPORTED (graph node kind the replayer cannot re-issue)'}

@@ -2699,3 +2699,66 @@ def batch_masks(captions, class_ids, word_mask, class_mask):
         raise ValueError('batch_masks: class_mask must be contiguous uint8 [%d][%d] on %s' % (B, B, dev))
     call('sba_batch_masks', _p(captions), _p(class_ids), _p(word_mask), _p(cm), B, L, _stream())
     return word_mask, class_mask
+
+
+# ----------------------------------------------------------------------------
+# Differentiable Augmentation (csrc/diffaug.hip; sbagan/diffaug.py)
+# ----------------------------------------------------------------------------
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4
+
+
+def _diffaug_workspace(n, S, flags, device):
+    """the f64 partial sums of sba_diffaug_fwd / _bwd over n images (None with color off: no reduction runs)"""
+    if not flags & DIFFAUG_COLOR:
+        return None
+    nbytes = _lib.lib.sba_diffaug_workspace_bytes(n, S)
+    if nbytes <= 0:
+        raise ValueError('diffaug: %d images of side %d are not supported (S even, 8..4096; 1..65535 images)' % (n, S))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+class DiffAugFn(torch.autograd.Function):
+    """[real | fake] -> T([real | fake]): the step's concatenation and the augmentation in one pass (sba_diffaug_fwd).
+    The gradient goes to `fake` only (real images are data); when `fake` needs none -- the discriminator update's
+    detached images -- the backward pass launches nothing."""
+
+    @staticmethod
+    def forward(ctx, fake, real, params, flags):
+        _need_gpu(fake)
+        nf, C, S, S2 = fake.shape
+        nr = 0 if real is None else real.size(0)
+        if C != 3 or S != S2 or fake.dtype != torch.float32 or not fake.is_contiguous():
+            raise ValueError('diffaug: fake must be contiguous float32 [n][3][S][S], got %s %s'
+                             % (fake.dtype, tuple(fake.shape)))
+        if real is not None and (real.dtype != torch.float32 or not real.is_contiguous() or real.device != fake.device
+                                 or tuple(real.shape[1:]) != (3, S, S)):
+            raise ValueError('diffaug: real must be contiguous float32 [n][3][%d][%d] on %s' % (S, S, fake.device))
+        if (params.dtype != torch.float32 or tuple(params.shape) != (nr + nf, 8) or not params.is_contiguous()
+                or params.device != fake.device):
+            raise ValueError('diffaug: params must be contiguous float32 [%d][8] on %s' % (nr + nf, fake.device))
+        flags = int(flags)
+        # both workspaces here, outside any later graph capture of the backward
+        ws = _diffaug_workspace(nr + nf, S, flags, fake.device)
+        ctx.ws_bwd = _diffaug_workspace(nf, S, flags, fake.device) if ctx.needs_input_grad[0] else None
+        out = torch.empty((nr + nf, 3, S, S), dtype=torch.float32, device=fake.device)
+        call('sba_diffaug_fwd', _p(real), nr, _p(fake), nf, _p(params), _p(out), S, flags, _p(ws), _stream())
+        ctx.save_for_backward(params)
+        ctx.geom = (nr, nf, S, flags)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        (params,) = ctx.saved_tensors
+        nr, nf, S, flags = ctx.geom
+        dout = dout.float().contiguous()[nr:]            # (a contiguous batch: its tail is contiguous and 16-byte aligned)
+        dx = torch.empty((nf, 3, S, S), dtype=torch.float32, device=dout.device)
+        call('sba_diffaug_bwd', _p(dout), nf, _p(params[nr:]), _p(dx), S, flags, _p(ctx.ws_bwd), _stream())
+        return dx, None, None, None
+
+
+def diffaug(real, fake, params, flags):
+    """The augmented [real | fake] batch of one discriminator pass (real = None: the fake images alone).  params: f32
+    [(nr + nf)][8] uniforms in [0, 1), one row per image (sbagan.diffaug.DiffAugment); flags: DIFFAUG_* bits."""
+    return DiffAugFn.apply(fake.float().contiguous(), None if real is None else real.float().contiguous(), params, flags)

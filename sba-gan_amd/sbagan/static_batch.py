@@ -214,6 +214,8 @@ class SlotStep(object):
             ops.weights_changed()
             self.noise.normal_(0, 1)
             self.eps.normal_(0, 1)
+            if self.gan.augment is not None:
+                self.gan.augment.draw()
             self.prologue()
             return self.gan.step(*self.args, eps=self.eps)
         out = self.recording.prioritize() if n == 1 else None

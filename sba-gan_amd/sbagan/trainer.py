@@ -224,6 +224,7 @@ class GANStep(object):
     the last fake image to (region features B x nef x 17 x 17, global code B x nef)."""
 
     def __init__(self, netG, netsD, image_encoder, batch_size, lr_g=None, lr_d=None, distributed=False):
+        self._check_augment(distributed)
         self.netG, self.netsD, self.image_encoder = netG, netsD, image_encoder
         dev = next(netG.parameters()).device
         self.device = dev
@@ -248,6 +249,13 @@ class GANStep(object):
         self._g_pending = None
         self._d_buckets = {}
 
+    def _check_augment(self, distributed):
+        """the real_features two-pass layout (data-parallel, force_overlap_layout) has no augmented form"""
+        if self.augment is not None and distributed:
+            raise ValueError('GANStep: augmentation (--diffaug) is single-GPU only: not with distributed=True')
+        if self.augment is not None and self.force_overlap_layout:
+            raise ValueError('GANStep: augmentation (--diffaug) does not go with force_overlap_layout')
+
     def _allreduce_start(self, flat):
         return self.exchange.start(flat.grad)
 
@@ -261,6 +269,9 @@ class GANStep(object):
     # (2) discriminators: D_NET128 / D_NET256 exchange their gradients in two buckets.  The backward pass reaches the
     #     tail of the network first (D_NET256: img_code_s64 .. heads = 242 of 287 MB): its all-reduce starts there and
     #     runs under the rest of the backward pass (the large-map layers, most of the time) instead of behind it.
+    augment = None      # sbagan.diffaug.DiffAugment, set by the trainer (--diffaug) BEFORE construction: every image a
+    #                     discriminator sees goes through ops.diffaug.  step() never draws: the uniforms are an input like
+    #                     `noise`, drawn by whoever draws the noise (augment.draw())
     bucket_d = True
     overlap_g = True
     force_overlap_layout = False    # tests: a SINGLE-process step with the data-parallel launch decomposition (real-image
@@ -400,8 +411,9 @@ class GANStep(object):
             self._bucket_off[i] is not None and not ops.SIDE_WGRAD
         if rf is None:
             netD.clear_cuts(record=split)
+        self._check_augment(self.distributed)        # (both can be set after construction)
         errD = discriminator_loss(netD, imgs[i], fake_imgs[i], sent_emb, self.real_labels, self.fake_labels,
-                                  real_features=rf)
+                                  real_features=rf, augment=None if self.augment is None else self.augment.d_arg(i))
         self._out['errD%d' % i] = errD.detach()
         cuts = list(netD._cuts)
         netD.clear_cuts(record=False)
@@ -476,7 +488,8 @@ class GANStep(object):
             p.requires_grad_(False)         # (phase_b_bwd restores them after the generator's backward pass; if that never
         self._d_frozen[i] = True            #  runs -- an exception, a caller driving the phases by hand -- the next
         #                                      phase_d_bwd_tail of this discriminator does)
-        value, grad = generator_d_term(netD, self._ctx[0][i], sent_emb)
+        value, grad = generator_d_term(netD, self._ctx[0][i], sent_emb,
+                                       augment=None if self.augment is None else self.augment.g_arg(i))
         self._g_terms[i] = (value, grad)
 
     def phase_b_bwd(self, sent_emb, words_embs, cap_lens, class_ids):
@@ -511,7 +524,9 @@ class GANStep(object):
         errG_total, logs = generator_loss(self.netsD, self.image_encoder, fake_imgs, self.real_labels, words_embs,
                                           sent_emb, self.match_labels, cap_lens, class_ids,
                                           streams=self._d_streams() if self.concurrent_d else None, damsm=damsm,
-                                          d_terms=None if d_terms is None else [t[0] for t in d_terms])
+                                          d_terms=None if d_terms is None else [t[0] for t in d_terms],
+                                          augment=None if self.augment is None or d_terms is not None else
+                                          [self.augment.g_arg(i) for i in range(len(self.netsD))])
         kl = KL_loss(mu, logvar)
         errG_total = errG_total + kl
         mark('g_loss_forward')
@@ -1012,6 +1027,8 @@ class ReplayedStep(object):
         with torch.cuda.stream(cap):
             noise.normal_(0, 1)
             eps.normal_(0, 1)
+            if gan.augment is not None:
+                gan.augment.draw()
             if recorded_prologue is not None:
                 recorded_prologue()
             out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise, eps=eps)
@@ -1083,6 +1100,8 @@ class ReplayedStep(object):
         if self.draw:
             self.noise.normal_(0, 1)
             self.eps.normal_(0, 1)
+            if self.gan.augment is not None:
+                self.gan.augment.draw()
         if self.prologue is not None:
             self.prologue()
 

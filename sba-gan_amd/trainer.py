@@ -128,6 +128,11 @@ class condGANTrainer(object):
             from sbagan.inception_hip import InceptionHIP
             enc = InceptionHIP(enc)
         self.gan = GANStep(netG, netsD, enc, self.batch_size)
+        if self.diffaug and cfg.TRAIN.FLAG:
+            # --diffaug: every image a discriminator sees goes through the augmentation; its uniforms are
+            # drawn beside the noise, by the loops below and by the recorded step's own draws
+            from sbagan.diffaug import DiffAugment
+            self.gan.augment = DiffAugment(self.diffaug, self.batch_size, len(netsD), self.gan.device)
         return self.gan.optG, self.gan.optD
 
     def prepare_labels(self):
@@ -208,6 +213,7 @@ class condGANTrainer(object):
 
     replay = False              # --replay: train() runs every batch through ONE recording of the step
     replay_eager = False        # with replay: the same loop over the static batch slot, the step launched eagerly
+    diffaug = ''                # --diffaug POLICY: Differentiable Augmentation in front of the discriminators ('' = off)
     average_interval = 1000     # iterations between the 'average' (EMA generator) image dumps
 
     def _replay_step(self, text_encoder, noise):
@@ -264,6 +270,8 @@ class condGANTrainer(object):
                     words_embs, sent_emb = self._encode(text_encoder, captions, cap_lens)
                     mask = build_mask(captions, words_embs.size(2))
                     noise.normal_(0, 1)
+                    if gan.augment is not None:
+                        gan.augment.draw()
                     out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise)
                 step += 1
                 gen_iterations += 1
