@@ -3,18 +3,7 @@
     python main.py --cfg cfg/bird_style.yml --gpu 0 --data_dir ../data/birds [--manualSeed N]
 
 cfg.TRAIN.FLAG: train; otherwise cfg.B_VALIDATION ? sampling(split) : gen_example(example_filenames.txt).
---fused_inference, --r_precision R (sampling also writes r_precision.json), --attention_maps (the attention-map
-overlay images, sbagan/visualize.py), --fid [--fid_stats PATH] (sampling also writes fid.json, sbagan/fid.py) and --prdc K
-(sampling also writes prdc.json: precision, recall, density and coverage, sbagan/prdc.py), --kid [--kid_subsets N]
-[--kid_subset_size M] (sampling also writes kid.json: the Kernel Inception Distance, sbagan/kid.py), --ms_ssim N
-(sampling also writes ms_ssim.json: the mean MS-SSIM over N same-class image pairs per class, sbagan/msssim.py), --swd N
-(sampling also writes swd.json: the sliced Wasserstein distance per resolution between the first N real and the first N
-generated images, sbagan/swd.py), --nearest K [--nearest_stats PATH] [--nearest_show M] (sampling also writes nearest.json
-and nearest.png: every generated image's K nearest training images and the memorisation figures, sbagan/nearest.py) and
---device_data
-[--device_data_gb G] (training: the split is decoded once into a device-resident cache and every batch is cropped, flipped,
-resized to every scale and normalised there, sbagan/device_data.py) and --replay (training: every batch through one
-recording of the step, read from a static batch slot, sbagan/static_batch.py) are this project's additions."""
+The flags beyond the reference's are this project's additions: miscc/cli.py lists and describes them."""
 import os
 import sys
 import time
@@ -29,6 +18,7 @@ if _HERE not in sys.path:
 from datasets import TextDataset, tokenize  # noqa: E402
 from miscc import cli, transforms  # noqa: E402
 from miscc.config import cfg  # noqa: E402
+from sbagan import evaluation  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -93,19 +83,10 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
         from trainer import condGANTrainer as make_trainer
     algo = make_trainer(output_dir, dataloader, dataset.n_words, dataset.ixtoword)
     algo.fused_inference = bool(getattr(args, 'fused_inference', False))
-    algo.r_precision = int(getattr(args, 'r_precision', 0))
     algo.attention_maps = bool(getattr(args, 'attention_maps', False))
-    algo.fid = bool(getattr(args, 'fid', False))
-    algo.fid_stats = getattr(args, 'fid_stats', None)
-    algo.prdc = int(getattr(args, 'prdc', 0))
-    algo.kid = bool(getattr(args, 'kid', False))
-    algo.kid_subsets = int(getattr(args, 'kid_subsets', 100))
-    algo.kid_subset_size = int(getattr(args, 'kid_subset_size', 1000))
-    algo.ms_ssim = int(getattr(args, 'ms_ssim', 0))
-    algo.swd = int(getattr(args, 'swd', 0))
-    algo.nearest = int(getattr(args, 'nearest', 0))
-    algo.nearest_stats = getattr(args, 'nearest_stats', None)
-    algo.nearest_show = int(getattr(args, 'nearest_show', 16))
+    for opt in evaluation.OPTIONS:      # the sampling evaluations: one attribute per flag of the table
+        if opt.help is not None:
+            setattr(algo, opt.name, getattr(args, opt.name, opt.default))
     algo.replay = bool(getattr(args, 'replay', False)) and training
     if getattr(args, 'replay', False) and not training:
         print('--replay is ignored outside training')

@@ -19,65 +19,32 @@ import re
 import numpy as np
 import torch
 
+from sbagan import evaluation
+
 from .config import cfg, cfg_from_file
 
 EVAL_SEED = 100
 
 
-def _r_precision(text):
-    r = int(text)
-    if r < 0 or r == 1:
-        raise argparse.ArgumentTypeError('R must be 0 (off) or at least 2 candidates per image')
-    return r
+def _ranged_int(metavar, lo, hi, what, also=None):
+    """the argparse type of an integer in [lo, hi] (hi None: unbounded) or equal to `also`"""
+    def parse(text):
+        v = int(text)
+        if v != also and (v < lo or (hi is not None and v > hi)):
+            raise argparse.ArgumentTypeError('%s must be %s' % (metavar, what))
+        return v
+    return parse
 
 
-def _prdc(text):
-    k = int(text)
-    if k < 0 or k > 8:
-        raise argparse.ArgumentTypeError('K must be 0 (off) or a neighbour count from 1 to 8')
-    return k
-
-
-def _kid_subsets(text):
-    n = int(text)
-    if n < 1 or n > 1024:
-        raise argparse.ArgumentTypeError('N must be a subset count from 1 to 1024')
-    return n
-
-
-def _kid_subset_size(text):
-    m = int(text)
-    if m < 2:
-        raise argparse.ArgumentTypeError('M must be at least 2 rows a side')
-    return m
-
-
-def _ms_ssim(text):
-    n = int(text)
-    if n < 0:
-        raise argparse.ArgumentTypeError('N must be 0 (off) or a number of pairs per class')
-    return n
-
-
-def _swd(text):
-    n = int(text)
-    if n < 0:
-        raise argparse.ArgumentTypeError('N must be 0 (off) or a number of images per side')
-    return n
-
-
-def _nearest(text):
-    k = int(text)
-    if k < 0 or k > 8:
-        raise argparse.ArgumentTypeError('K must be 0 (off) or a neighbour count from 1 to 8')
-    return k
-
-
-def _nearest_show(text):
-    m = int(text)
-    if m < 0:
-        raise argparse.ArgumentTypeError('M must be 0 (no picture) or a number of generated images')
-    return m
+def _add_evaluator(ap, record):
+    """the flags of one record of sbagan.evaluation's table: a switch, a path or a ranged integer each"""
+    for opt in record.options:
+        if opt.help is None:        # (an attribute of the trainer alone)
+            continue
+        kind = dict(action='store_true') if opt.metavar is None else dict(type=str, metavar=opt.metavar)
+        if opt.lo is not None:
+            kind['type'] = _ranged_int(opt.metavar, opt.lo, opt.hi, opt.cli_what or opt.what, also=opt.default)
+        ap.add_argument('--' + opt.name, dest=opt.name, default=opt.default, help=opt.help, **kind)
 
 
 DIFFAUG_POLICIES = ('color', 'translation', 'cutout')
@@ -92,13 +59,6 @@ def _diffaug(text):
     return ','.join(names)
 
 
-def _retrieval(text):
-    e = int(text)
-    if e < 0:
-        raise argparse.ArgumentTypeError('E must be 0 (off) or an interval in epochs')
-    return e
-
-
 def options(what, default_cfg, argv=None, bert=False):
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
@@ -108,62 +68,13 @@ def options(what, default_cfg, argv=None, bert=False):
     ap.add_argument('--fused_inference', dest='fused_inference', action='store_true', default=False,
                     help='sampling / gen_example: run the generator through sbagan.infer.FusedGenerator (BatchNorm '
                          'folded into the convs, GLU in the conv epilogue)')
-    ap.add_argument('--r_precision', dest='r_precision', type=_r_precision, default=0, metavar='R',
-                    help='sampling: also rank every generated image among R candidate captions (its own and R - 1 of '
-                         'other classes) with the DAMSM encoders and write r_precision.json; 0 = off, 100 = the '
-                         'AttnGAN paper\'s setting')
+    _add_evaluator(ap, evaluation.EVALUATORS[0])
     ap.add_argument('--attention_maps', dest='attention_maps', action='store_true', default=False,
                     help='write the attention-map overlays (sbagan.visualize): Image/G_*.png and D_*.png in training, '
                          '<key>/0_s_<i>_a<k>.png from gen_example, Image/attention_maps<step>.png in DAMSM '
                          'pre-training')
-    ap.add_argument('--fid', dest='fid', action='store_true', default=False,
-                    help='sampling: also take the Frechet Inception Distance between the real images of the split and '
-                         'the generated ones on the DAMSM image encoder\'s Inception-v3 trunk (sbagan.fid) and write '
-                         'fid.json')
-    ap.add_argument('--fid_stats', dest='fid_stats', type=str, default=None, metavar='PATH',
-                    help='with --fid: an .npz of the real images\' statistics; read instead of the real pass when it '
-                         'exists, written after the run when it does not')
-    ap.add_argument('--prdc', dest='prdc', type=_prdc, default=0, metavar='K',
-                    help='sampling: also take precision, recall, density and coverage (the K-nearest-neighbour manifold '
-                         'metrics, sbagan.prdc) between the real images of the split and the generated ones on the same '
-                         'trunk features as --fid and write prdc.json; 0 = off, K from 1 to 8, 5 = the usual setting.  '
-                         'On this project\'s own trunk and compute dtype: not comparable with published numbers')
-    ap.add_argument('--kid', dest='kid', action='store_true', default=False,
-                    help='sampling: also take the Kernel Inception Distance (the unbiased MMD^2 estimate under the '
-                         'kernel (x.y / D + 1)^3 with its standard deviation over subsets, sbagan.kid) between the real '
-                         'images of the split and the generated ones on the same trunk features as --fid and write '
-                         'kid.json.  On this project\'s own trunk and compute dtype: not comparable with published '
-                         'numbers')
-    ap.add_argument('--kid_subsets', dest='kid_subsets', type=_kid_subsets, default=100, metavar='N',
-                    help='with --kid: the number of subsets, 1 to 1024')
-    ap.add_argument('--kid_subset_size', dest='kid_subset_size', type=_kid_subset_size, default=1000, metavar='M',
-                    help='with --kid: rows per subset and side (at least 2); clamped to the smaller side')
-    ap.add_argument('--ms_ssim', dest='ms_ssim', type=_ms_ssim, default=0, metavar='N',
-                    help='sampling: also take the mean multi-scale structural similarity (MS-SSIM, the within-class '
-                         'diversity measure of the AC-GAN paper, sbagan.msssim) over N random pairs of images per class, '
-                         'for the generated images and for the real images of the same pairs, and write ms_ssim.json; '
-                         '0 = off, 100 = the AC-GAN setting.  In pixel space on the written uint8 images: it uses no '
-                         'trunk; images of at least 176 px')
-    ap.add_argument('--swd', dest='swd', type=_swd, default=0, metavar='N',
-                    help='sampling: also take the sliced Wasserstein distance (SWD, Karras et al. 2018, sbagan.swd) between '
-                         'the first N real and the first N generated images, per level of a Laplacian pyramid and on '
-                         'average, x 1e3, and write swd.json; 0 = off, 16384 = the setting of the paper.  In pixel '
-                         'space on the written uint8 images: it uses no trunk; square images of 32, 64, 128 or 256 px')
-    ap.add_argument('--nearest', dest='nearest', type=_nearest, default=0, metavar='K',
-                    help='sampling: also list the K nearest TRAINING images of every generated image on the same trunk '
-                         'features as --fid (float64 distances on the matrix cores, sbagan.nearest) and take the '
-                         'memorisation figures the other evaluations cannot see: authenticity (Alaa et al. 2022) with its '
-                         'baseline on the split\'s real images, the nearest-training-image distance of generated against '
-                         'unseen real images, the share of near-copies and how many distinct training images are hit; '
-                         'writes nearest.json and nearest.png; 0 = off, K from 1 to 8.  The training split is encoded '
-                         'once after the generation loop.  On this project\'s own trunk and compute dtype: not '
-                         'comparable with published numbers.  Ignored by the DAMSM entry points and in training')
-    ap.add_argument('--nearest_stats', dest='nearest_stats', type=str, default=None, metavar='PATH',
-                    help='with --nearest: an .npz of the training images\' feature rows and keys; read instead of the '
-                         'training pass when it exists, written after the run when it does not')
-    ap.add_argument('--nearest_show', dest='nearest_show', type=_nearest_show, default=16, metavar='M',
-                    help='with --nearest: the M generated images closest to a training image are listed in nearest.json '
-                         'and shown in nearest.png, one row each beside their K training images; 0 = no picture')
+    for record in evaluation.EVALUATORS[1:]:
+        _add_evaluator(ap, record)
     ap.add_argument('--device_data', dest='device_data', action='store_true', default=False,
                     help='training: decode the split once into a device-resident uint8 cache and make every batch '
                          'there -- crop, flip, every scale of the pyramid and the normalisation in one HIP launch '
@@ -188,7 +99,8 @@ def options(what, default_cfg, argv=None, bert=False):
                          'POLICY: a comma-separated subset of color,translation,cutout; empty = off.  The DAMSM terms, '
                          'sampling, the image dumps and checkpoints see un-augmented images.  Single GPU only.  Ignored '
                          'outside training and by the DAMSM pre-training entry points')
-    ap.add_argument('--retrieval', dest='retrieval', type=_retrieval, default=0, metavar='E',
+    ap.add_argument('--retrieval', dest='retrieval', default=0, metavar='E',
+                    type=_ranged_int('E', 0, None, '0 (off) or an interval in epochs'),
                     help='DAMSM pre-training: after the validation pass of every E-th epoch and of the last one, rank '
                          'every image of the validation split against every caption and every caption against every '
                          'image with the two encoders (sbagan.retrieval: float64 cosine scores on the matrix cores, the '

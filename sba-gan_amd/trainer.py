@@ -17,7 +17,6 @@ What differs, none of it in results:
     error and fails; pass `allow_random_encoders=True` to train against randomly initialised frozen encoders
     (synthetic-data runs and tests).
 """
-import json
 import os
 import time
 
@@ -29,12 +28,8 @@ from datasets import as_batch, prepare_data
 from miscc.config import cfg
 from miscc.utils import copy_G_params, load_params, mkdir_p, weights_init
 from model import CNN_ENCODER, D_NET64, D_NET128, D_NET256, G_NET, RNN_ENCODER
+from sbagan import evaluation
 from sbagan.trainer import GANStep, build_mask, prepare_labels
-
-
-def _figure(value):
-    """a figure that may be missing (sbagan.nearest reports None where no row has a neighbour)"""
-    return 'n/a' if value is None else '%.6g' % value
 
 
 def _to_uint8(img):
@@ -388,10 +383,6 @@ class condGANTrainer(object):
                                                  att.size(2))
                 Image.fromarray(img_set).save(os.path.join(out_dir, '0_s_%d_a%d%s.png' % (int(src), k, suffix)))
 
-    r_precision = 0             # --r_precision R: sampling() also ranks every image among R candidate captions
-    r_precision_seed = 100      # seed of the evaluator's own index generator and of the pool's caption draws
-    r_precision_result = None   # the result dict of the last sampling() with r_precision != 0
-
     def _load_image_encoder(self):
         """the DAMSM image encoder beside cfg.TRAIN.NET_E (as build_models finds it), frozen, in eval mode, behind its
         HIP forward (as define_optimizers wraps it).  Built with the CPU generator forked: its initialisation must not
@@ -409,167 +400,18 @@ class condGANTrainer(object):
             p.requires_grad = False
         return InceptionHIP(image_encoder.to(self.device).eval())
 
-    def _r_precision_evaluator(self, text_encoder):
-        """sbagan.rprecision.RPrecision over the sentence embeddings of every caption of the sampled split"""
-        from sbagan.rprecision import RPrecision, encode_pool
-        if self.r_precision < 2:
-            raise ValueError('r_precision must be 0 (off) or >= 2 candidates per image (got %d)' % self.r_precision)
-        pool, pool_class = encode_pool(self.data_loader.dataset, lambda c, n: self._encode(text_encoder, c, n),
-                                       self.batch_size, seed=self.r_precision_seed, device=self.device)
-        return RPrecision(self._load_image_encoder(), pool, pool_class, R=self.r_precision, seed=self.r_precision_seed)
-
-    fid = False                 # --fid: sampling() also takes the FID between the split's real images and the fakes
-    fid_stats = None            # --fid_stats PATH: the real side's statistics, read when present, written when not
-    fid_result = None           # the result dict of the last sampling() with fid on
-
-    def _fid_evaluator(self, image_encoder, split_dir):
-        """sbagan.fid.FID on the pooled trunk feature of `image_encoder` (an InceptionHIP); the real side comes from
-        fid_stats when that file exists"""
-        from miscc import cli
-        from sbagan.feature_rows import dtype_name
-        from sbagan.fid import FID, stats_key
-        dtype = dtype_name()
-        key = stats_key(cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder'), dtype, split_dir, cli.image_size())
-        evaluator = FID(image_encoder.pooled_features, D=2048, key=key, dtype=dtype)
-        if self.fid_stats and os.path.exists(self.fid_stats):
-            evaluator.load_real(self.fid_stats)
-            print('Load real FID statistics from:', self.fid_stats)
-        return evaluator
-
-    prdc = 0                    # --prdc K: sampling() also takes precision / recall / density / coverage at k = K
-    prdc_result = None          # the result dict of the last sampling() with prdc != 0
-
-    def _prdc_evaluator(self, image_encoder):
-        """sbagan.prdc.PRDC on the pooled trunk feature of `image_encoder` (an InceptionHIP)"""
-        from sbagan import ops
-        from sbagan.feature_rows import dtype_name
-        from sbagan.prdc import PRDC
-        if isinstance(self.prdc, bool) or not isinstance(self.prdc, int) or not 1 <= self.prdc <= ops.PRDC_MAX_K:
-            raise ValueError('prdc must be 0 (off) or a neighbour count from 1 to %d (got %r)'
-                             % (ops.PRDC_MAX_K, self.prdc))
-        return PRDC(image_encoder.pooled_features, D=2048, k=self.prdc, dtype=dtype_name())
-
-    kid = False                 # --kid: sampling() also takes the Kernel Inception Distance
-    kid_subsets = 100           # --kid_subsets N
-    kid_subset_size = 1000      # --kid_subset_size M: rows per subset and side, clamped to the smaller side
-    kid_seed = 100              # of the evaluator's own generator for the subset draws
-    kid_result = None           # the result dict of the last sampling() with kid on
-    kid_evaluator = None
-
-    def _kid_evaluator(self, image_encoder, prdc):
-        """sbagan.kid.KID on the pooled trunk feature of `image_encoder` (an InceptionHIP); with a PRDC evaluator it
-        reads that one's rows and stores none"""
-        from sbagan.feature_rows import dtype_name
-        from sbagan.kid import KID
-        return KID(image_encoder.pooled_features, D=2048, subsets=self.kid_subsets, subset_size=self.kid_subset_size,
-                   seed=self.kid_seed, dtype=dtype_name(), rows=prdc)
-
-    ms_ssim = 0                 # --ms_ssim N: sampling() also takes the mean MS-SSIM over N same-class pairs per class
-    ms_ssim_seed = 100          # of the evaluator's own generator for the pair draws
-    ms_ssim_result = None       # the result dict of the last sampling() with ms_ssim != 0
-    ms_ssim_evaluator = None
-
-    def _ms_ssim_evaluator(self):
-        """sbagan.msssim.MSSSIM on the uint8 pixels of the last stage's images; refuses a configuration whose images
-        are too small for five scales"""
-        from miscc import cli
-        from sbagan.msssim import MSSSIM
-        if isinstance(self.ms_ssim, bool) or not isinstance(self.ms_ssim, int) or self.ms_ssim < 1:
-            raise ValueError('ms_ssim must be 0 (off) or a number of pairs per class (got %r)' % (self.ms_ssim,))
-        return MSSSIM(self.ms_ssim, size=cli.image_size(), seed=self.ms_ssim_seed)
-
-    swd = 0                     # --swd N: sampling() also takes the sliced Wasserstein distance per resolution between the
-    #                             first N real and the first N generated images (0 = off)
-    swd_seed = 100              # of the evaluator's own generator for the patch positions and the directions
-    swd_result = None           # the result dict of the last sampling() with swd != 0
-    swd_evaluator = None
-
-    def _swd_evaluator(self, ms_ssim=None):
-        """sbagan.swd.SWD on the uint8 pixels of the last stage's images; refuses an image size it has no pyramid for.
-        ms_ssim: the MS-SSIM evaluator of the same run, whose stored images it then reads instead of keeping its own"""
-        from miscc import cli
-        from sbagan.swd import SWD
-        if isinstance(self.swd, bool) or not isinstance(self.swd, int) or self.swd < 1:
-            raise ValueError('swd must be 0 (off) or a number of images per side (got %r)' % (self.swd,))
-        return SWD(self.swd, size=cli.image_size(), seed=self.swd_seed, images=ms_ssim)
-
-    nearest = 0                 # --nearest K: sampling() also lists every generated image's K nearest TRAINING images and takes
-    #                             the memorisation figures of sbagan.nearest (0 = off)
-    nearest_stats = None        # --nearest_stats PATH: the training rows and keys, read when present, written when not
-    nearest_show = 16           # --nearest_show M: suspects in nearest.json and rows of nearest.png (0: no picture)
-    nearest_result = None       # the result dict of the last sampling() with nearest != 0
-    nearest_evaluator = None
-
-    def _nearest_evaluator(self, image_encoder):
-        """sbagan.nearest.Nearest on the pooled trunk feature of `image_encoder` (an InceptionHIP); the training side
-        comes from nearest_stats when that file exists"""
-        from miscc import cli
-        from sbagan import ops
-        from sbagan.feature_rows import dtype_name
-        from sbagan.nearest import Nearest, stats_key
-        if isinstance(self.nearest, bool) or not isinstance(self.nearest, int) or not 1 <= self.nearest <= ops.KNN_MAX_K:
-            raise ValueError('nearest must be 0 (off) or a neighbour count from 1 to %d (got %r)'
-                             % (ops.KNN_MAX_K, self.nearest))
-        dtype = dtype_name()
-        key = stats_key(cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder'), dtype, 'train', cli.image_size())
-        evaluator = Nearest(image_encoder.pooled_features, D=2048, k=self.nearest, show=int(self.nearest_show), key=key,
-                            dtype=dtype)
-        if self.nearest_stats and os.path.exists(self.nearest_stats):
-            evaluator.load_train(self.nearest_stats, self.device)
-            print('Load training rows from:', self.nearest_stats)
-        return evaluator
-
-    def _train_crops(self):
-        """the training split as the nearest-neighbour pass reads it: the data set class of the sampled split on 'train',
-        every image through retrieval._CenterCrops at the size the sampling loader yields for its last scale"""
-        from miscc import cli
-        from sbagan.retrieval import _CenterCrops
-        sampled = self.data_loader.dataset
-        extra = {'bert_dir': sampled.bert_dir} if hasattr(sampled, 'bert_dir') else {}
-        train = type(sampled)(sampled.data_dir, 'train', base_size=cfg.TREE.BASE_SIZE, transform=None, **extra)
-        imsize = cli.image_size()
-        return _CenterCrops(train, imsize, int(imsize * 76 / 64))
-
-    def _nearest_finish(self, nearest, res, out_dir, crops):
-        """after the result: the cache of the training rows, and nearest.png (sbagan.nearest.write_sheet)"""
-        from sbagan.nearest import write_sheet
-        if self.nearest_stats and not nearest.is_loaded():
-            nearest.save_train(self.nearest_stats)
-            print('Save training rows to:', self.nearest_stats)
-        if nearest.show:
-            crops = crops if crops is not None else self._train_crops()
-            if [str(k) for k in crops.dataset.filenames] != nearest.keys['train']:
-                raise RuntimeError('nearest: the cached training keys are not those of the training split')
-            write_sheet(os.path.join(out_dir, 'nearest.png'), res['suspects'], nearest.k,
-                        lambda key: os.path.join(out_dir, 'single', key) + '_s-1.png', crops.window)
-
     def sampling(self, split_dir):
-        """trainer.py:363-433: one image (the last stage's) per caption of the split."""
+        """trainer.py:363-433: one image (the last stage's) per caption of the split; beside them what the evaluators
+        that are on report (sbagan.evaluation: its table names their attributes here, set below the class)."""
         root = self._output_root()
         if root is None:
             return None
-        ms_ssim = self._ms_ssim_evaluator() if self.ms_ssim else None   # (refused before anything is written)
-        swd = self._swd_evaluator(ms_ssim) if self.swd else None        # (likewise)
+        suite = evaluation.Suite({opt.name: getattr(self, opt.name) for opt in evaluation.OPTIONS}, split_dir,
+                                 self._encode, self._load_image_encoder, self.data_loader, self.batch_size, self.device)
         out_dir = os.path.join(root, 'valid' if split_dir == 'test' else split_dir)
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
-        evaluator = self._r_precision_evaluator(text_encoder) if self.r_precision else None
-        fid = fid_real = prdc = kid = nearest = None
-        if self.fid or self.prdc or self.kid or self.nearest:       # one image encoder serves the five evaluators
-            image_encoder = evaluator.image_encoder if evaluator is not None else self._load_image_encoder()
-        if self.fid:
-            fid = self._fid_evaluator(image_encoder, split_dir)
-            fid_real = not fid.is_loaded('real')
-        if self.prdc:
-            prdc = self._prdc_evaluator(image_encoder)
-        if self.kid:
-            kid = self._kid_evaluator(image_encoder, prdc)
-        if self.nearest:
-            nearest = self._nearest_evaluator(image_encoder)
-        # who takes the fake rows and who the real ones: FID its moments, PRDC the rows, KID the rows unless PRDC has them
-        keeps = [ev for ev in (prdc, kid if prdc is None else None) if ev is not None]
-        takes_fake = ([fid] if fid is not None else []) + keeps
-        takes_real = ([fid] if fid_real else []) + keeps
+        suite.attach(text_encoder)
         noise = torch.empty(self._noise_shape(self.batch_size), device=self.device)
         made = set()
         for nbatch, data in enumerate(self.data_loader):
@@ -578,77 +420,12 @@ class condGANTrainer(object):
             real_imgs, captions, cap_lens, class_ids, keys = prepare_data(data)
             fake_imgs, sent_emb = self._generate(netG, text_encoder, captions, cap_lens, noise, with_sent=True)
             last = fake_imgs[-1]
-            if evaluator is not None:
-                evaluator.update(last, sent_emb, class_ids)
-            if takes_fake or nearest is not None:       # each batch goes through the trunk once, for all of them
-                if evaluator is None:           # (R-precision has otherwise just run this batch through it)
-                    image_encoder.pooled_features(last)
-                for ev in takes_fake:
-                    ev.update_features('fake', image_encoder.last_pooled)
-                if nearest is not None:         # (its rows go with their keys)
-                    nearest.update_features('fake', image_encoder.last_pooled, keys)
-                if takes_real or nearest is not None:   # with cached FID statistics: encoded for the others alone
-                    real_feats = image_encoder.pooled_features(real_imgs[-1])
-                    for ev in takes_real:
-                        ev.update_features('real', real_feats)
-                    if nearest is not None:
-                        nearest.update_features('real', real_feats)
-            if ms_ssim is not None:             # the pixels themselves: no trunk
-                ms_ssim.update('fake', last, class_ids)
-                ms_ssim.update('real', real_imgs[-1], class_ids)
-            if swd is not None:                 # (stores nothing of its own beside an MS-SSIM evaluator)
-                swd.update('fake', last)
-                swd.update('real', real_imgs[-1])
+            suite.update(last, real_imgs[-1], sent_emb, class_ids, keys)
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
-        train_crops = None
-        if nearest is not None and not nearest.is_loaded():     # the training split, once, after the generation loop
-            from sbagan.nearest import encode_train
-            train_crops = self._train_crops()
-            rows, train_keys = encode_train(train_crops.dataset, image_encoder.pooled_features, self.batch_size,
-                                            train_crops.crop, train_crops.resize, self.device,
-                                            getattr(self.data_loader, 'num_workers', 0))
-            nearest.update_features('train', rows, train_keys)
-        # (attribute stem and file name, evaluator, the printed line, the result fields it shows: a name, or a function
-        # of the result)
-        reports = (
-            ('r_precision', evaluator,
-             'R-precision (R = %d, %d images): R@1 %.4f  R@5 %.4f  R@10 %.4f  R@1 over %d splits %.4f +- %.4f',
-             ('R', 'n', 'r_at_1', 'r_at_5', 'r_at_10', 'splits', 'r_at_1_splits_mean', 'r_at_1_splits_std')),
-            ('fid', fid, 'FID (%d real, %d generated images, %s trunk): %.6g  (mean term %.6g, tr real %.6g, tr fake %.6g)',
-             ('n_real', 'n_fake', 'dtype', 'fid', 'mean_term', 'trace_real', 'trace_fake')),
-            ('prdc', prdc, 'PRDC (k = %d, %d real, %d generated images, %s trunk): precision %.4f  recall %.4f  '
-             'density %.4f  coverage %.4f',
-             ('k', 'n_real', 'n_fake', 'dtype', 'precision', 'recall', 'density', 'coverage')),
-            ('kid', kid, 'KID (%d subsets of %d, %d real, %d generated images, %s trunk): %.6g +- %.6g',
-             ('subsets', 'subset_size', 'n_real', 'n_fake', 'dtype', 'kid', 'kid_std')),
-            ('ms_ssim', ms_ssim, 'MS-SSIM (%d same-class pairs of %d images, %d classes, %d skipped, %d px): generated '
-             '%.6g +- %.6g  real %.6g +- %.6g',
-             ('pairs', 'n_images', 'classes', 'classes_skipped', 'size', 'ms_ssim_fake', 'ms_ssim_fake_std',
-              'ms_ssim_real', 'ms_ssim_real_std')),
-            ('swd', swd, 'SWD x 1e3 (%d real and %d generated images, %d patches each, %d directions): %s  average %.6g',
-             ('n_images', 'n_images', 'patches_per_image', lambda r: r['dir_repeats'] * r['dirs_per_repeat'],
-              lambda r: '  '.join('%d px %.6g' % v for v in zip(r['resolutions'], r['swd_x1e3'])), 'swd_avg_x1e3')),
-            ('nearest', nearest, 'Nearest training images (K = %d, %d training, %d real, %d generated images, %s trunk, this '
-             'project\'s own features): authenticity %.4f (real %.4f)  median distance %s (real %s, ratio %s)  '
-             'copies %.4f  distinct training images hit %.4f  most hits on one %d',
-             ('k', 'n_train', 'n_real', 'n_fake', 'dtype', 'authenticity', 'authenticity_real',
-              lambda r: _figure(r['nn_dist_fake']['median']), lambda r: _figure(r['nn_dist_real']['median']),
-              lambda r: _figure(r['nn_ratio']), 'copy_fraction', 'train_hit_distinct', 'train_hit_max')))
-        for stem, ev, line, fields in reports:
-            if ev is None:
-                continue
-            setattr(self, stem + '_evaluator', ev)
-            res = ev.result()
-            setattr(self, stem + '_result', res)
-            print(line % tuple(f(res) if callable(f) else res[f] for f in fields))
-            with open(os.path.join(out_dir, stem + '.json'), 'w') as f:
-                json.dump(res, f, indent=1, sort_keys=True)
-            if ev is fid and self.fid_stats and fid_real:
-                fid.save_real(self.fid_stats)
-                print('Save real FID statistics to:', self.fid_stats)
-            if ev is nearest:
-                self._nearest_finish(nearest, res, out_dir, train_crops)
+        for stem, (evaluator, result) in suite.finish(out_dir).items():
+            setattr(self, stem + '_evaluator', evaluator)
+            setattr(self, stem + '_result', result)
         return out_dir
 
     def gen_example(self, data_dic):
@@ -673,3 +450,9 @@ class condGANTrainer(object):
             if self.attention_maps:
                 self._write_top_words(stages, att_maps, captions, cap_lens, order, out_dir)
         return root
+
+
+# the evaluation attributes of sampling(): every option of sbagan.evaluation's table with its default, and per evaluator
+# <stem>_evaluator / <stem>_result of the last sampling() that had it on
+for _name, _default in evaluation.ATTRIBUTES:
+    setattr(condGANTrainer, _name, _default)

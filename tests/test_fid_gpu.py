@@ -2,15 +2,15 @@
 on integer-valued features (every f64 sum is then exact), within the derived summation bounds on real-valued ones --
 determinism, the refusals, the FID class with a stub feature callable, and sampling() with --fid through both trainers."""
 import functools
-import glob
 import json
 import math
 import os
-import random
 
 import numpy as np
 import pytest
 import torch
+
+import sampling_harness as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -284,74 +284,6 @@ def test_fid_class_with_stub_features():
 
 
 # ------------------------------------------------------------------ sampling() with the flag
-def _toy_cfg():
-    from miscc.config import cfg, reset_cfg
-    reset_cfg()
-    cfg.GAN.GF_DIM, cfg.GAN.DF_DIM, cfg.TREE.BRANCH_NUM = 32, 64, 2
-    cfg.TEXT.CAPTIONS_PER_IMAGE, cfg.TEXT.WORDS_NUM, cfg.TEXT.EMBEDDING_DIM = 2, 8, 256
-    cfg.TRAIN.BATCH_SIZE = 2
-    cfg.TRAIN.NET_E, cfg.TRAIN.NET_G, cfg.TRAIN.FLAG, cfg.CUDA, cfg.GPU_ID = '', '', False, True, 0
-    return cfg
-
-
-def _seed_all(seed):
-    for seeder in (random.seed, np.random.seed, torch.manual_seed, torch.cuda.manual_seed_all):
-        seeder(seed)
-
-
-class _CountForwards(object):
-    """counts InceptionHIP.forward calls while active"""
-
-    def __enter__(self):
-        from sbagan.inception_hip import InceptionHIP
-        self.cls, self.orig, self.n = InceptionHIP, InceptionHIP.forward, 0
-        counter = self
-
-        def forward(runner, img, *args, **kwargs):
-            counter.n += 1
-            return counter.orig(runner, img, *args, **kwargs)
-        InceptionHIP.forward = forward
-        return self
-
-    def __exit__(self, *exc):
-        self.cls.forward = self.orig
-
-
-def _sample(make_trainer, loader, ds, ckpt, fid=False, fid_stats=None, R=0):
-    """sampling('test') from `ckpt` after identical seeding, in the deterministic-reduction mode: the generator's
-    attention / AdaIN kernels add partial sums with f32 atomics in the default mode, so two runs of the SAME command
-    differ in a few image bytes there; the byte comparisons below need the mode in which a run is reproducible"""
-    from sbagan import ops
-    ops.set_deterministic(True, DEV)
-    try:
-        return _sample_det(make_trainer, loader, ds, ckpt, fid, fid_stats, R)
-    finally:
-        ops.set_deterministic(False)
-
-
-def _sample_det(make_trainer, loader, ds, ckpt, fid, fid_stats, R):
-    from miscc.config import cfg
-    cfg.TRAIN.NET_G = ckpt
-    algo = make_trainer(os.path.dirname(ckpt), loader, ds.n_words, ds.ixtoword)
-    algo.fid, algo.fid_stats, algo.r_precision = fid, fid_stats, R
-    _seed_all(100)
-    with _CountForwards() as count:
-        out_dir = algo.sampling('test')
-    states = (np.random.get_state(), torch.cuda.get_rng_state(), torch.get_rng_state())
-    files = {os.path.relpath(f, out_dir): open(f, 'rb').read()
-             for f in glob.glob(os.path.join(out_dir, '**', '*'), recursive=True) if os.path.isfile(f)}
-    return algo, files, states, count.n
-
-
-def _same_states(a, b):
-    return (a[0][0] == b[0][0] and np.array_equal(a[0][1], b[0][1]) and a[0][2:] == b[0][2:]
-            and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]))
-
-
-def _images(files):
-    return {k: v for k, v in files.items() if k.endswith('.png')}
-
-
 def _check_result(algo, files, n_images):
     res = json.loads(files['fid.json'].decode())
     print('fid.json:', res)
@@ -364,62 +296,32 @@ def _check_result(algo, files, n_images):
     return res
 
 
-def _rnn_setup(tmp_path, names):
-    from test_host_cpu import _make_dataset
-    _toy_cfg()
-    import datasets
-    import model
-    from miscc import transforms
-    from miscc.utils import weights_init
-    from sbagan import ops
-    from trainer import condGANTrainer
-    ops.set_compute_dtype(torch.bfloat16)
-    root = str(tmp_path / 'toy')
-    _make_dataset(root, n_test=6)
-    tf = transforms.Compose([transforms.Resize(int(128 * 76 / 64)), transforms.RandomCrop(128),
-                             transforms.RandomHorizontalFlip()])
-    ds = datasets.TextDataset(root, 'test', base_size=64, transform=tf)
-    loader = torch.utils.data.DataLoader(ds, batch_size=2, drop_last=True, shuffle=True)
-    torch.manual_seed(1)
-    netG = model.G_NET()
-    netG.apply(weights_init)
-    ckpts = []
-    for d in names:
-        os.makedirs(str(tmp_path / d))
-        ckpts.append(str(tmp_path / d / 'netG_epoch_0.pth'))
-        torch.save(netG.state_dict(), ckpts[-1])
-
-    def make(*a):
-        return condGANTrainer(*a, allow_random_encoders=True)
-    return make, loader, ds, ckpts
-
-
 def test_sampling_without_with_and_with_cached_real_statistics(tmp_path):
     from miscc.config import reset_cfg
-    make, loader, ds, ckpts = _rnn_setup(tmp_path, ('without', 'with', 'cached'))
+    make, loader, ds, ckpts = sh.setup(tmp_path, ('without', 'with', 'cached'))
     stats = str(tmp_path / 'real.npz')
-    algo0, files0, states0, calls0 = _sample(make, loader, ds, ckpts[0])
-    algo1, files1, states1, calls1 = _sample(make, loader, ds, ckpts[1], fid=True, fid_stats=stats)
+    algo0, files0, states0, calls0 = sh.sample(make, loader, ds, ckpts[0])
+    algo1, files1, states1, calls1 = sh.sample(make, loader, ds, ckpts[1], fid=True, fid_stats=stats)
     assert algo0.fid_result is None and calls0 == 0 and len(files0) == 6 and all(k.endswith('.png') for k in files0)
     # the same image files, byte for byte, and fid.json beside them
-    assert sorted(files1) == sorted(list(files0) + ['fid.json']) and _images(files1) == files0
+    assert sorted(files1) == sorted(list(files0) + ['fid.json']) and sh.images(files1) == files0
     # the flag consumes none of the randomness the data path and the noise draw from
-    assert _same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     res1 = _check_result(algo1, files1, 6)
     assert calls1 == 3 + 3                          # one trunk forward per generated and per real batch
     assert os.path.exists(stats)                    # a missing --fid_stats file is written after the run
     # a second run reads the real side from that file: no real-side forward, the same trace_real bit for bit
-    algo2, files2, states2, calls2 = _sample(make, loader, ds, ckpts[2], fid=True, fid_stats=stats)
+    algo2, files2, states2, calls2 = sh.sample(make, loader, ds, ckpts[2], fid=True, fid_stats=stats)
     res2 = _check_result(algo2, files2, 6)
     assert calls2 == 3
     assert res2['trace_real'] == res1['trace_real'] and res2['n_real'] == 6
-    assert _images(files2) == files0 and _same_states(states2, states0)
+    assert sh.images(files2) == files0 and sh.same_states(states2, states0)
     # a file written under another key is refused
     from sbagan import ops
     ops.set_compute_dtype(torch.float32)
     try:
         with pytest.raises(ValueError, match='holds statistics for'):
-            _sample(make, loader, ds, ckpts[2], fid=True, fid_stats=stats)
+            sh.sample(make, loader, ds, ckpts[2], fid=True, fid_stats=stats)
     finally:
         ops.set_compute_dtype(torch.bfloat16)
     reset_cfg()
@@ -427,47 +329,22 @@ def test_sampling_without_with_and_with_cached_real_statistics(tmp_path):
 
 def test_sampling_with_r_precision_shares_the_generated_forward(tmp_path):
     from miscc.config import reset_cfg
-    make, loader, ds, ckpts = _rnn_setup(tmp_path, ('rp', 'both'))
-    algo0, files0, states0, calls0 = _sample(make, loader, ds, ckpts[0], R=4)
-    algo1, files1, states1, calls1 = _sample(make, loader, ds, ckpts[1], fid=True, R=4)
+    make, loader, ds, ckpts = sh.setup(tmp_path, ('rp', 'both'))
+    algo0, files0, states0, calls0 = sh.sample(make, loader, ds, ckpts[0], r_precision=4)
+    algo1, files1, states1, calls1 = sh.sample(make, loader, ds, ckpts[1], fid=True, r_precision=4)
     assert calls0 == 3
     assert calls1 == 3 + 3                          # the generated batch goes through the trunk ONCE
-    assert sorted(files1) == sorted(list(files0) + ['fid.json']) and _images(files1) == _images(files0)
+    assert sorted(files1) == sorted(list(files0) + ['fid.json']) and sh.images(files1) == sh.images(files0)
     assert json.loads(files1['r_precision.json'].decode()) == json.loads(files0['r_precision.json'].decode())
-    assert _same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     _check_result(algo1, files1, 6)
     reset_cfg()
 
 
 def test_sampling_with_fid_through_the_bert_trainer(tmp_path):
-    from test_bert_entry_gpu import _bert_dir
-    from test_host_cpu import _make_dataset
-    _toy_cfg()
-    import datasets_bert
-    import model_bert
-    from miscc import transforms
     from miscc.config import reset_cfg
-    from miscc.utils import weights_init
-    from sbagan import ops
-    from trainer_bert import condGANTrainer
-    ops.set_compute_dtype(torch.bfloat16)
-    root = str(tmp_path / 'toy')
-    _make_dataset(root, n_test=6)
-    bert_dir = _bert_dir(tmp_path)
-    tf = transforms.Compose([transforms.Resize(int(128 * 76 / 64)), transforms.RandomCrop(128),
-                             transforms.RandomHorizontalFlip()])
-    ds = datasets_bert.TextDataset(root, 'test', base_size=64, transform=tf, bert_dir=bert_dir)
-    loader = torch.utils.data.DataLoader(ds, batch_size=2, drop_last=True, shuffle=False)
-    torch.manual_seed(1)
-    netG = model_bert.G_NET()
-    netG.apply(weights_init)
-    os.makedirs(str(tmp_path / 'out'))
-    ckpt = str(tmp_path / 'out' / 'netG_epoch_0.pth')
-    torch.save(netG.state_dict(), ckpt)
-
-    def make(*a):
-        return condGANTrainer(*a, allow_random_encoders=True, bert_dir=bert_dir)
-    algo, files, _, calls = _sample(make, loader, ds, ckpt, fid=True)
+    make, loader, ds, (ckpt,) = sh.setup(tmp_path, ('out',), bert=True)
+    algo, files, _, calls = sh.sample(make, loader, ds, ckpt, fid=True)
     assert len(files) == 7 and calls == 6
     _check_result(algo, files, 6)
     reset_cfg()

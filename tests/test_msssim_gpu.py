@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import msssim_ref
+import sampling_harness as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -306,70 +307,12 @@ def test_class_with_hand_fed_batches():
 CLASSES = [1, 1, 1, 2, 2, 3]        # of the 6 test images: 3 + 1 pairs, 2 drawn of the first class; class 3 is skipped
 PER_CLASS = 2
 SIZE = 256
+OTHERS = dict(fid=True, r_precision=4, prdc=3, kid=True, kid_subsets=4, kid_subset_size=5)  # every other evaluator on
 
 
 def _setup_256(tmp_path, names, bert=False):
-    """test_fid_gpu._rnn_setup at 256 px (BRANCH_NUM 3) on a toy data dir of its own whose 6 test images have CLASSES"""
-    import pickle
-    import test_fid_gpu as tf
-    from test_host_cpu import _make_dataset
-    cfg = tf._toy_cfg()
-    cfg.TREE.BRANCH_NUM = 3
-    from miscc import transforms
-    from miscc.utils import weights_init
-    from sbagan import ops
-    ops.set_compute_dtype(torch.bfloat16)
-    root = str(tmp_path / 'toy256')
-    _make_dataset(root, n_test=6)
-    with open(os.path.join(root, 'test', 'class_info.pickle'), 'wb') as f:
-        pickle.dump(CLASSES, f)
-    tfm = transforms.Compose([transforms.Resize(int(SIZE * 76 / 64)), transforms.RandomCrop(SIZE),
-                              transforms.RandomHorizontalFlip()])
-    if bert:
-        import datasets_bert
-        import model_bert
-        from test_bert_entry_gpu import _bert_dir
-        from trainer_bert import condGANTrainer
-        bert_dir = _bert_dir(tmp_path)
-        ds = datasets_bert.TextDataset(root, 'test', base_size=64, transform=tfm, bert_dir=bert_dir)
-        G_NET = model_bert.G_NET
-
-        def make(*a):
-            return condGANTrainer(*a, allow_random_encoders=True, bert_dir=bert_dir)
-    else:
-        import datasets
-        import model
-        from trainer import condGANTrainer
-        ds = datasets.TextDataset(root, 'test', base_size=64, transform=tfm)
-        G_NET = model.G_NET
-
-        def make(*a):
-            return condGANTrainer(*a, allow_random_encoders=True)
-    assert ds.imsize[-1] == SIZE
-    loader = torch.utils.data.DataLoader(ds, batch_size=2, drop_last=True, shuffle=not bert)
-    torch.manual_seed(1)
-    netG = G_NET()
-    netG.apply(weights_init)
-    ckpts = []
-    for d in names:
-        os.makedirs(str(tmp_path / d))
-        ckpts.append(str(tmp_path / d / 'netG_epoch_0.pth'))
-        torch.save(netG.state_dict(), ckpts[-1])
-    return make, loader, ds, ckpts
-
-
-def _sample(make, loader, ds, ckpt, ms_ssim=0, others=False):
-    """test_fid_gpu._sample (identical seeding, the deterministic-reduction mode) with ms_ssim set; others: every other
-    evaluator on as well"""
-    import test_fid_gpu as tf
-
-    def make_with_flag(*a):
-        algo = make(*a)
-        algo.ms_ssim = ms_ssim
-        if others:
-            algo.prdc, algo.kid, algo.kid_subsets, algo.kid_subset_size = 3, True, 4, 5
-        return algo
-    return tf._sample(make_with_flag, loader, ds, ckpt, fid=others, R=4 if others else 0)
+    """the toy setup at 256 px (BRANCH_NUM 3) on a data dir of its own whose 6 test images have CLASSES"""
+    return sh.setup(tmp_path, names, size=SIZE, bert=bert, classes=CLASSES)
 
 
 def _decoded(files):
@@ -399,33 +342,31 @@ def _check_result(algo, files):
 
 
 def test_sampling_without_and_with_the_flag(tmp_path):
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
     make, loader, ds, ckpts = _setup_256(tmp_path, ('without', 'with'))
-    algo0, files0, states0, calls0 = _sample(make, loader, ds, ckpts[0])
-    algo1, files1, states1, calls1 = _sample(make, loader, ds, ckpts[1], ms_ssim=PER_CLASS)
+    algo0, files0, states0, calls0 = sh.sample(make, loader, ds, ckpts[0])
+    algo1, files1, states1, calls1 = sh.sample(make, loader, ds, ckpts[1], ms_ssim=PER_CLASS)
     assert algo0.ms_ssim_result is None and algo0.ms_ssim_evaluator is None
     assert calls0 == 0 and len(files0) == 6 and all(k.endswith('.png') for k in files0)
     # the same image files, byte for byte, and ms_ssim.json beside them
-    assert sorted(files1) == sorted(list(files0) + ['ms_ssim.json']) and tf._images(files1) == files0
+    assert sorted(files1) == sorted(list(files0) + ['ms_ssim.json']) and sh.images(files1) == files0
     # the flag consumes none of the randomness the data path and the noise draw from
-    assert tf._same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     assert calls1 == 0                              # no image encoder: the figure is on the pixels
     _check_result(algo1, files1)
     reset_cfg()
 
 
 def test_sampling_with_every_other_evaluator_leaves_their_results_unchanged(tmp_path):
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
     make, loader, ds, ckpts = _setup_256(tmp_path, ('four', 'five'))
-    algo0, files0, states0, calls0 = _sample(make, loader, ds, ckpts[0], others=True)
-    algo1, files1, states1, calls1 = _sample(make, loader, ds, ckpts[1], ms_ssim=PER_CLASS, others=True)
+    algo0, files0, states0, calls0 = sh.sample(make, loader, ds, ckpts[0], **OTHERS)
+    algo1, files1, states1, calls1 = sh.sample(make, loader, ds, ckpts[1], ms_ssim=PER_CLASS, **OTHERS)
     assert calls0 == calls1 == 3 + 3
-    assert sorted(files1) == sorted(list(files0) + ['ms_ssim.json']) and tf._images(files1) == tf._images(files0)
+    assert sorted(files1) == sorted(list(files0) + ['ms_ssim.json']) and sh.images(files1) == sh.images(files0)
     for name in ('fid.json', 'prdc.json', 'kid.json', 'r_precision.json'):
         assert json.loads(files1[name].decode()) == json.loads(files0[name].decode()), name
-    assert tf._same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     _check_result(algo1, files1)
     reset_cfg()
 
@@ -433,23 +374,17 @@ def test_sampling_with_every_other_evaluator_leaves_their_results_unchanged(tmp_
 def test_sampling_with_ms_ssim_through_the_bert_trainer(tmp_path):
     from miscc.config import reset_cfg
     make, loader, ds, ckpts = _setup_256(tmp_path, ('out',), bert=True)
-    algo, files, _, calls = _sample(make, loader, ds, ckpts[0], ms_ssim=PER_CLASS)
+    algo, files, _, calls = sh.sample(make, loader, ds, ckpts[0], ms_ssim=PER_CLASS)
     assert len(files) == 7 and calls == 0
     _check_result(algo, files)
     reset_cfg()
 
 
 def test_a_128_px_configuration_is_refused_before_any_file_exists(tmp_path):
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
-    make, loader, ds, ckpts = tf._rnn_setup(tmp_path, ('small',))
-
-    def make_with_flag(*a):
-        algo = make(*a)
-        algo.ms_ssim = PER_CLASS
-        return algo
+    make, loader, ds, ckpts = sh.setup(tmp_path, ('small',))
     with pytest.raises(ValueError, match='176'):
-        tf._sample(make_with_flag, loader, ds, ckpts[0])
+        sh.sample(make, loader, ds, ckpts[0], ms_ssim=PER_CLASS)
     left = [os.path.join(d, f) for d, _, fs in os.walk(os.path.dirname(ckpts[0])) for f in fs]
     assert left == [ckpts[0]]
     assert not os.path.exists(ckpts[0][:-len('.pth')])          # not even the output directory

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import nearest_ref
+import sampling_harness as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -374,37 +375,6 @@ def random_encoders(monkeypatch):
     monkeypatch.setattr(trainer.condGANTrainer, '__init__', init_random)
 
 
-def _run_main(mod, tmp_path, name, extra, root, bert_dir=None, dtype=torch.bfloat16):
-    """<mod>.main() sampling the toy data set's test split from a fresh copy of one generator checkpoint, in the
-    deterministic-reduction mode (see test_fid_gpu._sample); returns (files, generator states, trunk forwards)"""
-    import glob
-
-    import test_fid_gpu as tf
-    from sbagan import ops
-    tf._toy_cfg()
-    ops.set_compute_dtype(dtype)
-    os.makedirs(str(tmp_path / name))
-    ckpt = str(tmp_path / name / 'netG_epoch_0.pth')
-    torch.save(torch.load(str(tmp_path / 'netG.pth')), ckpt)
-    yml = str(tmp_path / (name + '.yml'))
-    with open(yml, 'w') as f:
-        f.write('CONFIG_NAME: toy\nDATASET_NAME: toy\nB_VALIDATION: True\nWORKERS: 0\n'
-                'TREE: {BRANCH_NUM: 2}\nTRAIN: {FLAG: False, BATCH_SIZE: 2, NET_G: "%s"}\n'
-                'GAN: {GF_DIM: 32, DF_DIM: 64}\nTEXT: {CAPTIONS_PER_IMAGE: 2, WORDS_NUM: 8, EMBEDDING_DIM: 256}\n' % ckpt)
-    argv = ['--cfg', yml, '--data_dir', root] + (['--bert_dir', bert_dir] if bert_dir else []) + extra
-    ops.set_deterministic(True, DEV)
-    try:
-        with tf._CountForwards() as count:
-            mod.main(argv)
-    finally:
-        ops.set_deterministic(False)
-    states = (np.random.get_state(), torch.cuda.get_rng_state(), torch.get_rng_state())
-    out_dir = os.path.join(os.path.dirname(ckpt), 'netG_epoch_0', 'valid')
-    files = {os.path.relpath(f, out_dir): open(f, 'rb').read()
-             for f in glob.glob(os.path.join(out_dir, '**', '*'), recursive=True) if os.path.isfile(f)}
-    return files, states, count.n
-
-
 def _check_json(files, k, show, n_train=4, n_images=6):
     from sbagan.nearest import FIELDS
     res = json.loads(files['nearest.json'].decode())
@@ -423,9 +393,8 @@ def _check_json(files, k, show, n_train=4, n_images=6):
 
 
 def _rnn_generator(tmp_path):
-    import test_fid_gpu as tf
     from test_host_cpu import _make_dataset
-    tf._toy_cfg()
+    sh.toy_cfg()
     import model
     from miscc.utils import weights_init
     root = str(tmp_path / 'toy')
@@ -441,20 +410,19 @@ def test_main_without_and_with_the_flag_and_with_the_cache(tmp_path, random_enco
     import io
 
     import main
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
     from PIL import Image
     root = _rnn_generator(tmp_path)
     stats = str(tmp_path / 'train.npz')
-    files0, states0, calls0 = _run_main(main, tmp_path, 'without', [], root)
-    files1, states1, calls1 = _run_main(main, tmp_path, 'with', ['--nearest', '3', '--nearest_show', '2',
+    files0, states0, calls0 = sh.run_main(main, tmp_path, 'without', [], root)
+    files1, states1, calls1 = sh.run_main(main, tmp_path, 'with', ['--nearest', '3', '--nearest_show', '2',
                                                                    '--nearest_stats', stats], root)
     assert calls0 == 0 and len(files0) == 6 and all(k.endswith('_s-1.png') for k in files0)
     # the same image files, byte for byte, with nearest.json and nearest.png beside them
     assert sorted(files1) == sorted(list(files0) + ['nearest.json', 'nearest.png'])
     assert {k: v for k, v in files1.items() if k in files0} == files0
     # the flag consumes none of the randomness the data path and the noise draw from
-    assert tf._same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     assert calls1 == 3 + 3 + 2                      # one trunk forward per generated, per real and per training batch
     res1 = _check_json(files1, 3, 2)
     sheet = Image.open(io.BytesIO(files1['nearest.png']))
@@ -472,19 +440,19 @@ def test_main_without_and_with_the_flag_and_with_the_cache(tmp_path, random_enco
                                   np.asarray(tile))
     # a missing --nearest_stats file was written; a second run reads it: no training pass, the same JSON
     assert os.path.exists(stats)
-    files2, states2, calls2 = _run_main(main, tmp_path, 'cached', ['--nearest', '3', '--nearest_show', '2',
+    files2, states2, calls2 = sh.run_main(main, tmp_path, 'cached', ['--nearest', '3', '--nearest_show', '2',
                                                                      '--nearest_stats', stats], root)
     assert calls2 == 3 + 3
     assert json.loads(files2['nearest.json'].decode()) == res1 and files2['nearest.png'] == files1['nearest.png']
-    assert {k: v for k, v in files2.items() if k in files0} == files0 and tf._same_states(states2, states0)
+    assert {k: v for k, v in files2.items() if k in files0} == files0 and sh.same_states(states2, states0)
     # --nearest_show 0: no picture and no suspects; a file written under another key is refused
-    files3, _, _ = _run_main(main, tmp_path, 'bare', ['--nearest', '1', '--nearest_show', '0'], root)
+    files3, _, _ = sh.run_main(main, tmp_path, 'bare', ['--nearest', '1', '--nearest_show', '0'], root)
     assert sorted(files3) == sorted(list(files0) + ['nearest.json'])
     _check_json(files3, 1, 0)
     from sbagan import ops
     try:
         with pytest.raises(ValueError, match='holds training rows for'):
-            _run_main(main, tmp_path, 'refused', ['--nearest', '3', '--nearest_stats', stats], root, dtype=torch.float32)
+            sh.run_main(main, tmp_path, 'refused', ['--nearest', '3', '--nearest_stats', stats], root, dtype=torch.float32)
     finally:
         ops.set_compute_dtype(torch.bfloat16)
     reset_cfg()
@@ -492,18 +460,17 @@ def test_main_without_and_with_the_flag_and_with_the_cache(tmp_path, random_enco
 
 def test_main_with_fid_and_prdc_shares_the_forwards(tmp_path, random_encoders):
     import main
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
     root = _rnn_generator(tmp_path)
-    files0, states0, calls0 = _run_main(main, tmp_path, 'two', ['--fid', '--prdc', '2'], root)
-    files1, states1, calls1 = _run_main(main, tmp_path, 'three', ['--fid', '--prdc', '2', '--nearest', '2'], root)
+    files0, states0, calls0 = sh.run_main(main, tmp_path, 'two', ['--fid', '--prdc', '2'], root)
+    files1, states1, calls1 = sh.run_main(main, tmp_path, 'three', ['--fid', '--prdc', '2', '--nearest', '2'], root)
     assert calls0 == 3 + 3
     assert calls1 == 3 + 3 + 2                      # each batch goes through the trunk ONCE for all three evaluators
     assert sorted(files1) == sorted(list(files0) + ['nearest.json', 'nearest.png'])
-    assert tf._images({k: v for k, v in files1.items() if k != 'nearest.png'}) == tf._images(files0)
+    assert sh.images({k: v for k, v in files1.items() if k != 'nearest.png'}) == sh.images(files0)
     for name in ('fid.json', 'prdc.json'):
         assert json.loads(files1[name].decode()) == json.loads(files0[name].decode())
-    assert tf._same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     _check_json(files1, 2, 16)
     reset_cfg()
 
@@ -511,12 +478,11 @@ def test_main_with_fid_and_prdc_shares_the_forwards(tmp_path, random_encoders):
 def test_main_bert_with_the_flag(tmp_path, random_encoders):
     import main_bert
     import model_bert
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
     from miscc.utils import weights_init
     from test_bert_entry_gpu import _bert_dir
     from test_host_cpu import _make_dataset
-    tf._toy_cfg()
+    sh.toy_cfg()
     root = str(tmp_path / 'toy')
     _make_dataset(root, n_test=6)
     bert_dir = _bert_dir(tmp_path)
@@ -524,7 +490,7 @@ def test_main_bert_with_the_flag(tmp_path, random_encoders):
     netG = model_bert.G_NET()
     netG.apply(weights_init)
     torch.save(netG.state_dict(), str(tmp_path / 'netG.pth'))
-    files, _, calls = _run_main(main_bert, tmp_path, 'bert', ['--nearest', '2', '--nearest_show', '3'], root, bert_dir)
+    files, _, calls = sh.run_main(main_bert, tmp_path, 'bert', ['--nearest', '2', '--nearest_show', '3'], root, bert_dir)
     assert len(files) == 8 and calls == 3 + 3 + 2
     _check_json(files, 2, 3)
     reset_cfg()

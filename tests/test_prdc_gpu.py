@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import prdc_ref
+import sampling_harness as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -384,17 +385,6 @@ def test_prdc_class_with_stub_features():
 
 
 # ------------------------------------------------------------------ sampling() with the flag
-def _sample(make, loader, ds, ckpt, prdc=0, fid=False, fid_stats=None, R=0):
-    """test_fid_gpu._sample with algo.prdc set: sampling('test') after identical seeding, in the deterministic mode"""
-    import test_fid_gpu as tf
-
-    def make_with_flag(*a):
-        algo = make(*a)
-        algo.prdc = prdc
-        return algo
-    return tf._sample(make_with_flag, loader, ds, ckpt, fid=fid, fid_stats=fid_stats, R=R)
-
-
 def _check_result(algo, files, n_images, k):
     res = json.loads(files['prdc.json'].decode())
     print('prdc.json:', res)
@@ -408,74 +398,46 @@ def _check_result(algo, files, n_images, k):
 
 
 def test_sampling_without_and_with_the_flag(tmp_path):
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
-    make, loader, ds, ckpts = tf._rnn_setup(tmp_path, ('without', 'with'))
-    algo0, files0, states0, calls0 = _sample(make, loader, ds, ckpts[0])
-    algo1, files1, states1, calls1 = _sample(make, loader, ds, ckpts[1], prdc=2)
+    make, loader, ds, ckpts = sh.setup(tmp_path, ('without', 'with'))
+    algo0, files0, states0, calls0 = sh.sample(make, loader, ds, ckpts[0])
+    algo1, files1, states1, calls1 = sh.sample(make, loader, ds, ckpts[1], prdc=2)
     assert algo0.prdc_result is None and calls0 == 0 and len(files0) == 6 and all(k.endswith('.png') for k in files0)
     # the same image files, byte for byte, and prdc.json beside them
-    assert sorted(files1) == sorted(list(files0) + ['prdc.json']) and tf._images(files1) == files0
+    assert sorted(files1) == sorted(list(files0) + ['prdc.json']) and sh.images(files1) == files0
     # the flag consumes none of the randomness the data path and the noise draw from
-    assert tf._same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     _check_result(algo1, files1, 6, 2)
     assert calls1 == 3 + 3                          # one trunk forward per generated and per real batch
     reset_cfg()
 
 
 def test_sampling_with_fid_and_r_precision_shares_the_forwards(tmp_path):
-    import test_fid_gpu as tf
     from miscc.config import reset_cfg
-    make, loader, ds, ckpts = tf._rnn_setup(tmp_path, ('two', 'three', 'cached'))
+    make, loader, ds, ckpts = sh.setup(tmp_path, ('two', 'three', 'cached'))
     stats = str(tmp_path / 'real.npz')
-    algo0, files0, states0, calls0 = _sample(make, loader, ds, ckpts[0], fid=True, fid_stats=stats, R=4)
-    algo1, files1, states1, calls1 = _sample(make, loader, ds, ckpts[1], prdc=2, fid=True, R=4)
+    algo0, files0, states0, calls0 = sh.sample(make, loader, ds, ckpts[0], fid=True, fid_stats=stats, r_precision=4)
+    algo1, files1, states1, calls1 = sh.sample(make, loader, ds, ckpts[1], prdc=2, fid=True, r_precision=4)
     assert calls0 == 3 + 3 and os.path.exists(stats)
     assert calls1 == 3 + 3                          # each batch goes through the trunk ONCE for all three evaluators
-    assert sorted(files1) == sorted(list(files0) + ['prdc.json']) and tf._images(files1) == tf._images(files0)
+    assert sorted(files1) == sorted(list(files0) + ['prdc.json']) and sh.images(files1) == sh.images(files0)
     for name in ('fid.json', 'r_precision.json'):
         assert json.loads(files1[name].decode()) == json.loads(files0[name].decode())
-    assert tf._same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     res1 = _check_result(algo1, files1, 6, 2)
     # cached real FID statistics: FID skips its real pass, the real batches are encoded for PRDC alone
-    algo2, files2, states2, calls2 = _sample(make, loader, ds, ckpts[2], prdc=2, fid=True, fid_stats=stats, R=4)
+    algo2, files2, states2, calls2 = sh.sample(make, loader, ds, ckpts[2], prdc=2, fid=True, fid_stats=stats, r_precision=4)
     assert calls2 == 3 + 3
     assert _check_result(algo2, files2, 6, 2) == res1
     assert json.loads(files2['fid.json'].decode()) == json.loads(files0['fid.json'].decode())
-    assert tf._images(files2) == tf._images(files0) and tf._same_states(states2, states0)
+    assert sh.images(files2) == sh.images(files0) and sh.same_states(states2, states0)
     reset_cfg()
 
 
 def test_sampling_with_prdc_through_the_bert_trainer(tmp_path):
-    import test_fid_gpu as tf
-    from test_bert_entry_gpu import _bert_dir
-    from test_host_cpu import _make_dataset
-    tf._toy_cfg()
-    import datasets_bert
-    import model_bert
-    from miscc import transforms
     from miscc.config import reset_cfg
-    from miscc.utils import weights_init
-    from sbagan import ops
-    from trainer_bert import condGANTrainer
-    ops.set_compute_dtype(torch.bfloat16)
-    root = str(tmp_path / 'toy')
-    _make_dataset(root, n_test=6)
-    bert_dir = _bert_dir(tmp_path)
-    tfm = transforms.Compose([transforms.Resize(int(128 * 76 / 64)), transforms.RandomCrop(128),
-                              transforms.RandomHorizontalFlip()])
-    ds = datasets_bert.TextDataset(root, 'test', base_size=64, transform=tfm, bert_dir=bert_dir)
-    loader = torch.utils.data.DataLoader(ds, batch_size=2, drop_last=True, shuffle=False)
-    torch.manual_seed(1)
-    netG = model_bert.G_NET()
-    netG.apply(weights_init)
-    os.makedirs(str(tmp_path / 'out'))
-    ckpt = str(tmp_path / 'out' / 'netG_epoch_0.pth')
-    torch.save(netG.state_dict(), ckpt)
-
-    def make(*a):
-        return condGANTrainer(*a, allow_random_encoders=True, bert_dir=bert_dir)
-    algo, files, _, calls = _sample(make, loader, ds, ckpt, prdc=2)
+    make, loader, ds, (ckpt,) = sh.setup(tmp_path, ('out',), bert=True)
+    algo, files, _, calls = sh.sample(make, loader, ds, ckpt, prdc=2)
     assert len(files) == 7 and calls == 6
     _check_result(algo, files, 6, 2)
     reset_cfg()

@@ -3,14 +3,14 @@ tests/test_rprecision_cpu.py (scores within the f32 summation bound, ranks exact
 determinism, the wrapper's refusals, the evaluator with a stub image encoder, and sampling() with the flag through both
 trainers."""
 import functools
-import glob
 import json
 import os
-import random
 
 import numpy as np
 import pytest
 import torch
+
+import sampling_harness as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -232,33 +232,10 @@ def test_evaluator_code_equal_to_a_mismatched_candidate():
 
 
 # ------------------------------------------------------------------ sampling() with the flag
-def _toy_cfg():
-    from miscc.config import cfg, reset_cfg
-    reset_cfg()
-    cfg.GAN.GF_DIM, cfg.GAN.DF_DIM, cfg.TREE.BRANCH_NUM = 32, 64, 2
-    cfg.TEXT.CAPTIONS_PER_IMAGE, cfg.TEXT.WORDS_NUM, cfg.TEXT.EMBEDDING_DIM = 2, 8, 256
-    cfg.TRAIN.BATCH_SIZE = 2
-    cfg.TRAIN.NET_E, cfg.TRAIN.NET_G, cfg.TRAIN.FLAG, cfg.CUDA, cfg.GPU_ID = '', '', False, True, 0
-    return cfg
-
-
-def _seed_all(seed):
-    for seeder in (random.seed, np.random.seed, torch.manual_seed, torch.cuda.manual_seed_all):
-        seeder(seed)
-
-
-def _sample(make_trainer, loader, ds, ckpt, R):
-    """sampling('test') from `ckpt` after identical seeding: (trainer, relative file names, generator states after)"""
-    from miscc.config import cfg
-    cfg.TRAIN.NET_G = ckpt
-    algo = make_trainer(os.path.dirname(ckpt), loader, ds.n_words, ds.ixtoword)
-    algo.r_precision = R
-    _seed_all(100)
-    out_dir = algo.sampling('test')
-    states = (np.random.get_state(), torch.cuda.get_rng_state(), torch.get_rng_state())
-    files = sorted(os.path.relpath(f, out_dir) for f in glob.glob(os.path.join(out_dir, '**', '*'), recursive=True)
-                   if os.path.isfile(f))
-    return algo, out_dir, files, states
+def _sample(make, loader, ds, ckpt, R):
+    """sampling_harness.sample as these tests read it: (trainer, output directory, sorted file names, states after)"""
+    algo, files, states, _ = sh.sample(make, loader, ds, ckpt, r_precision=R)
+    return algo, os.path.join(ckpt[:-len('.pth')], 'valid'), sorted(files), states
 
 
 def _check_result(algo, out_dir, R):
@@ -275,33 +252,8 @@ def _check_result(algo, out_dir, R):
 
 
 def test_sampling_with_and_without_the_flag(tmp_path):
-    from test_host_cpu import _make_dataset
-    cfg = _toy_cfg()
-    import datasets
-    import model
-    from miscc import transforms
     from miscc.config import reset_cfg
-    from miscc.utils import weights_init
-    from sbagan import ops
-    from trainer import condGANTrainer
-    ops.set_compute_dtype(torch.bfloat16)
-    root = str(tmp_path / 'toy')
-    _make_dataset(root, n_test=6)
-    tf = transforms.Compose([transforms.Resize(int(128 * 76 / 64)), transforms.RandomCrop(128),
-                             transforms.RandomHorizontalFlip()])
-    ds = datasets.TextDataset(root, 'test', base_size=64, transform=tf)
-    loader = torch.utils.data.DataLoader(ds, batch_size=2, drop_last=True, shuffle=True)
-    torch.manual_seed(1)
-    netG = model.G_NET()
-    netG.apply(weights_init)
-    ckpts = []
-    for d in ('with', 'without'):
-        os.makedirs(str(tmp_path / d))
-        ckpts.append(str(tmp_path / d / 'netG_epoch_0.pth'))
-        torch.save(netG.state_dict(), ckpts[-1])
-
-    def make(*a):
-        return condGANTrainer(*a, allow_random_encoders=True)
+    make, loader, ds, ckpts = sh.setup(tmp_path, ('with', 'without'))
     algo, out_dir, files, states = _sample(make, loader, ds, ckpts[0], 4)
     algo0, out_dir0, files0, states0 = _sample(make, loader, ds, ckpts[1], 0)
     assert algo0.r_precision_result is None and 'r_precision.json' not in files0
@@ -316,33 +268,8 @@ def test_sampling_with_and_without_the_flag(tmp_path):
 
 def test_sampling_with_the_flag_through_the_bert_trainer(tmp_path):
     """the pool is encoded through the trainer's _encode hook: trainer_bert's BertEncoder (a random 2-layer trunk)"""
-    from test_bert_entry_gpu import _bert_dir
-    from test_host_cpu import _make_dataset
-    _toy_cfg()
-    import datasets_bert
-    import model_bert
-    from miscc import transforms
     from miscc.config import reset_cfg
-    from miscc.utils import weights_init
-    from sbagan import ops
-    from trainer_bert import condGANTrainer
-    ops.set_compute_dtype(torch.bfloat16)
-    root = str(tmp_path / 'toy')
-    _make_dataset(root, n_test=6)
-    bert_dir = _bert_dir(tmp_path)
-    tf = transforms.Compose([transforms.Resize(int(128 * 76 / 64)), transforms.RandomCrop(128),
-                             transforms.RandomHorizontalFlip()])
-    ds = datasets_bert.TextDataset(root, 'test', base_size=64, transform=tf, bert_dir=bert_dir)
-    loader = torch.utils.data.DataLoader(ds, batch_size=2, drop_last=True, shuffle=False)
-    torch.manual_seed(1)
-    netG = model_bert.G_NET()
-    netG.apply(weights_init)
-    os.makedirs(str(tmp_path / 'out'))
-    ckpt = str(tmp_path / 'out' / 'netG_epoch_0.pth')
-    torch.save(netG.state_dict(), ckpt)
-
-    def make(*a):
-        return condGANTrainer(*a, allow_random_encoders=True, bert_dir=bert_dir)
+    make, loader, ds, (ckpt,) = sh.setup(tmp_path, ('out',), bert=True)
     algo, out_dir, files, _ = _sample(make, loader, ds, ckpt, 4)
     assert len(files) == 7 and 'r_precision.json' in files
     _check_result(algo, out_dir, 4)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import sampling_harness as sh
 import swd_ref
 
 pytestmark = pytest.mark.gpu
@@ -441,8 +442,7 @@ def test_main_with_and_without_the_flag(tmp_path, capsys):
     assert len(pngs0) == 4 and pngs0 == files0
     swd_name = [k for k in files1 if k.endswith('swd.json')]
     assert len(swd_name) == 1 and {k: v for k, v in files1.items() if k != swd_name[0]} == files0
-    import test_fid_gpu as tf
-    assert tf._same_states(states1, states0)
+    assert sh.same_states(states1, states0)
     res = json.loads(files1[swd_name[0]].decode())
     print(out1)
     assert res == algo1.swd_result and res['levels'] == 4 == len(res['swd_x1e3']) and res['n_images'] == 4

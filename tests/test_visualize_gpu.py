@@ -4,13 +4,13 @@ wrappers' refusals, the C ABI's, and the flag end to end through both trainers a
 import functools
 import glob
 import os
-import random
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
 
+import sampling_harness as sh
 import vis_ref
 
 pytestmark = pytest.mark.gpu
@@ -285,18 +285,8 @@ def test_c_abi_rejects_bad_sizes_and_null_pointers():
 
 
 # ------------------------------------------------------------------ end to end, on the toy config of test_rprecision_gpu
-def _seed_all(seed):
-    for seeder in (random.seed, np.random.seed, torch.manual_seed, torch.cuda.manual_seed_all):
-        seeder(seed)
-
-
 def _rng_states():
     return np.random.get_state(), torch.cuda.get_rng_state(), torch.get_rng_state()
-
-
-def _same_states(s, s0):
-    return s[0][0] == s0[0][0] and np.array_equal(s[0][1], s0[0][1]) and s[0][2:] == s0[0][2:] \
-        and torch.equal(s[1], s0[1]) and torch.equal(s[2], s0[2])
 
 
 def _files(root):
@@ -306,8 +296,7 @@ def _files(root):
 
 def _toy(tmp_path, bert):
     from test_host_cpu import _make_dataset
-    from test_rprecision_gpu import _toy_cfg
-    _toy_cfg()
+    sh.toy_cfg()
     from miscc import transforms
     from sbagan import ops
     ops.set_compute_dtype(torch.bfloat16)
@@ -367,7 +356,7 @@ def _save_img_runs(tmp_path, ds, loader, captions, cap_lens, written, trainer, b
     for name, flag in (('on', True), ('off', False), ('off2', False)):
         algo, out = _trainer(tmp_path, name, ds, loader, None, True)
         algo.attention_maps = flag
-        _seed_all(7)
+        sh.seed_all(7)
         text_encoder, image_encoder, netG, netsD, _ = algo.build_models()
         netG.set_return_attention(False)
         words_embs, sent_emb = algo._encode(text_encoder, captions, cap_lens)
@@ -399,7 +388,7 @@ def _gen_example(tmp_path, name, ds, loader, bert_dir, netG, flag, fused=False):
     torch.save(netG.state_dict(), cfg.TRAIN.NET_G)
     algo.attention_maps = flag
     caps = np.array([[1, 2, 3, 4, 5, 6, 7], [3, 2, 1, 0, 0, 0, 0]], dtype=np.int64)
-    _seed_all(100)
+    sh.seed_all(100)
     root = algo.gen_example({'bird': [caps, np.array([7, 3]), np.array([1, 0])]})
     return root, _rng_states()
 
@@ -435,7 +424,7 @@ def test_gen_example_with_and_without_the_flag(tmp_path, bert, fused):
     for t in tags:                                         # caption 1 (7 words) is row 0, caption 0 (3 words) row 1
         assert Image.open(os.path.join(root, 'bird/0_s_1_a0%s.png' % t)).size == (5 * 258, 306)
         assert Image.open(os.path.join(root, 'bird/0_s_0_a0%s.png' % t)).size == (3 * 258, 306)
-    assert _same_states(states, states0)
+    assert sh.same_states(states, states0)
     reset_cfg()
 
 
