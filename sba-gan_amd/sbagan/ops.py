@@ -265,14 +265,10 @@ class PackedWeight(object):
         return self._dgrad
 
 
-_FRAG_DESC = [('src', '<u8'), ('dst', '<u8'), ('R', '<i4'), ('taps', '<i4'), ('K', '<i4'), ('unit_begin', '<i4')]
-
-
 def _frag_descs(items, device):
     """device array of sba_frag_desc for items = [(src tensor, dst tensor, R, taps, K)] and the total unit count"""
     import numpy as np
-    desc = np.zeros(len(items), dtype=np.dtype(_FRAG_DESC, align=True))
-    assert desc.dtype.itemsize == 32
+    desc = np.zeros(len(items), dtype=np.dtype(_lib.STRUCTS['sba_frag_desc']))
     units = 0
     for d, (src, dst, R, taps, K) in zip(desc, items):
         d['src'], d['dst'], d['R'], d['taps'], d['K'], d['unit_begin'] = src.data_ptr(), dst.data_ptr(), R, taps, K, units
@@ -295,9 +291,6 @@ class PackGroup(object):
     operands, data-gradient operands) and refreshed by ONE sba_pack_weights_multi launch when any
     of them is stale (normally: once after the network's optimizer step) instead of two launches
     per layer.  `layers` = [(PackedWeight, kind)] with kind in '3x3' | '3x3up' | '4x4s2'."""
-
-    _DESC = [('w', '<u8'), ('fwd', '<u8'), ('tr', '<u8'), ('Cout', '<i4'), ('KH', '<i4'), ('KW', '<i4'),
-             ('Cin', '<i4'), ('mode', '<i4'), ('tile_begin', '<i4'), ('co_tiles', '<i4'), ('ci_tiles', '<i4')]
 
     def __init__(self, layers):
         self.layers = [(pw, kind) for pw, kind in layers if pw.param.shape[1] % 4 == 0]
@@ -322,8 +315,7 @@ class PackGroup(object):
         st = {'fwd': torch.empty(n, dtype=dtype, device=dev) if dtype != torch.float32 else None,
               'tr': torch.empty(tn, dtype=dtype, device=dev)}
         esz = st['tr'].element_size()
-        desc = np.zeros(len(self.layers), dtype=np.dtype(self._DESC, align=True))
-        assert desc.dtype.itemsize == 56
+        desc = np.zeros(len(self.layers), dtype=np.dtype(_lib.STRUCTS['sba_pack_desc']))
         tiles = 0
         for i, ((pw, kind), o) in enumerate(zip(self.layers, offs)):
             O, I, KH, KW = pw.param.shape

@@ -2,7 +2,6 @@
 functions and its autograd, the adjoint identity, the integer maps at their edges, the error bound against an f32
 emulation of the kernel's chain and five mutations of it, and the interface: header, bindings, policy, flags."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -159,11 +158,9 @@ def test_bound_fails_every_mutation(S, mutation, flags, forward_fails, backward_
 
 
 def _declared(name):
-    with open(os.path.join(ROOT, 'include', 'sbagan_hip.h')) as fh:
-        text = fh.read()
-    m = re.search(r'int\s+%s\s*\(([^)]*)\)\s*;' % name, text)
-    assert m, '%s is not declared' % name
-    return [' '.join(a.split()) for a in m.group(1).split(',')]
+    from sbagan import _lib
+    assert name in _lib.DECLS and _lib.DECLS[name].ret == 'int', '%s is not declared' % name
+    return ['%s %s' % (ctext, arg) for ctext, arg, _ in _lib.DECLS[name].params]
 
 
 def test_header_and_bindings_agree():

@@ -1,10 +1,9 @@
-"""CPU-only tests of the host side: the C-ABI library loads and exports exactly what
-include/sbagan_hip.h declares, the config loader mirrors the reference's semantics, the
+"""CPU-only tests of the host side: the C-ABI library loads and exports every entry point that
+include/sbagan_hip.h declares (as sbagan.abi parses it), the config loader mirrors the reference's semantics, the
 module tree has the reference's state_dict surface, integer caption work is bit-exact, the
 product path refuses to run without a GPU, and the data-parallel exchange is correct on two
 gloo ranks."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -14,24 +13,20 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_decls():
-    txt = open(os.path.join(ROOT, 'include', 'sbagan_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    decls = {}
-    for m in re.finditer(r'\bint\s+(sba_\w+)\s*\(([^;]*?)\)\s*;', txt, flags=re.S):
-        args = [a for a in m.group(2).split(',') if a.strip() and a.strip() != 'void']
-        decls[m.group(1)] = len(args)
-    return decls
-
-
 def test_library_exports_every_declared_symbol():
+    """every prototype of the header (_lib.DECLS), whatever it returns; SIGNATURES is the part that returns int"""
+    import ctypes
     from sbagan import _lib
-    decls = _header_decls()
-    assert len(decls) >= 40
-    assert set(decls) == set(_lib.SIGNATURES), set(decls) ^ set(_lib.SIGNATURES)
-    for name, nargs in decls.items():
+    assert len(_lib.DECLS) >= 40
+    ints = {name for name, d in _lib.DECLS.items() if d.ret == 'int'}
+    assert ints == set(_lib.SIGNATURES), ints ^ set(_lib.SIGNATURES)
+    for name, d in _lib.DECLS.items():
         assert hasattr(_lib.lib, name), name
-        assert len(_lib.SIGNATURES[name]) == nargs, (name, nargs, len(_lib.SIGNATURES[name]))
+        fn = getattr(_lib.lib, name)
+        assert len(fn.argtypes) == len(d.params), (name, len(d.params), len(fn.argtypes))
+        assert fn.restype is {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'const char*': ctypes.c_char_p}[d.ret], name
+        if name in ints:
+            assert len(_lib.SIGNATURES[name]) == len(d.params), (name, len(d.params), len(_lib.SIGNATURES[name]))
     assert 'gfx950' in _lib.version()
 
 

@@ -4,9 +4,7 @@ misses it), draw_pairs, combine, quantize against trainer._to_uint8, the flag, t
 refusal of CPU tensors, the workspace size and the header / binding agreement.  (The kernel is tested on the GPU in
 tests/test_msssim_gpu.py.)"""
 import ctypes
-import os
 import random
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import torch
 
 import msssim_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C1, C2 = (0.01 * 255.0) ** 2, (0.03 * 255.0) ** 2
 H, W = 176, 208                     # five scales, the last one 11 x 13
 
@@ -247,10 +244,8 @@ def test_operator_refuses_cpu_tensors():
 
 def test_header_declares_what_the_binding_binds():
     from sbagan import _lib
-    txt = open(os.path.join(ROOT, 'include', 'sbagan_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    decls = {m.group(2): (m.group(1), [a for a in m.group(3).split(',') if a.strip()])
-             for m in re.finditer(r'\b(int|int64_t)\s+(sba_msssim_\w+)\s*\(([^;]*?)\)\s*;', txt, flags=re.S)}
+    decls = {name: (d.ret, ['%s %s' % (ctext, arg) for ctext, arg, _ in d.params])
+             for name, d in _lib.DECLS.items() if name.startswith('sba_msssim_')}
     assert sorted(decls) == ['sba_msssim_pairs', 'sba_msssim_workspace_bytes']
     ret, args = decls['sba_msssim_pairs']
     sig = _lib.SIGNATURES['sba_msssim_pairs']

@@ -4,8 +4,6 @@ command-line flags, the gaps of the real-valued fixtures the GPU test relies on,
 (The kernel is tested on the GPU in tests/test_nearest_gpu.py.)"""
 import ctypes
 import json
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +11,6 @@ import torch
 
 import nearest_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = float('inf')
 
 
@@ -244,10 +241,8 @@ def test_operator_refuses_cpu_tensors():
 
 def test_header_declares_what_the_binding_binds():
     from sbagan import _lib
-    txt = open(os.path.join(ROOT, 'include', 'sbagan_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    decls = {m.group(2): (m.group(1), [a for a in m.group(3).split(',') if a.strip()])
-             for m in re.finditer(r'\b(int|int64_t)\s+(sba_knn_\w+)\s*\(([^;]*?)\)\s*;', txt, flags=re.S)}
+    decls = {name: (d.ret, ['%s %s' % (ctext, arg) for ctext, arg, _ in d.params])
+             for name, d in _lib.DECLS.items() if name.startswith('sba_knn_')}
     assert sorted(decls) == ['sba_knn_topk', 'sba_knn_workspace_bytes']
     ret, args = decls['sba_knn_topk']
     sig = _lib.SIGNATURES['sba_knn_topk']

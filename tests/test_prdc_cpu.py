@@ -3,16 +3,12 @@ prdc_from_counts against it, the result fields, the command-line flag, the opera
 header / binding agreement.  (The kernels are tested on the GPU in tests/test_prdc_gpu.py.)"""
 import ctypes
 import json
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import prdc_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def on_a_line(xs, D=64, axis=7):
@@ -128,10 +124,8 @@ def test_prdc_operators_refuse_cpu_tensors():
 
 def test_header_declares_what_the_binding_binds():
     from sbagan import _lib
-    txt = open(os.path.join(ROOT, 'include', 'sbagan_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    decls = {m.group(2): (m.group(1), [a for a in m.group(3).split(',') if a.strip()])
-             for m in re.finditer(r'\b(int|int64_t)\s+(sba_prdc_\w+)\s*\(([^;]*?)\)\s*;', txt, flags=re.S)}
+    decls = {name: (d.ret, ['%s %s' % (ctext, arg) for ctext, arg, _ in d.params])
+             for name, d in _lib.DECLS.items() if name.startswith('sba_prdc_')}
     assert sorted(decls) == ['sba_prdc_ball_counts', 'sba_prdc_knn_radius', 'sba_prdc_workspace_bytes']
     for name in ('sba_prdc_knn_radius', 'sba_prdc_ball_counts'):
         ret, args = decls[name]

@@ -1,12 +1,8 @@
 """--replay without a GPU: the flag on the four entry points, the declared kernel, the host side of the batch slot, and
 losses.class_mask left as it was for host ids."""
-import os
-import re
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize('module', ['main', 'main_bert', 'pretrain_DAMSM', 'pretrain_DAMSM_bert'])
@@ -26,15 +22,13 @@ def test_trainer_defaults():
 
 
 def test_header_declares_batch_masks():
-    with open(os.path.join(ROOT, 'include', 'sbagan_hip.h')) as f:
-        text = f.read()
-    m = re.search(r'int\s+sba_batch_masks\s*\(([^)]*)\)\s*;', text)
-    assert m, 'sba_batch_masks is not declared'
-    args = [a.strip() for a in m.group(1).split(',')]
+    from sbagan import _lib
+    d = _lib.DECLS.get('sba_batch_masks')
+    assert d and d.ret == 'int', 'sba_batch_masks is not declared'
+    args = ['%s %s' % (ctext, arg) for ctext, arg, _ in d.params]
     assert len(args) == 7
     assert args[0].startswith('const int64_t*') and args[1].startswith('const int64_t*')
     assert args[2].startswith('uint8_t*') and args[3].startswith('uint8_t*') and args[6].startswith('void*')
-    from sbagan import _lib
     assert len(_lib.SIGNATURES['sba_batch_masks']) == 7
 
 

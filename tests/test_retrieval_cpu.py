@@ -4,8 +4,6 @@ binding, the evaluator's refusals, and the derivation of the score bound the GPU
 emulation of the kernel's summation order."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +11,6 @@ import torch
 
 import retrieval_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
 
 
@@ -196,10 +193,8 @@ def test_every_entry_point_parses_the_options(module):
 # ------------------------------------------------------------------ the binding
 def test_header_declares_what_the_binding_binds():
     from sbagan import _lib
-    txt = open(os.path.join(ROOT, 'include', 'sbagan_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    decls = {m.group(2): (m.group(1), [a for a in m.group(3).split(',') if a.strip()])
-             for m in re.finditer(r'\b(int|int64_t)\s+(sba_retrieval_\w+)\s*\(([^;]*?)\)\s*;', txt, flags=re.S)}
+    decls = {name: (d.ret, ['%s %s' % (ctext, arg) for ctext, arg, _ in d.params])
+             for name, d in _lib.DECLS.items() if name.startswith('sba_retrieval_')}
     assert sorted(decls) == ['sba_retrieval_counts', 'sba_retrieval_own_best', 'sba_retrieval_workspace_bytes']
     ret, args = decls.pop('sba_retrieval_workspace_bytes')
     fn = _lib.lib.sba_retrieval_workspace_bytes

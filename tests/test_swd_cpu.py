@@ -6,7 +6,6 @@ import ctypes
 import hashlib
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -228,10 +227,8 @@ def test_entry_points_refuse_without_a_device():
 
 def test_header_declares_what_the_binding_binds():
     from sbagan import _lib
-    txt = open(os.path.join(ROOT, 'include', 'sbagan_hip.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    decls = {m.group(2): (m.group(1), [a for a in m.group(3).split(',') if a.strip()])
-             for m in re.finditer(r'\b(int|int64_t)\s+(sba_swd_\w+)\s*\(([^;]*?)\)\s*;', txt, flags=re.S)}
+    decls = {name: (d.ret, ['%s %s' % (ctext, arg) for ctext, arg, _ in d.params])
+             for name, d in _lib.DECLS.items() if name.startswith('sba_swd_')}
     assert sorted(decls) == ['sba_swd_abs_mean', 'sba_swd_descriptors', 'sba_swd_project', 'sba_swd_sort_columns']
     for name, (ret, args) in decls.items():
         sig = _lib.SIGNATURES[name]

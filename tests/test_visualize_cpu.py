@@ -1,16 +1,12 @@
 """CPU checks of the attention-map overlays (sbagan/visualize.py): the expand operator against scipy, the declared and
 bound entry points, the command-line flag in all four entry points, the top-k order, the wrappers' refusal of CPU
 tensors."""
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import vis_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize('a,up', [(1, 16), (3, 2), (5, 4), (17, 16), (64, 2), (64, 4), (128, 2)])
@@ -35,12 +31,9 @@ def test_expand_operator_up_1_is_the_identity():
 
 def test_header_declares_and_lib_binds_both_entry_points():
     from sbagan import _lib
-    with open(os.path.join(ROOT, 'include', 'sbagan_hip.h')) as f:
-        header = f.read()
     for name, nargs in (('sba_vis_expand', 11), ('sba_vis_compose', 20)):
-        m = re.search(r'\bint %s\(([^;]*)\);' % name, header)
-        assert m, name
-        assert len(m.group(1).split(',')) == nargs == len(_lib.SIGNATURES[name])
+        assert name in _lib.DECLS and _lib.DECLS[name].ret == 'int', name
+        assert len(_lib.DECLS[name].params) == nargs == len(_lib.SIGNATURES[name])
         assert getattr(_lib.lib, name).argtypes == _lib.SIGNATURES[name]
 
 
