@@ -198,7 +198,7 @@ int embed_ln(int dtype, const int64_t* tokens, const float* word_emb, const floa
              const float* gamma, const float* beta, void* out, int B, int L, int C, int ntoken, float eps, Dropout dp,
              void* stream) {
     if (!tokens || !word_emb || !pos_emb || !type_emb || !gamma || !beta || !out) return SBA_E_ARG;
-    if (B <= 0 || L <= 0 || C % 64 != 0 || C > 1024 || ntoken <= 0) return SBA_E_ARG;
+    if (B <= 0 || L <= 0 || C <= 0 || C % 64 != 0 || C > 1024 || ntoken <= 0) return SBA_E_ARG;
     const int rows = B * L;
     SBA_DISPATCH(dtype, SBA_LAUNCH((bert_embed_ln_kernel<T, DROPOUT>), dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream,
                                    tokens, word_emb, pos_emb, type_emb, gamma, beta, (T*)out, rows, L, C, ntoken, eps, dp));
@@ -208,7 +208,7 @@ int embed_ln(int dtype, const int64_t* tokens, const float* word_emb, const floa
 template <bool DROPOUT>
 int add_ln(int dtype, const void* x, const void* residual, const float* gamma, const float* beta, void* out, int rows,
            int C, float eps, Dropout dp, void* stream) {
-    if (!x || !residual || !gamma || !beta || !out || rows <= 0 || C % 64 != 0 || C > 1024) return SBA_E_ARG;
+    if (!x || !residual || !gamma || !beta || !out || rows <= 0 || C <= 0 || C % 64 != 0 || C > 1024) return SBA_E_ARG;
     SBA_DISPATCH(dtype, SBA_LAUNCH((bert_add_ln_kernel<T, DROPOUT>), dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream,
                                    (const T*)x, (const T*)residual, gamma, beta, (T*)out, rows, C, eps, dp));
     return SBA_CHECK_LAUNCH();
