@@ -1,0 +1,61 @@
+/*
+ * sbagan_hip_ext.h -- the second header of libsbagan_hip.so's C ABI: entry points added after sbagan_hip.h was pinned
+ * by its tests (tests/test_abi_cpu.py counts its declarations).  Same conventions, same few declaration forms, read by
+ * the same parser (sbagan/abi.py: EXT_CONSTANTS, EXT_STRUCTS, EXT_DECLS; a name declared in both headers raises).
+ */
+#ifndef SBAGAN_HIP_EXT_H
+#define SBAGAN_HIP_EXT_H
+
+#include <stdint.h>
+
+#include "sbagan_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Gated Differentiable Augmentation: sba_diffaug_fwd / sba_diffaug_bwd (sbagan_hip.h) with PER-IMAGE flags, for an
+ * augmentation probability that lives in device memory (csrc/diffaug.hip, sbagan/ops.py: DiffAugGatedFn).
+ * Images, params, flags, S, workspace: as for the ungated pair.
+ * sba_diffaug_gated_fwd: image n is transformed with f_n = flags & g_n; bit b of g_n (0 color, 1 translation, 2 cutout)
+ *   is set iff gates[n][b] < *p_dev, strictly.  gates [n][4] f32: three uniforms in [0, 1), column 3 unused.  p_dev: ONE
+ *   f32 in device memory, read when the kernel runs.  A NaN p and p = 0 apply nothing, p >= 1 applies everything.
+ *   applied [n] int32 = f_n is written as well.
+ * sba_diffaug_gated_bwd: dx [n] for dout [n] with f_n = applied[n] & flags: `applied` is an INPUT, not re-derived from
+ *   gates and p, so the backward stays that of its forward whatever has happened to p since.  A value outside 0..7 is
+ *   masked with flags, never used as an address.
+ * Image n of out / dx has the same bits as sba_diffaug_fwd / _bwd with flags = f_n on that image alone (the same kernel
+ * body; the per-image sums never mix images and their partition depends on S alone); f_n = 0: a bit-exact copy.  The
+ * per-image sum is skipped, before any load, for an image whose color bit is off.  No atomics; two calls give the
+ * same bits.
+ * SBA_E_ARG before any launch, nothing written: as for the ungated pair, and on a NULL gates / p_dev / applied or one
+ * that is not 4-byte aligned. */
+int sba_diffaug_gated_fwd(const float* real, int nr, const float* fake, int nf, const float* params,
+                          const float* gates, const float* p_dev, float* out, int32_t* applied, int S, int flags,
+                          void* workspace, void* stream);
+int sba_diffaug_gated_bwd(const float* dout, int n, const float* params, const int32_t* applied, float* dx, int S,
+                          int flags, void* workspace, void* stream);
+
+/* The adaptive-augmentation controller (Karras et al., NeurIPS 2020, "Training GANs with Limited Data"; csrc/ada.hip,
+ * sbagan/diffaug.py).  State per discriminator, in device memory: p [nD] f32 (the augmentation
+ * probability), rt [nD] f32 (the last overfitting read-out r_t = E[sign(D(real) - 0.5)]), counters [nD][4] int32
+ * (pos, neg, cnt, calls).  Neither entry point synchronises with the host, uses atomics or needs a workspace; both
+ * are graph-capturable.
+ * sba_ada_count: ONE workgroup adds to counters_row (4 int32): pos += #(prob > 0.5), neg += #(prob < 0.5), cnt += n,
+ *   calls += 1, over prob [n] f32.  Exactly 0.5 and NaN count in cnt only.  Integer sums: exact in any order.  The row
+ *   must be written by this launch alone while it runs.  SBA_E_ARG unless 1 <= n <= 2^20 and both pointers are non-NULL
+ *   and 4-byte aligned.
+ * sba_ada_adjust: one launch, one thread per row.  For a row with calls >= interval:
+ *     cnt == 0: rt = 0, p unchanged;  else rt = (float)(pos - neg) / (float)cnt (one IEEE division) and
+ *     p = min(max(p', 0), p_max) with p' = p + adjust when rt > target, p - adjust when rt < target, p otherwise;
+ *   then the row's four counters are zeroed.  Rows below the interval are untouched.
+ *   SBA_E_ARG unless 1 <= nD <= 8, 1 <= interval <= 1024, 0 <= p_max <= 1, adjust >= 0 and finite, target not NaN, and
+ *   all pointers non-NULL and 4-byte aligned. */
+int sba_ada_count(const float* prob, int n, int32_t* counters_row, void* stream);
+int sba_ada_adjust(float* p, float* rt, int32_t* counters, int nD, int interval, float target, float adjust,
+                   float p_max, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SBAGAN_HIP_EXT_H */

@@ -11,7 +11,12 @@
 // block p of the sum kernel adds elements [4096 p, 4096 (p + 1)) of the image -- the partition depends on S alone --
 // thread by thread, then by the xor butterfly of the wave, then over the four waves in index order, and stores ONE f64;
 // the main kernel adds the partials of its image in index order.  No atomics; two calls give the same bits.
+//
+// The gated entry points (sba_diffaug_gated_fwd / _bwd in sbagan_hip_ext.h) are the SAME kernels with
+// per-image flags: every block resolves its image's flags once (da_image_flags) and branches on them block-uniformly.
+// An image whose color bit is off leaves the sum kernel before any load; with all bits off the main kernel is a copy.
 #include "common.h"
+#include "sbagan_hip_ext.h"
 
 namespace {
 
@@ -57,6 +62,24 @@ __device__ __forceinline__ bool da_live(const DaMaps& m, int S, int i, int j) {
     return in && !cut;
 }
 
+// The flags of image n, once per block.  gates == nullptr && applied == nullptr: the ungated entry points, `flags` as
+// given.  applied: the backward of a gated forward, what that forward recorded (masked: never an address).  gates: bit b
+// is on iff gates[n][b] < *p_dev -- false for every gate when p is NaN or 0, true for every gate in [0, 1) when p >= 1.
+struct DaGate {
+    const float* gates;
+    const float* p_dev;
+    const int32_t* applied;
+};
+
+__device__ __forceinline__ int da_image_flags(int flags, const DaGate& g, int n) {
+    if (g.applied) return flags & g.applied[n];
+    if (!g.gates) return flags;
+    const float p = *g.p_dev;
+    const float* row = g.gates + (size_t)n * 4;
+    const int on = (row[0] < p ? 1 : 0) | (row[1] < p ? 2 : 0) | (row[2] < p ? 4 : 0);
+    return flags & on;
+}
+
 __device__ __forceinline__ const float* da_image(const float* a, int na, const float* b, int n, size_t img) {
     return n < na ? a + (size_t)n * img : b + (size_t)(n - na) * img;
 }
@@ -65,8 +88,10 @@ __device__ __forceinline__ const float* da_image(const float* a, int na, const f
 template <bool BWD>
 __global__ __launch_bounds__(DA_THREADS) void diffaug_sum_kernel(
     const float* __restrict__ a, int na, const float* __restrict__ b, const float* __restrict__ params,
-    double* __restrict__ partials, int S, int flags, int shift, int cut, int P) {
+    double* __restrict__ partials, int S, int flags, int shift, int cut, int P, DaGate gate) {
     const int n = blockIdx.y, p = blockIdx.x;
+    flags = da_image_flags(flags, gate, n);
+    if (!(flags & 1)) return;               // no color on this image: nobody reads its partials
     const int plane = S * S, total4 = 3 * plane / 4;
     const float* img = da_image(a, na, b, n, (size_t)3 * plane);
     DaMaps m = {0, 0, 0, 0, 0, 0};
@@ -106,9 +131,12 @@ __global__ __launch_bounds__(DA_THREADS) void diffaug_sum_kernel(
 template <bool BWD>
 __global__ __launch_bounds__(DA_THREADS) void diffaug_main_kernel(
     const float* __restrict__ a, int na, const float* __restrict__ b, const float* __restrict__ params,
-    float* __restrict__ out, int S, int flags, int shift, int cut, const double* __restrict__ partials, int P) {
+    float* __restrict__ out, int S, int flags, int shift, int cut, const double* __restrict__ partials, int P,
+    DaGate gate, int32_t* __restrict__ applied_out) {
     const int n = blockIdx.y;
     const int plane = S * S;
+    flags = da_image_flags(flags, gate, n);
+    if (applied_out && blockIdx.x == 0 && threadIdx.x == 0) applied_out[n] = flags;
     const bool color = flags & 1;
     __shared__ float sh_mean;
     if (color) {
@@ -201,17 +229,17 @@ int da_check(int n, int S, int flags, const void* params, const void* out, const
 
 template <bool BWD>
 int da_launch(const float* a, int na, const float* b, int n, const float* params, float* out, int S, int flags,
-              void* workspace, hipStream_t st) {
+              void* workspace, hipStream_t st, DaGate gate = {nullptr, nullptr, nullptr}, int32_t* applied_out = nullptr) {
     const int shift = (int)(S * 0.125 + 0.5), cut = (int)(S * 0.5 + 0.5);
     const int P = da_parts(S);
     double* partials = (double*)workspace;
     if (flags & 1) {
         SBA_LAUNCH((diffaug_sum_kernel<BWD>), dim3(P, n), dim3(DA_THREADS), 0, st, a, na, b, params, partials, S, flags,
-                   shift, cut, P);
+                   shift, cut, P, gate);
         if (SBA_CHECK_LAUNCH() != SBA_OK) return SBA_E_LAUNCH;
     }
     SBA_LAUNCH((diffaug_main_kernel<BWD>), dim3(cdiv(S * S / 4, DA_THREADS), n), dim3(DA_THREADS), 0, st, a, na, b,
-               params, out, S, flags, shift, cut, partials, P);
+               params, out, S, flags, shift, cut, partials, P, gate, applied_out);
     return SBA_CHECK_LAUNCH();
 }
 
@@ -235,4 +263,25 @@ extern "C" int sba_diffaug_bwd(const float* dout, int n, const float* params, fl
     if (da_check(n, S, flags, params, dx, workspace) != SBA_OK) return SBA_E_ARG;
     if (!dout || da_misaligned(dout)) return SBA_E_ARG;
     return da_launch<true>(dout, n, nullptr, n, params, dx, S, flags, workspace, (hipStream_t)stream);
+}
+
+static inline bool da_bad_word(const void* p) { return !p || ((uintptr_t)p & 3) != 0; }
+
+extern "C" int sba_diffaug_gated_fwd(const float* real, int nr, const float* fake, int nf, const float* params,
+                                     const float* gates, const float* p_dev, float* out, int32_t* applied, int S,
+                                     int flags, void* workspace, void* stream) {
+    if (nr < 0 || nf < 0 || nr > 65535 || nf > 65535) return SBA_E_ARG;
+    if (da_check(nr + nf, S, flags, params, out, workspace) != SBA_OK) return SBA_E_ARG;
+    if ((nr > 0 && (!real || da_misaligned(real))) || (nf > 0 && (!fake || da_misaligned(fake)))) return SBA_E_ARG;
+    if (da_bad_word(gates) || da_bad_word(p_dev) || da_bad_word(applied)) return SBA_E_ARG;
+    return da_launch<false>(real, nr, fake, nr + nf, params, out, S, flags, workspace, (hipStream_t)stream,
+                            DaGate{gates, p_dev, nullptr}, applied);
+}
+
+extern "C" int sba_diffaug_gated_bwd(const float* dout, int n, const float* params, const int32_t* applied, float* dx,
+                                     int S, int flags, void* workspace, void* stream) {
+    if (da_check(n, S, flags, params, dx, workspace) != SBA_OK) return SBA_E_ARG;
+    if (!dout || da_misaligned(dout) || da_bad_word(applied)) return SBA_E_ARG;
+    return da_launch<true>(dout, n, nullptr, n, params, dx, S, flags, workspace, (hipStream_t)stream,
+                           DaGate{nullptr, nullptr, applied}, nullptr);
 }

@@ -93,6 +93,13 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo.diffaug = getattr(args, 'diffaug', '') if training else ''
     if getattr(args, 'diffaug', '') and not training:
         print('--diffaug is ignored outside training')
+    ada_given = getattr(args, 'ada', None) is not None or getattr(args, 'diffaug_p', None) is not None
+    if training:
+        algo.ada, algo.diffaug_p = getattr(args, 'ada', None), getattr(args, 'diffaug_p', None)
+        algo.ada_kimg, algo.ada_interval = getattr(args, 'ada_kimg', 500.0), getattr(args, 'ada_interval', 4)
+        algo.ada_pmax = getattr(args, 'ada_pmax', 1.0)
+    elif ada_given:
+        print('--ada / --diffaug_p are ignored outside training')
     start_t = time.time()
     if training:
         algo.train()

@@ -4,6 +4,7 @@
     [--kid]  [--kid_subsets N]  [--kid_subset_size M]  [--ms_ssim N]  [--swd N]
     [--nearest K]  [--nearest_stats PATH]  [--nearest_show M]
     [--device_data]  [--device_data_gb G]  [--replay]  [--diffaug POLICY]
+    [--diffaug_p P]  [--ada TARGET]  [--ada_kimg K]  [--ada_interval N]  [--ada_pmax P]
     [--retrieval E]  [--retrieval_only: DAMSM pre-training]
     [--bert_dir DIR: the BERT entry points]
 
@@ -59,6 +60,17 @@ def _diffaug(text):
     return ','.join(names)
 
 
+def _ranged_float(metavar, lo, hi, what, open_ends=False):
+    """the argparse type of a float in [lo, hi] ((lo, hi) with open_ends; hi None: unbounded above)"""
+    def parse(text):
+        v = float(text)
+        inside = (lo < v if open_ends else lo <= v) and (hi is None or (v < hi if open_ends else v <= hi))
+        if not inside:          # (a NaN fails both comparisons)
+            raise argparse.ArgumentTypeError('%s must be %s' % (metavar, what))
+        return v
+    return parse
+
+
 def options(what, default_cfg, argv=None, bert=False):
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
@@ -99,6 +111,31 @@ def options(what, default_cfg, argv=None, bert=False):
                          'POLICY: a comma-separated subset of color,translation,cutout; empty = off.  The DAMSM terms, '
                          'sampling, the image dumps and checkpoints see un-augmented images.  Single GPU only.  Ignored '
                          'outside training and by the DAMSM pre-training entry points')
+    ap.add_argument('--diffaug_p', dest='diffaug_p', default=None, metavar='P',
+                    type=_ranged_float('P', 0.0, 1.0, 'a probability in [0, 1]'),
+                    help='with --diffaug: apply each part of the policy to an image with probability P instead of '
+                         'always (the gated HIP kernels; P lives in device memory, one value per discriminator).  '
+                         'Without --ada P stays fixed -- the fixed-p ablation of Karras et al. -- and no controller '
+                         'launch is issued; with --ada it is the initial value (default then: 0).  Default: the '
+                         'ungated kernels')
+    ap.add_argument('--ada', dest='ada', default=None, metavar='TARGET',
+                    type=_ranged_float('TARGET', -1.0, 1.0, 'in (-1, 1)', open_ends=True),
+                    help='with --diffaug: adaptive augmentation strength (Karras et al., NeurIPS 2020, "Training GANs '
+                         'with Limited Data").  Per discriminator, the overfitting read-out r_t = E[sign(D(real))] is '
+                         'counted on the device behind every update, and every --ada_interval iterations p moves one '
+                         'step towards r_t = TARGET (0.6 in the paper).  Counting, the controller and p itself stay '
+                         'on the device, so --replay records them with the step.  Every 100 iterations one line shows '
+                         'p and r_t per discriminator; the same goes to Model/ada.jsonl, the state to '
+                         'Model/ada_state.pth (restored on resume).  Default: off')
+    ap.add_argument('--ada_kimg', dest='ada_kimg', default=500.0, metavar='K',
+                    type=_ranged_float('K', 0.0, None, 'positive', open_ends=True),
+                    help='with --ada: p can travel from 0 to 1 in K thousand real images (default 500)')
+    ap.add_argument('--ada_interval', dest='ada_interval', default=4, metavar='N',
+                    type=_ranged_int('N', 1, 1024, 'an interval of 1 to 1024 iterations'),
+                    help='with --ada: iterations between two controller updates (default 4)')
+    ap.add_argument('--ada_pmax', dest='ada_pmax', default=1.0, metavar='P',
+                    type=_ranged_float('P', 0.0, 1.0, 'a probability in [0, 1]'),
+                    help='with --ada: the largest p the controller sets (default 1.0)')
     ap.add_argument('--retrieval', dest='retrieval', default=0, metavar='E',
                     type=_ranged_int('E', 0, None, '0 (off) or an interval in epochs'),
                     help='DAMSM pre-training: after the validation pass of every E-th epoch and of the last one, rank '
@@ -113,7 +150,13 @@ def options(what, default_cfg, argv=None, bert=False):
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    for flag in ('ada', 'diffaug_p'):
+        if getattr(args, flag) is not None and not args.diffaug:
+            ap.error('--%s needs a non-empty --diffaug POLICY' % flag)
+    if args.ada is not None and args.diffaug_p is not None and args.diffaug_p > args.ada_pmax:
+        ap.error('--diffaug_p %g is above --ada_pmax %g' % (args.diffaug_p, args.ada_pmax))
+    return args
 
 
 def configure(args):

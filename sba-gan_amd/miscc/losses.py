@@ -126,8 +126,17 @@ def g_term_heads(n, uncond):
     return (H(0, n, 0, 1., 1., 0),)
 
 
+def _augmented(real, fake, augment):
+    """ops.diffaug for an `augment` argument (rows, flags), ops.diffaug_gated for (rows, flags, gates, p_dev): the
+    adaptive and fixed-p modes of sbagan.diffaug.DiffAugment, whose probability the kernel reads from device memory"""
+    if len(augment) == 2:
+        return ops.diffaug(real, fake, augment[0], augment[1])
+    rows, flags, gates, p_dev = augment
+    return ops.diffaug_gated(real, fake, rows, gates, p_dev, flags)
+
+
 def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake_labels, real_features=None,
-                       augment=None):
+                       augment=None, count_sink=None):
     """losses.py:136-161: the real and the fake.detach() trunk pass, five heads,
     errD = (real + cond_real)/2 + (fake + cond_fake + cond_wrong)/3.
 
@@ -142,7 +151,11 @@ def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake
 
     augment (optional, (rows, flags): f32 uniforms [2n][8] -- n rows for the real images, then n for the fake ones -- and
     the policy bits of sbagan.diffaug): Differentiable Augmentation of both halves.  ops.diffaug writes the augmented
-    [real | fake] batch in one pass, in place of the concatenation; not available with real_features."""
+    [real | fake] batch in one pass, in place of the concatenation; not available with real_features.  With
+    (rows, flags, gates [2n][4], p_dev [1]) the gated kernels run instead (_augmented).
+
+    count_sink (optional): handed to ops.d_heads -- the signs of the real rows' probabilities are counted on the device
+    (the overfitting read-out of --ada)."""
     if augment is not None and real_features is not None:
         raise ValueError('discriminator_loss: augment does not go with real_features (the two-pass layout)')
     if real_features is not None:
@@ -153,12 +166,13 @@ def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake
         raise ValueError('discriminator_loss: real %s and fake %s differ in shape'
                          % (tuple(real.shape), tuple(fake.shape)))
     if augment is not None:
-        feats = ops.diffaug(real, fake, augment[0], augment[1])
+        feats = _augmented(real, fake, augment)
     else:
         feats = torch.cat((real, fake), 0)
     if real_features is None:
         feats = netD(feats, groups=2)
-    return ops.d_heads(netD, feats, conditions, d_term_heads(real.size(0), netD.UNCOND_DNET is not None))
+    return ops.d_heads(netD, feats, conditions, d_term_heads(real.size(0), netD.UNCOND_DNET is not None),
+                       sink=count_sink)
 
 
 def damsm_image_terms(image_encoder, fake_img, words_embs, sent_emb, match_labels, cap_lens, class_ids):
@@ -211,7 +225,7 @@ def generator_d_term(netD, fake_img, sent_emb, augment=None):
     augment (optional, (rows [n][8], flags)): the discriminator sees the augmented image (ops.diffaug); the returned
     gradient is with respect to the image itself, through the augmentation."""
     leaf = fake_img.detach().requires_grad_(True)
-    seen = leaf if augment is None else ops.diffaug(None, leaf, augment[0], augment[1])
+    seen = leaf if augment is None else _augmented(None, leaf, augment)
     g_loss = _g_term(netD, netD(seen), sent_emb)
     (grad,) = torch.autograd.grad(g_loss, leaf)
     return g_loss.detach(), grad
@@ -255,7 +269,7 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
             with branch(i):
                 seen = fake_imgs[i]
                 if augment is not None:
-                    seen = ops.diffaug(None, seen, augment[i][0], augment[i][1])
+                    seen = _augmented(None, seen, augment[i])
                 g_loss = _g_term(netsD[i], netsD[i](seen), sent_emb)
         terms.append(g_loss)
         logs['g_loss%d' % i] = g_loss.detach()

@@ -13,7 +13,7 @@ import torch  # noqa: F401  -- FIRST: PyTorch-ROCm brings its own libamdhip64; i
 #                     not own torch's streams (every launch then fails)
 from ctypes import POINTER, byref, c_float, c_int, c_int64, c_uint64, c_void_p
 
-from .abi import CONSTANTS, DECLS, STRUCTS
+from .abi import CONSTANTS, DECLS, EXT_DECLS, STRUCTS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SBA_LIB_PATH') or os.path.join(os.path.dirname(_HERE), 'csrc', 'libsbagan_hip.so')
@@ -40,6 +40,20 @@ for _name, _decl in DECLS.items():
     _fn.restype = _decl.restype
     if _decl.restype is c_int:
         SIGNATURES[_name] = _args
+
+EXT_SIGNATURES = {}     # the same for the second header (include/sbagan_hip_ext.h): its tables stay apart from the core's
+for _name, _decl in EXT_DECLS.items():
+    _fn = getattr(lib, _name)          # AttributeError if the .so lacks a declared symbol
+    _fn.argtypes = _args = [_ctype for _, _, _ctype in _decl.params]
+    _fn.restype = _decl.restype
+    if _decl.restype is c_int:
+        EXT_SIGNATURES[_name] = _args
+
+
+def signature(name):
+    """argtypes of an int-returning entry point of either header, or None"""
+    return SIGNATURES.get(name) or EXT_SIGNATURES.get(name)
+
 
 _ERR = {CONSTANTS['SBA_E_ARG']: 'SBA_E_ARG (unsupported shape/alignment/enum)',
         CONSTANTS['SBA_E_LAUNCH']: 'SBA_E_LAUNCH (HIP launch failed)',

@@ -12,6 +12,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
                       'include', 'sbagan_hip.h')
+EXT_HEADER = os.path.join(os.path.dirname(HEADER), 'sbagan_hip_ext.h')
 
 # The type map.  Scalars by name; `int*` and `void**` are host out-parameters; a pointer to one of HOST_STRUCTS is a
 # struct the host fills in; every other pointer is an address (device memory, a stream, a handle): c_void_p.
@@ -92,5 +93,19 @@ def parse(text, host_structs=HOST_STRUCTS):
     return constants, structs, decls
 
 
+def disjoint(core, ext):
+    """refuse a name that both headers declare (constants, structs and entry points share one namespace in C)"""
+    names = [set().union(*tables) for tables in (core, ext)]
+    both = sorted(names[0] & names[1])
+    if both:
+        raise ValueError('%s: declared in both headers' % ', '.join(both))
+
+
 with open(HEADER) as _f:
     CONSTANTS, STRUCTS, DECLS = parse(_f.read())
+
+# The second header: entry points added since the first one's declaration count was pinned by its tests.  Parsed the
+# same way into tables of its own; the three above stay those of sbagan_hip.h alone.
+with open(EXT_HEADER) as _f:
+    EXT_CONSTANTS, EXT_STRUCTS, EXT_DECLS = parse(_f.read())
+disjoint((CONSTANTS, STRUCTS, DECLS), (EXT_CONSTANTS, EXT_STRUCTS, EXT_DECLS))

@@ -11,6 +11,7 @@ Parameter gradients are ACCUMULATED IN PLACE into `param.grad` by the kernels
 trainer.py:269-297); the autograd Functions therefore return None for
 parameters.
 """
+import collections
 import ctypes
 import os
 from collections import namedtuple
@@ -1484,7 +1485,7 @@ class DHeadsFn(torch.autograd.Function):
     its rows of d feats."""
 
     @staticmethod
-    def forward(ctx, feats, cond, netD, heads, *params):
+    def forward(ctx, feats, cond, netD, heads, sink, *params):
         feats = as_act(feats)
         dev = feats.device
         dt = _dt(feats)
@@ -1532,6 +1533,17 @@ class DHeadsFn(torch.autograd.Function):
         dprob = torch.empty_like(prob)
         call('sba_bce_multi', _p(prob), _p(meta[0]), _p(meta[1]), _p(meta[2]), len(heads), _p(loss), _p(dprob),
              _stream())
+        if sink is not None:
+            # the overfitting read-out: the probabilities of the heads whose target is 1, counted right
+            # behind the loss on this stream; segments next to each other are one slice of prob, one launch
+            runs = []
+            for seg in range(len(sizes)):
+                if targets[seg] == 1. and sizes[seg] > 0:
+                    if runs and runs[-1][1] == offs[seg]:
+                        runs[-1][1] = offs[seg + 1]
+                    else:
+                        runs.append([offs[seg], offs[seg + 1]])
+            sink([prob[a:b] for a, b in runs])
         ctx.netD, ctx.heads, ctx.offs, ctx.tape, ctx.groups = netD, heads, offs, tape, groups
         ctx.has_cond = cond is not None
         ctx.cond_shape = None if cond is None else tuple(cond.shape)
@@ -1549,7 +1561,7 @@ class DHeadsFn(torch.autograd.Function):
         d = dprob * g
         need_feats = ctx.needs_input_grad[0]
         need_cond = ctx.has_cond and ctx.needs_input_grad[1]
-        need_p = any(ctx.needs_input_grad[4:])
+        need_p = any(ctx.needs_input_grad[5:])
         dfeats = torch.empty_like(feats) if need_feats else None
         dcond = torch.zeros(ctx.cond_shape, dtype=torch.float32, device=feats.device) if need_cond else None
         # (a term without a gradient to feats may hold any subset of the heads: nothing to cover)
@@ -1592,12 +1604,14 @@ class DHeadsFn(torch.autograd.Function):
                     dh, acc = dh_rows(j)
                     call('sba_cond_cat_bwd', dt, _p(dxin[grp.off[j]:grp.off[j] + rows]), _p(dh),
                          _p(dcond[c0:c0 + rows]) if need_cond else None, rows, C, E, acc, _stream())
-        return (dfeats, dcond, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
+        return (dfeats, dcond, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 5)
 
 
-def d_heads(netD, feats, cond, heads):
+def d_heads(netD, feats, cond, heads, sink=None):
     """DHeadsFn with the parameters of netD's heads passed as autograd inputs (their gradients go to the flat
-    gradient buffers like every other layer's)."""
+    gradient buffers like every other layer's).  sink (optional, sbagan.diffaug.DiffAugment.count_sink): called in the
+    forward with the slices of the probability vector that belong to heads of target 1 -- it counts their signs on the
+    device (ops.ada_count); None: nothing more is launched."""
     params = []
     if netD.COND_DNET is not None:
         c = netD.COND_DNET
@@ -1608,7 +1622,7 @@ def d_heads(netD, feats, cond, heads):
     if netD.UNCOND_DNET is not None:
         u = netD.UNCOND_DNET
         params += [u.outlogits[0].weight, u.outlogits[0].bias]
-    return DHeadsFn.apply(feats, cond, netD, tuple(Head(*h) for h in heads), *params)
+    return DHeadsFn.apply(feats, cond, netD, tuple(Head(*h) for h in heads), sink, *params)
 
 
 class KLFn(torch.autograd.Function):
@@ -2754,3 +2768,85 @@ def diffaug(real, fake, params, flags):
     """The augmented [real | fake] batch of one discriminator pass (real = None: the fake images alone).  params: f32
     [(nr + nf)][8] uniforms in [0, 1), one row per image (sbagan.diffaug.DiffAugment); flags: DIFFAUG_* bits."""
     return DiffAugFn.apply(fake.float().contiguous(), None if real is None else real.float().contiguous(), params, flags)
+
+
+class DiffAugGatedFn(torch.autograd.Function):
+    """DiffAugFn with per-image flags (sba_diffaug_gated_fwd): image n gets the parts of `flags` whose gate
+    gates[n][b] is below the probability p_dev holds WHEN THE KERNEL RUNS.  The forward records what it applied
+    (ctx.applied, int32 [n]); the backward reads that, not p, so it is the backward of its own forward whatever the
+    controller has done in between.  As with DiffAugFn, a `fake` that needs no gradient launches nothing backward."""
+
+    @staticmethod
+    def forward(ctx, fake, real, params, gates, p_dev, flags):
+        _need_gpu(fake)
+        nf, C, S, S2 = fake.shape
+        nr = 0 if real is None else real.size(0)
+        dev = fake.device
+        if C != 3 or S != S2 or fake.dtype != torch.float32 or not fake.is_contiguous():
+            raise ValueError('diffaug_gated: fake must be contiguous float32 [n][3][S][S], got %s %s'
+                             % (fake.dtype, tuple(fake.shape)))
+        if real is not None and (real.dtype != torch.float32 or not real.is_contiguous() or real.device != dev
+                                 or tuple(real.shape[1:]) != (3, S, S)):
+            raise ValueError('diffaug_gated: real must be contiguous float32 [n][3][%d][%d] on %s' % (S, S, dev))
+        for name, t, shape in (('params', params, (nr + nf, 8)), ('gates', gates, (nr + nf, 4)), ('p_dev', p_dev, (1,))):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError('diffaug_gated: %s must be contiguous float32 %s on %s' % (name, list(shape), dev))
+        flags = int(flags)
+        # both workspaces here, outside any later graph capture of the backward
+        ws = _diffaug_workspace(nr + nf, S, flags, dev)
+        ctx.ws_bwd = _diffaug_workspace(nf, S, flags, dev) if ctx.needs_input_grad[0] else None
+        out = torch.empty((nr + nf, 3, S, S), dtype=torch.float32, device=dev)
+        applied = torch.empty(nr + nf, dtype=torch.int32, device=dev)
+        call('sba_diffaug_gated_fwd', _p(real), nr, _p(fake), nf, _p(params), _p(gates), _p(p_dev), _p(out), _p(applied),
+             S, flags, _p(ws), _stream())
+        ctx.save_for_backward(params, applied)
+        ctx.applied = applied
+        ctx.geom = (nr, nf, S, flags)
+        DiffAugGatedFn.last_applied = applied
+        DiffAugGatedFn.applied_log.append(applied)
+        return out
+
+    last_applied = None                             # `applied` of the most recent forward, and of the last 16 (tests,
+    applied_log = collections.deque(maxlen=16)      # diagnostics; under --replay: of the recording, refilled by every replay)
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        params, applied = ctx.saved_tensors
+        nr, nf, S, flags = ctx.geom
+        dout = dout.float().contiguous()[nr:]            # (a contiguous batch: its tail is contiguous and 16-byte aligned)
+        dx = torch.empty((nf, 3, S, S), dtype=torch.float32, device=dout.device)
+        call('sba_diffaug_gated_bwd', _p(dout), nf, _p(params[nr:]), _p(applied[nr:]), _p(dx), S, flags, _p(ctx.ws_bwd),
+             _stream())
+        return dx, None, None, None, None, None
+
+
+def diffaug_gated(real, fake, params, gates, p_dev, flags):
+    """ops.diffaug with each of the three parts applied to image n only where gates[n][part] < p_dev[0] (f32 [1] in
+    device memory, read by the kernel): gates f32 [(nr + nf)][4] uniforms in [0, 1) (sbagan.diffaug.DiffAugment)."""
+    return DiffAugGatedFn.apply(fake.float().contiguous(), None if real is None else real.float().contiguous(), params,
+                                gates, p_dev, flags)
+
+
+def ada_count(prob, counters_row):
+    """counters_row (int32 [4]: pos, neg, cnt, calls) += the signs of prob - 0.5 over the contiguous f32 vector `prob`
+    (sba_ada_count: one tiny launch on the current stream, no host sync)"""
+    if prob.dtype != torch.float32 or prob.dim() != 1 or not prob.is_contiguous() or prob.numel() < 1:
+        raise ValueError('ada_count: prob must be a contiguous float32 vector')
+    if counters_row.dtype != torch.int32 or tuple(counters_row.shape) != (4,) or not counters_row.is_contiguous() \
+            or counters_row.device != prob.device:
+        raise ValueError('ada_count: counters_row must be contiguous int32 [4] on %s' % prob.device)
+    call('sba_ada_count', _p(prob), prob.numel(), _p(counters_row), _stream())
+
+
+def ada_adjust(p, rt, counters, interval, target, adjust, p_max):
+    """one controller update of every row whose `calls` has reached `interval` (sba_ada_adjust): p [nD], rt [nD] f32,
+    counters int32 [nD][4], all in device memory; one launch on the current stream, no host sync"""
+    nD = p.numel()
+    for name, t, dtype, shape in (('p', p, torch.float32, (nD,)), ('rt', rt, torch.float32, (nD,)),
+                                  ('counters', counters, torch.int32, (nD, 4))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != p.device:
+            raise ValueError('ada_adjust: %s must be contiguous %s %s on %s' % (name, dtype, list(shape), p.device))
+    call('sba_ada_adjust', _p(p), _p(rt), _p(counters), nD, int(interval), float(target), float(adjust), float(p_max),
+         _stream())

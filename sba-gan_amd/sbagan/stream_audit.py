@@ -78,7 +78,7 @@ class StreamAudit(object):
             self._busy = False
 
     def _on_call(self, name, args):
-        sig = _lib.SIGNATURES.get(name)
+        sig = _lib.signature(name)
         if not sig or sig[-1] is not ctypes.c_void_p or name.startswith(('sba_replay', 'sba_set_', 'sba_det_')):
             return
         stream = args[-1] or 0

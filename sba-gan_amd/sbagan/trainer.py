@@ -413,7 +413,8 @@ class GANStep(object):
             netD.clear_cuts(record=split)
         self._check_augment(self.distributed)        # (both can be set after construction)
         errD = discriminator_loss(netD, imgs[i], fake_imgs[i], sent_emb, self.real_labels, self.fake_labels,
-                                  real_features=rf, augment=None if self.augment is None else self.augment.d_arg(i))
+                                  real_features=rf, augment=None if self.augment is None else self.augment.d_arg(i),
+                                  count_sink=None if self.augment is None else self.augment.count_sink(i))
         self._out['errD%d' % i] = errD.detach()
         cuts = list(netD._cuts)
         netD.clear_cuts(record=False)
@@ -563,6 +564,10 @@ class GANStep(object):
 
     def phase_b_opt(self):
         self.optG.step(1.0 / self.world)
+        if self.augment is not None:
+            # --ada: the controller's one launch, behind the step's last join -- every augmentation launch of this step
+            # has read the p it started with; the next step sees the new one (a no-op without a target)
+            self.augment.adjust()
         self._mark('g_adam')
         ops.ARENA.end()
         ops.SIDE_WGRAD = False

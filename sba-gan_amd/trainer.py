@@ -17,6 +17,7 @@ What differs, none of it in results:
     error and fails; pass `allow_random_encoders=True` to train against randomly initialised frozen encoders
     (synthetic-data runs and tests).
 """
+import json
 import os
 import time
 
@@ -127,7 +128,11 @@ class condGANTrainer(object):
             # --diffaug: every image a discriminator sees goes through the augmentation; its uniforms are
             # drawn beside the noise, by the loops below and by the recorded step's own draws
             from sbagan.diffaug import DiffAugment
-            self.gan.augment = DiffAugment(self.diffaug, self.batch_size, len(netsD), self.gan.device)
+            self.gan.augment = DiffAugment(self.diffaug, self.batch_size, len(netsD), self.gan.device,
+                                           p0=self.diffaug_p, target=self.ada, kimg=self.ada_kimg,
+                                           interval=self.ada_interval, p_max=self.ada_pmax)
+            if self.gan.augment.adaptive:
+                self._restore_ada(self.gan.augment)
         return self.gan.optG, self.gan.optD
 
     def prepare_labels(self):
@@ -141,7 +146,28 @@ class condGANTrainer(object):
         load_params(netG, backup_para)
         for i, netD in enumerate(netsD):
             torch.save(netD.state_dict(), '%s/netD%d.pth' % (self.model_dir, i))
+        augment = getattr(getattr(self, 'gan', None), 'augment', None)
+        if augment is not None and augment.adaptive:        # --ada: the controller's state beside the discriminators
+            torch.save(augment.state_dict(), '%s/ada_state.pth' % self.model_dir)
         print('Save G/Ds models.')
+
+    def _restore_ada(self, augment):
+        """on resume (TRAIN.NET_G set): the controller state saved beside the generator checkpoint, if there is one"""
+        if cfg.TRAIN.NET_G == '':
+            return
+        path = os.path.join(os.path.dirname(cfg.TRAIN.NET_G), 'ada_state.pth')
+        if os.path.isfile(path):
+            augment.load_state_dict(torch.load(path, map_location='cpu'))
+            print('Load ada state from: ', path)
+        else:
+            print('no ada_state.pth beside %s: p restarts from its initial value %g' % (cfg.TRAIN.NET_G, augment.p0))
+
+    def _report_ada(self, augment, gen_iterations):
+        """the --ada line of the interval log and its JSON twin in Model/ada.jsonl: ONE read-back of p and r_t"""
+        p, rt = augment.report()
+        print('ada p: ' + ' '.join('%.3f' % v for v in p) + ' r_t: ' + ' '.join('%.2f' % v for v in rt))
+        with open(os.path.join(self.model_dir, 'ada.jsonl'), 'a') as f:
+            f.write(json.dumps({'iteration': gen_iterations, 'p': p, 'r_t': rt}) + '\n')
 
     def set_requires_grad_value(self, models_list, brequires):
         for m in models_list:
@@ -209,6 +235,10 @@ class condGANTrainer(object):
     replay = False              # --replay: train() runs every batch through ONE recording of the step
     replay_eager = False        # with replay: the same loop over the static batch slot, the step launched eagerly
     diffaug = ''                # --diffaug POLICY: Differentiable Augmentation in front of the discriminators ('' = off)
+    diffaug_p = None            # --diffaug_p P: each part with probability P (the gated kernels); None = always
+    ada = None                  # --ada TARGET: p follows the overfitting read-out r_t on the device
+    ada_kimg, ada_interval, ada_pmax = 500.0, 4, 1.0
+    log_interval = 100          # iterations between two loss lines
     average_interval = 1000     # iterations between the 'average' (EMA generator) image dumps
 
     def _replay_step(self, text_encoder, noise):
@@ -270,12 +300,14 @@ class condGANTrainer(object):
                     out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise)
                 step += 1
                 gen_iterations += 1
-                if gen_iterations % 100 == 0:
+                if gen_iterations % self.log_interval == 0:
                     v = {k: float(t) for k, t in out.items()}
                     nD = len(netsD)
                     print(' '.join('errD%d: %.2f' % (i, v['errD%d' % i]) for i in range(nD)) + '\n' +
                           ' '.join('g_loss%d: %.2f' % (i, v['g_loss%d' % i]) for i in range(nD)) +
                           ' w_loss: %.2f s_loss: %.2f kl_loss: %.2f' % (v['w_loss'], v['s_loss'], v['kl_loss']))
+                    if gan.augment is not None and gan.augment.adaptive:
+                        self._report_ada(gan.augment, gen_iterations)
                 if gen_iterations % self.average_interval == 0:
                     gan.finish()        # (data-parallel: a pending generator update is applied before it is read)
                     backup_para = copy_G_params(netG)
