@@ -55,6 +55,40 @@ int sba_ada_count(const float* prob, int n, int32_t* counters_row, void* stream)
 int sba_ada_adjust(float* p, float* rt, int32_t* counters, int nD, int interval, float target, float adjust,
                    float p_max, void* stream);
 
+/* Geometric augmentation: x-flip, 90-degree rotation, isotropic scaling and rotation of the images a discriminator sees
+ * (Karras et al., NeurIPS 2020; csrc/geoaug.hip, sbagan/geoaug.py, sbagan/ops.py: GeoAugFn).  Parts, as
+ * bits of their OWN namespace (not sba_diffaug_fwd's): 1 flip, 2 rot90, 4 scale, 8 rotate.  Per image the parts compose
+ * into one matrix M [m00 m01 m10 m11] about the centre c = (S - 1) / 2, pixel centres on the integers, (x, y) columns:
+ *     src - c = M (dst - c),   M = F . Q^k . R(theta) / s,
+ *     F = [[-1, 0], [0, 1]] if flipped else I,  Q = [[0, -1], [1, 0]],  R(t) = [[cos t, -sin t], [sin t, cos t]];
+ * a part that is off contributes the identity.  All parts fix the centre: M does not depend on S.
+ * Sampling is bilinear with zero padding: out[ch, d] = sum over pixels q of x[ch, q] hat(sx - qx) hat(sy - qy),
+ * hat(t) = max(0, 1 - |t|).
+ * sba_geoaug_prepare: ONE launch, one thread per row, for N rows: uniforms [N][8] f32 in [0, 1) -> mats [N][4] f32 and
+ *   applied [N] int32 (the parts that were on).  flip: on a row whose part is on, F is drawn: flipped iff u0 >= 0.5.
+ *   rot90: k = min(int(4 u1), 3).  scale: s = 2^(0.2 z), z = sqrt(-2 ln(1 - u2)) cos(2 pi u3) clamped to [-3, 3], so
+ *   2^-0.6 <= s <= 2^0.6.  rotate: theta = pi (2 u4 - 1).  u5..u7 unused.
+ *   Part b of row r is on iff bit b of `flags` is set and (gates == NULL or gates[r][b] < p_dev[r / rows_per_p],
+ *   strictly): nothing when p is NaN or 0, everything when p >= 1.  gates [N][4] f32 uniforms; p_dev f32 in device memory,
+ *   at least ceil(N / rows_per_p) values, read when the kernel runs; both ignored (may be NULL) when gates is NULL.
+ *   SBA_E_ARG unless 1 <= N <= 2^20, 1 <= flags <= 15, uniforms / applied non-NULL and 4-byte aligned, mats non-NULL and
+ *   16-byte aligned, and with gates: gates and p_dev 4-byte aligned, p_dev non-NULL, rows_per_p >= 1.
+ * sba_geoaug_fwd: out [nr + nf][3][S][S] = the warp of [real | fake] (in place of a concatenation), image n by mats[n];
+ *   nr = 0 or nf = 0 allowed (the pointer of an empty half is ignored).  An image whose M is exactly the identity is copied.
+ *   With flip / rot90 alone (entries 0, +-1) the output is a permutation of the input, bit for bit.
+ * sba_geoaug_bwd: dx [n][3][S][S] = the exact adjoint, dx[ch, q] = sum over d of dout[ch, d] hat(sx(d) - qx) hat(sy(d) - qy),
+ *   gathered: no atomics, no workspace, f32 sums in a fixed order -- two calls give the same bits.  An input pixel looks
+ *   at the output pixels of the bounding box of M^-1 ([qx - 1, qx + 1] x [qy - 1, qy + 1]), at most 7 per axis: exact for
+ *   every M sba_geoaug_prepare writes; for a matrix that shrinks the image further (singular values below 2^-0.6) the
+ *   window is cut there and the result is no longer the adjoint.  A NaN matrix reads nothing.
+ * Both: S even, 8..4096; 1 <= number of images <= 65535; images, out / dx and mats 16-byte aligned; SBA_E_ARG before any
+ * launch otherwise, nothing written.  No host synchronisation; graph-capturable. */
+int sba_geoaug_prepare(const float* uniforms, const float* gates, const float* p_dev, int rows_per_p, int N, int flags,
+                       float* mats, int32_t* applied, void* stream);
+int sba_geoaug_fwd(const float* real, int nr, const float* fake, int nf, const float* mats, float* out, int S,
+                   void* stream);
+int sba_geoaug_bwd(const float* dout, int n, const float* mats, float* dx, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,9 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
     algo.diffaug = getattr(args, 'diffaug', '') if training else ''
     if getattr(args, 'diffaug', '') and not training:
         print('--diffaug is ignored outside training')
+    algo.geoaug = getattr(args, 'geoaug', '') if training else ''
+    if getattr(args, 'geoaug', '') and not training:
+        print('--geoaug is ignored outside training')
     ada_given = getattr(args, 'ada', None) is not None or getattr(args, 'diffaug_p', None) is not None
     if training:
         algo.ada, algo.diffaug_p = getattr(args, 'ada', None), getattr(args, 'diffaug_p', None)

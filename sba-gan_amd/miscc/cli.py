@@ -5,6 +5,7 @@
     [--nearest K]  [--nearest_stats PATH]  [--nearest_show M]
     [--device_data]  [--device_data_gb G]  [--replay]  [--diffaug POLICY]
     [--diffaug_p P]  [--ada TARGET]  [--ada_kimg K]  [--ada_interval N]  [--ada_pmax P]
+    [--geoaug POLICY: flip,rot90,scale,rotate in front of the discriminators]
     [--retrieval E]  [--retrieval_only: DAMSM pre-training]
     [--bert_dir DIR: the BERT entry points]
 
@@ -57,6 +58,18 @@ def _diffaug(text):
         if n not in DIFFAUG_POLICIES:
             raise argparse.ArgumentTypeError('unknown policy %r; valid names are %s (comma separated)'
                                              % (n, ', '.join(DIFFAUG_POLICIES)))
+    return ','.join(names)
+
+
+GEOAUG_POLICIES = ('flip', 'rot90', 'scale', 'rotate')
+
+
+def _geoaug(text):
+    names = [n.strip() for n in text.split(',')] if text else []
+    for n in names:
+        if n not in GEOAUG_POLICIES:
+            raise argparse.ArgumentTypeError('unknown policy %r; valid names are %s (comma separated)'
+                                             % (n, ', '.join(GEOAUG_POLICIES)))
     return ','.join(names)
 
 
@@ -136,6 +149,14 @@ def options(what, default_cfg, argv=None, bert=False):
     ap.add_argument('--ada_pmax', dest='ada_pmax', default=1.0, metavar='P',
                     type=_ranged_float('P', 0.0, 1.0, 'a probability in [0, 1]'),
                     help='with --ada: the largest p the controller sets (default 1.0)')
+    ap.add_argument('--geoaug', dest='geoaug', type=_geoaug, default='', metavar='POLICY',
+                    help='GAN training: geometric augmentation (Karras et al., NeurIPS 2020) of every image a '
+                         'discriminator sees, real and fake, gradients flowing through to the generator: per image one '
+                         'affine warp about the centre, bilinear, zero padded (sbagan.geoaug, one HIP pass in place of '
+                         'the step\'s concatenation).  POLICY: a comma-separated subset of flip,rot90,scale,rotate; '
+                         'empty = off.  With --diffaug it runs first, then colour, translation and cutout; with '
+                         '--diffaug_p / --ada each part is applied with the same per-discriminator probability p.  '
+                         'Single GPU only.  Ignored outside training and by the DAMSM pre-training entry points')
     ap.add_argument('--retrieval', dest='retrieval', default=0, metavar='E',
                     type=_ranged_int('E', 0, None, '0 (off) or an interval in epochs'),
                     help='DAMSM pre-training: after the validation pass of every E-th epoch and of the last one, rank '

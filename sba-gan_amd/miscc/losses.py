@@ -135,8 +135,18 @@ def _augmented(real, fake, augment):
     return ops.diffaug_gated(real, fake, rows, gates, p_dev, flags)
 
 
+def _seen(real, fake, augment, geo):
+    """what a discriminator sees of [real | fake] (real None: the fake images alone).  geo (mats, one row per image):
+    ops.geoaug writes the warped, joined batch; augment then runs over that batch as it is -- geometry first, then
+    colour, translation and cutout, the order of Karras et al."""
+    if geo is None:
+        return _augmented(real, fake, augment)
+    seen = ops.geoaug(real, fake, geo)
+    return seen if augment is None else _augmented(None, seen, augment)
+
+
 def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake_labels, real_features=None,
-                       augment=None, count_sink=None):
+                       augment=None, count_sink=None, geo=None):
     """losses.py:136-161: the real and the fake.detach() trunk pass, five heads,
     errD = (real + cond_real)/2 + (fake + cond_fake + cond_wrong)/3.
 
@@ -155,9 +165,15 @@ def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake
     (rows, flags, gates [2n][4], p_dev [1]) the gated kernels run instead (_augmented).
 
     count_sink (optional): handed to ops.d_heads -- the signs of the real rows' probabilities are counted on the device
-    (the overfitting read-out of --ada)."""
+    (the overfitting read-out of --ada).
+
+    geo (optional, f32 [2n][4]: one matrix per image, real rows first -- sbagan.geoaug.GeoAugment.d_mats): the geometric
+    augmentation of both halves (ops.geoaug), which does the concatenation; with `augment` as well the
+    joined batch then goes through the kernels above (_seen).  Not available with real_features."""
     if augment is not None and real_features is not None:
         raise ValueError('discriminator_loss: augment does not go with real_features (the two-pass layout)')
+    if geo is not None and real_features is not None:
+        raise ValueError('discriminator_loss: geo does not go with real_features (the two-pass layout)')
     if real_features is not None:
         real, fake = real_features, netD(fake_imgs.detach())
     else:
@@ -165,8 +181,8 @@ def discriminator_loss(netD, real_imgs, fake_imgs, conditions, real_labels, fake
     if real.shape != fake.shape:
         raise ValueError('discriminator_loss: real %s and fake %s differ in shape'
                          % (tuple(real.shape), tuple(fake.shape)))
-    if augment is not None:
-        feats = _augmented(real, fake, augment)
+    if augment is not None or geo is not None:
+        feats = _seen(real, fake, augment, geo)
     else:
         feats = torch.cat((real, fake), 0)
     if real_features is None:
@@ -211,7 +227,7 @@ def _g_term(netD, features, sent_emb):
     return ops.d_heads(netD, features, sent_emb, g_term_heads(features.size(0), netD.UNCOND_DNET is not None))
 
 
-def generator_d_term(netD, fake_img, sent_emb, augment=None):
+def generator_d_term(netD, fake_img, sent_emb, augment=None, geo=None):
     """One discriminator's term of generator_loss (losses.py:168-186) on its own, together with its gradient with
     respect to the fake images: returns (g_loss, d g_loss / d fake_img).
 
@@ -223,16 +239,18 @@ def generator_d_term(netD, fake_img, sent_emb, augment=None):
     require gradients (the reference computes and discards them, trainer.py:270,287).
 
     augment (optional, (rows [n][8], flags)): the discriminator sees the augmented image (ops.diffaug); the returned
-    gradient is with respect to the image itself, through the augmentation."""
+    gradient is with respect to the image itself, through the augmentation.
+
+    geo (optional, f32 [n][4]): the image is warped first (ops.geoaug); the gradient comes back through its adjoint."""
     leaf = fake_img.detach().requires_grad_(True)
-    seen = leaf if augment is None else _augmented(None, leaf, augment)
+    seen = leaf if augment is None and geo is None else _seen(None, leaf, augment, geo)
     g_loss = _g_term(netD, netD(seen), sent_emb)
     (grad,) = torch.autograd.grad(g_loss, leaf)
     return g_loss.detach(), grad
 
 
 def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sent_emb, match_labels,
-                   cap_lens, class_ids, streams=None, damsm=None, d_terms=None, augment=None):
+                   cap_lens, class_ids, streams=None, damsm=None, d_terms=None, augment=None, geo=None):
     """losses.py:164-206.  Returns (errG_total, logs) where logs is a dict of device scalars
     {'g_loss0', ..., 'w_loss', 's_loss'} (format with .item() outside the step).
 
@@ -248,7 +266,9 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
     terms; the caller back-propagates with `backward_with_image_grads`.
 
     augment (optional, one (rows [n][8], flags) per discriminator): each discriminator sees its fake image through
-    ops.diffaug; the ranking terms see the image itself."""
+    ops.diffaug; the ranking terms see the image itself.
+
+    geo (optional, one f32 [n][4] per discriminator): each discriminator sees its fake image through ops.geoaug first."""
     import contextlib
     numDs = len(netsD)
     batch_size = real_labels.size(0)
@@ -268,8 +288,8 @@ def generator_loss(netsD, image_encoder, fake_imgs, real_labels, words_embs, sen
         else:
             with branch(i):
                 seen = fake_imgs[i]
-                if augment is not None:
-                    seen = _augmented(None, seen, augment[i])
+                if augment is not None or geo is not None:
+                    seen = _seen(None, seen, None if augment is None else augment[i], None if geo is None else geo[i])
                 g_loss = _g_term(netsD[i], netsD[i](seen), sent_emb)
         terms.append(g_loss)
         logs['g_loss%d' % i] = g_loss.detach()

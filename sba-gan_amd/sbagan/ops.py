@@ -2850,3 +2850,75 @@ def ada_adjust(p, rt, counters, interval, target, adjust, p_max):
             raise ValueError('ada_adjust: %s must be contiguous %s %s on %s' % (name, dtype, list(shape), p.device))
     call('sba_ada_adjust', _p(p), _p(rt), _p(counters), nD, int(interval), float(target), float(adjust), float(p_max),
          _stream())
+
+
+# ----------------------------------------------------------------------------
+# Geometric augmentation (csrc/geoaug.hip; sbagan/geoaug.py)
+# ----------------------------------------------------------------------------
+GEOAUG_FLIP, GEOAUG_ROT90, GEOAUG_SCALE, GEOAUG_ROTATE = 1, 2, 4, 8
+
+
+def geoaug_prepare(uniforms, gates, p_dev, rows_per_p, flags, mats, applied):
+    """mats [N][4] and applied [N] (int32) from uniforms [N][8]: the one launch of sba_geoaug_prepare on the current
+    stream.  gates [N][4] and p_dev [nP] (row r reads p_dev[r // rows_per_p]) gate each part per row; both None: every
+    part of `flags` (GEOAUG_* bits) on every row."""
+    _need_gpu(uniforms)
+    N, dev = uniforms.size(0), uniforms.device
+    need = [('uniforms', uniforms, torch.float32, (N, 8)), ('mats', mats, torch.float32, (N, 4)),
+            ('applied', applied, torch.int32, (N,))]
+    if (gates is None) != (p_dev is None):
+        raise ValueError('geoaug_prepare: gates and p_dev go together')
+    if gates is not None:
+        rows_per_p = int(rows_per_p)
+        if rows_per_p < 1 or p_dev.dim() != 1 or p_dev.numel() * rows_per_p < N:
+            raise ValueError('geoaug_prepare: %d rows at %d rows per p need more than %d values of p'
+                             % (N, rows_per_p, p_dev.numel()))
+        need += [('gates', gates, torch.float32, (N, 4)), ('p_dev', p_dev, torch.float32, tuple(p_dev.shape))]
+    for name, t, dtype, shape in need:
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError('geoaug_prepare: %s must be contiguous %s %s on %s' % (name, dtype, list(shape), dev))
+    call('sba_geoaug_prepare', _p(uniforms), _p(gates), _p(p_dev), int(rows_per_p) if gates is not None else 1, N,
+         int(flags), _p(mats), _p(applied), _stream())
+
+
+class GeoAugFn(torch.autograd.Function):
+    """[real | fake] -> W([real | fake]): the step's concatenation and the per-image affine warp in one pass
+    (sba_geoaug_fwd).  The map is linear: no input is saved, the backward is its exact adjoint (sba_geoaug_bwd) on the
+    fake rows' matrices.  The gradient goes to `fake` only; when `fake` needs none the backward launches nothing."""
+
+    @staticmethod
+    def forward(ctx, fake, real, mats):
+        _need_gpu(fake)
+        nf, C, S, S2 = fake.shape
+        nr = 0 if real is None else real.size(0)
+        if C != 3 or S != S2 or fake.dtype != torch.float32 or not fake.is_contiguous():
+            raise ValueError('geoaug: fake must be contiguous float32 [n][3][S][S], got %s %s'
+                             % (fake.dtype, tuple(fake.shape)))
+        if real is not None and (real.dtype != torch.float32 or not real.is_contiguous() or real.device != fake.device
+                                 or tuple(real.shape[1:]) != (3, S, S)):
+            raise ValueError('geoaug: real must be contiguous float32 [n][3][%d][%d] on %s' % (S, S, fake.device))
+        if (mats.dtype != torch.float32 or tuple(mats.shape) != (nr + nf, 4) or not mats.is_contiguous()
+                or mats.device != fake.device):
+            raise ValueError('geoaug: mats must be contiguous float32 [%d][4] on %s' % (nr + nf, fake.device))
+        out = torch.empty((nr + nf, 3, S, S), dtype=torch.float32, device=fake.device)
+        call('sba_geoaug_fwd', _p(real), nr, _p(fake), nf, _p(mats), _p(out), S, _stream())
+        ctx.save_for_backward(mats)
+        ctx.geom = (nr, nf, S)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        (mats,) = ctx.saved_tensors
+        nr, nf, S = ctx.geom
+        dout = dout.float().contiguous()[nr:]            # (a contiguous batch: its tail is contiguous and 16-byte aligned)
+        dx = torch.empty((nf, 3, S, S), dtype=torch.float32, device=dout.device)
+        call('sba_geoaug_bwd', _p(dout), nf, _p(mats[nr:]), _p(dx), S, _stream())
+        return dx, None, None
+
+
+def geoaug(real, fake, mats):
+    """The geometrically augmented [real | fake] batch of one discriminator pass (real = None: the fake images alone).
+    mats: f32 [(nr + nf)][4], one matrix per image, as sba_geoaug_prepare writes them (sbagan.geoaug.GeoAugment)."""
+    return GeoAugFn.apply(fake.float().contiguous(), None if real is None else real.float().contiguous(), mats)

@@ -216,6 +216,8 @@ class SlotStep(object):
             self.eps.normal_(0, 1)
             if self.gan.augment is not None:
                 self.gan.augment.draw()
+            if self.gan.geo_augment is not None:
+                self.gan.geo_augment.draw()
             self.prologue()
             return self.gan.step(*self.args, eps=self.eps)
         out = self.recording.prioritize() if n == 1 else None

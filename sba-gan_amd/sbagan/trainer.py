@@ -255,6 +255,10 @@ class GANStep(object):
             raise ValueError('GANStep: augmentation (--diffaug) is single-GPU only: not with distributed=True')
         if self.augment is not None and self.force_overlap_layout:
             raise ValueError('GANStep: augmentation (--diffaug) does not go with force_overlap_layout')
+        if self.geo_augment is not None and distributed:
+            raise ValueError('GANStep: augmentation (--geoaug) is single-GPU only: not with distributed=True')
+        if self.geo_augment is not None and self.force_overlap_layout:
+            raise ValueError('GANStep: augmentation (--geoaug) does not go with force_overlap_layout')
 
     def _allreduce_start(self, flat):
         return self.exchange.start(flat.grad)
@@ -272,6 +276,9 @@ class GANStep(object):
     augment = None      # sbagan.diffaug.DiffAugment, set by the trainer (--diffaug) BEFORE construction: every image a
     #                     discriminator sees goes through ops.diffaug.  step() never draws: the uniforms are an input like
     #                     `noise`, drawn by whoever draws the noise (augment.draw())
+    geo_augment = None  # sbagan.geoaug.GeoAugment, set the same way (--geoaug): every image a discriminator sees is warped
+    #                     by ops.geoaug first.  Its uniforms are drawn with the noise (geo_augment.draw(), behind
+    #                     augment.draw()); the step issues geo_augment.prepare(), the one launch that makes the matrices
     bucket_d = True
     overlap_g = True
     force_overlap_layout = False    # tests: a SINGLE-process step with the data-parallel launch decomposition (real-image
@@ -377,6 +384,10 @@ class GANStep(object):
         ops.SIDE_WGRAD = self.overlap_wgrad
         ops.det_reset()                   # deterministic mode: the step's partial sums start at the ring's base
         ops.ARENA.begin(self.device)      # one memset for all per-layer accumulators of the step
+        if self.geo_augment is not None:
+            # --geoaug: this step's matrices, on the origin stream ahead of the generator's forward pass -- every
+            # discriminator stream forks from a later point of it
+            self.geo_augment.prepare()
         self.netG.ca_net.eps = eps
         fake_imgs, _, mu, logvar = self.netG(noise, sent_emb, words_embs, mask)
         self._ctx = (fake_imgs, mu, logvar)
@@ -414,7 +425,8 @@ class GANStep(object):
         self._check_augment(self.distributed)        # (both can be set after construction)
         errD = discriminator_loss(netD, imgs[i], fake_imgs[i], sent_emb, self.real_labels, self.fake_labels,
                                   real_features=rf, augment=None if self.augment is None else self.augment.d_arg(i),
-                                  count_sink=None if self.augment is None else self.augment.count_sink(i))
+                                  count_sink=None if self.augment is None else self.augment.count_sink(i),
+                                  geo=None if self.geo_augment is None else self.geo_augment.d_mats(i))
         self._out['errD%d' % i] = errD.detach()
         cuts = list(netD._cuts)
         netD.clear_cuts(record=False)
@@ -490,7 +502,8 @@ class GANStep(object):
         self._d_frozen[i] = True            #  runs -- an exception, a caller driving the phases by hand -- the next
         #                                      phase_d_bwd_tail of this discriminator does)
         value, grad = generator_d_term(netD, self._ctx[0][i], sent_emb,
-                                       augment=None if self.augment is None else self.augment.g_arg(i))
+                                       augment=None if self.augment is None else self.augment.g_arg(i),
+                                       geo=None if self.geo_augment is None else self.geo_augment.g_mats(i))
         self._g_terms[i] = (value, grad)
 
     def phase_b_bwd(self, sent_emb, words_embs, cap_lens, class_ids):
@@ -527,7 +540,9 @@ class GANStep(object):
                                           streams=self._d_streams() if self.concurrent_d else None, damsm=damsm,
                                           d_terms=None if d_terms is None else [t[0] for t in d_terms],
                                           augment=None if self.augment is None or d_terms is not None else
-                                          [self.augment.g_arg(i) for i in range(len(self.netsD))])
+                                          [self.augment.g_arg(i) for i in range(len(self.netsD))],
+                                          geo=None if self.geo_augment is None or d_terms is not None else
+                                          [self.geo_augment.g_mats(i) for i in range(len(self.netsD))])
         kl = KL_loss(mu, logvar)
         errG_total = errG_total + kl
         mark('g_loss_forward')
@@ -1034,6 +1049,8 @@ class ReplayedStep(object):
             eps.normal_(0, 1)
             if gan.augment is not None:
                 gan.augment.draw()
+            if gan.geo_augment is not None:
+                gan.geo_augment.draw()
             if recorded_prologue is not None:
                 recorded_prologue()
             out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise, eps=eps)
@@ -1107,6 +1124,8 @@ class ReplayedStep(object):
             self.eps.normal_(0, 1)
             if self.gan.augment is not None:
                 self.gan.augment.draw()
+            if self.gan.geo_augment is not None:
+                self.gan.geo_augment.draw()
         if self.prologue is not None:
             self.prologue()
 

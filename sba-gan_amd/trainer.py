@@ -133,6 +133,13 @@ class condGANTrainer(object):
                                            interval=self.ada_interval, p_max=self.ada_pmax)
             if self.gan.augment.adaptive:
                 self._restore_ada(self.gan.augment)
+        if self.geoaug and cfg.TRAIN.FLAG:
+            # --geoaug: the geometric family in front of the same discriminators, gated by the p of
+            # --diffaug_p / --ada where there is one
+            from sbagan.geoaug import GeoAugment
+            aug = self.gan.augment
+            self.gan.geo_augment = GeoAugment(self.geoaug, self.batch_size, len(netsD), self.gan.device,
+                                              p=aug.p if aug is not None and aug.gated else None)
         return self.gan.optG, self.gan.optD
 
     def prepare_labels(self):
@@ -238,6 +245,7 @@ class condGANTrainer(object):
     diffaug_p = None            # --diffaug_p P: each part with probability P (the gated kernels); None = always
     ada = None                  # --ada TARGET: p follows the overfitting read-out r_t on the device
     ada_kimg, ada_interval, ada_pmax = 500.0, 4, 1.0
+    geoaug = ''                 # --geoaug POLICY: flip, rot90, scale, rotate in front of the discriminators ('' = off)
     log_interval = 100          # iterations between two loss lines
     average_interval = 1000     # iterations between the 'average' (EMA generator) image dumps
 
@@ -297,6 +305,8 @@ class condGANTrainer(object):
                     noise.normal_(0, 1)
                     if gan.augment is not None:
                         gan.augment.draw()
+                    if gan.geo_augment is not None:
+                        gan.geo_augment.draw()
                     out = gan.step(imgs, sent_emb, words_embs, mask, cap_lens, class_ids, noise)
                 step += 1
                 gen_iterations += 1
