@@ -18,11 +18,11 @@ if _HERE not in sys.path:
 from datasets import TextDataset, tokenize  # noqa: E402
 from miscc import cli, transforms  # noqa: E402
 from miscc.config import cfg  # noqa: E402
-from sbagan import evaluation  # noqa: E402
+from sbagan import evaluation, track  # noqa: E402
 
 
 def parse_args(argv=None):
-    return cli.options('Train a AttnGAN network', 'cfg/bird_attn2.yml', argv)
+    return cli.options('Train a AttnGAN network', 'cfg/bird_attn2.yml', argv, gan=True)
 
 
 def _encode_sentences(path, wordtoix):
@@ -103,6 +103,14 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
         algo.ada_pmax = getattr(args, 'ada_pmax', 1.0)
     elif ada_given:
         print('--ada / --diffaug_p are ignored outside training')
+    if training:
+        algo.track = getattr(args, 'track', 0)
+        algo.track_split, algo.track_n = getattr(args, 'track_split', 'test'), getattr(args, 'track_n', 0)
+        algo.track_captions, algo.track_best = getattr(args, 'track_captions', 1), getattr(args, 'track_best', None)
+        if algo.track and track.not_tracked_line(args):
+            print(track.not_tracked_line(args))
+    elif getattr(args, 'track', 0):
+        print('--track is ignored outside training')
     start_t = time.time()
     if training:
         algo.train()

@@ -19,7 +19,7 @@ from miscc import cli  # noqa: E402
 
 
 def parse_args(argv=None):
-    return cli.options('Train a AttnGAN network', 'cfg/bird_style.yml', argv, bert=True)
+    return cli.options('Train a AttnGAN network', 'cfg/bird_style.yml', argv, bert=True, gan=True)
 
 
 def gen_example(wordtoix, algo):

@@ -6,6 +6,7 @@
     [--device_data]  [--device_data_gb G]  [--replay]  [--diffaug POLICY]
     [--diffaug_p P]  [--ada TARGET]  [--ada_kimg K]  [--ada_interval N]  [--ada_pmax P]
     [--geoaug POLICY: flip,rot90,scale,rotate in front of the discriminators]
+    [--track E]  [--track_split NAME]  [--track_n N]  [--track_captions C]  [--track_best KEY: GAN training]
     [--retrieval E]  [--retrieval_only: DAMSM pre-training]
     [--bert_dir DIR: the BERT entry points]
 
@@ -21,7 +22,7 @@ import re
 import numpy as np
 import torch
 
-from sbagan import evaluation
+from sbagan import evaluation, track
 
 from .config import cfg, cfg_from_file
 
@@ -84,7 +85,15 @@ def _ranged_float(metavar, lo, hi, what, open_ends=False):
     return parse
 
 
-def options(what, default_cfg, argv=None, bert=False):
+def _track_key(text):
+    if text not in track.BEST_KEYS:
+        raise argparse.ArgumentTypeError('unknown key %r; valid keys are %s' % (text, ', '.join(track.BEST_KEYS)))
+    return text
+
+
+def options(what, default_cfg, argv=None, bert=False, gan=False):
+    """gan: the entry point trains the GAN (main.py, main_bert.py) -- the only ones --track means something to, so the
+    only ones that refuse a --track that would measure nothing"""
     ap = argparse.ArgumentParser(description=what)
     ap.add_argument('--cfg', dest='cfg_file', type=str, default=default_cfg, help='optional config file')
     ap.add_argument('--gpu', dest='gpu_id', type=int, default=0)
@@ -168,6 +177,28 @@ def options(what, default_cfg, argv=None, bert=False):
     ap.add_argument('--retrieval_only', dest='retrieval_only', action='store_true', default=False,
                     help='DAMSM pre-training: load the encoder pair of TRAIN.NET_E, rank the validation split once, '
                          'print the figures, write retrieval.json and return without training')
+    ap.add_argument('--track', dest='track', default=0, metavar='E',
+                    type=_ranged_int('E', 0, None, '0 (off) or an interval in epochs'),
+                    help='GAN training: at the end of every epoch with epoch %% E == 0 and once more after the final '
+                         'checkpoint, evaluate the EMA generator -- the weights save_model would write at that moment -- '
+                         'on a held-out split (sbagan.track): the figures of those of --fid, --kid, --prdc and '
+                         '--r_precision that are on (at least one must be), over a frozen set of captions, noise and '
+                         'real-image rows, one printed line and one JSON line in Model/track.jsonl per evaluation, no '
+                         'image written; 0 = off.  It draws from no global generator and leaves the training untouched, '
+                         'with --replay too.  On this project\'s own trunk and compute dtype: comparable between epochs '
+                         'and runs of this project only.  Ignored outside training and by the DAMSM entry points')
+    ap.add_argument('--track_split', dest='track_split', type=str, default='test', metavar='NAME',
+                    help='with --track: the held-out split (default test)')
+    ap.add_argument('--track_n', dest='track_n', default=0, metavar='N',
+                    type=_ranged_int('N', 0, None, '0 (the whole split) or a number of images'),
+                    help='with --track: the first N images of the split in the data set\'s own order; 0 = all of them')
+    ap.add_argument('--track_captions', dest='track_captions', default=1, metavar='C',
+                    type=_ranged_int('C', 1, None, 'a number of captions per image, at least 1'),
+                    help='with --track: captions 0 .. C - 1 of every image, 1 to TEXT.CAPTIONS_PER_IMAGE (default 1)')
+    ap.add_argument('--track_best', dest='track_best', default=None, metavar='KEY', type=_track_key,
+                    help='with --track: whenever an evaluation improves on the best KEY so far, write '
+                         'Model/netG_best.pth (the bytes of that epoch\'s checkpoint) and Model/best.json; KEY one of '
+                         + ', '.join(track.BEST_KEYS) + '.  On resume a best.json beside TRAIN.NET_G is honoured')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')
@@ -177,6 +208,10 @@ def options(what, default_cfg, argv=None, bert=False):
             ap.error('--%s needs a non-empty --diffaug POLICY' % flag)
     if args.ada is not None and args.diffaug_p is not None and args.diffaug_p > args.ada_pmax:
         ap.error('--diffaug_p %g is above --ada_pmax %g' % (args.diffaug_p, args.ada_pmax))
+    if args.track and gan:
+        problem = track.check_flags(args)
+        if problem:
+            ap.error(problem)
     return args
 
 

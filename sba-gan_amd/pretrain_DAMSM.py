@@ -10,7 +10,7 @@ only): the update is ONE recording over a static batch slot (sbagan.damsm.DAMSMS
 read only where the interval line is printed.  --retrieval E: after the validation pass of every E-th epoch and of the
 last one, the whole validation split is ranked both ways (sbagan.retrieval): one printed line and one JSON
 line in Model/retrieval.jsonl.  --retrieval_only: the pair of TRAIN.NET_E is ranked once, retrieval.json is written and
-nothing is trained."""
+nothing is trained.  --track E and its companions belong to GAN training (main.py): parsed here and ignored."""
 import json
 import os
 import sys

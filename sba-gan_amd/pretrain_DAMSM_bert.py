@@ -6,7 +6,7 @@ pretrain_DAMSM.py's loop with datasets_bert.TextDataset and a BertEncoder: its t
 (dropout), only pooler / fc / conv_text and the image side's two embedding layers train (sbagan.damsm.DAMSMStep's BERT
 path).  Checkpoints: Model/text_encoder<N>.pth, Model/image_encoder<N>.pth.  --bert_dir: a local HuggingFace BERT
 directory whose config and weights BertEncoder loads (and whose vocab.txt the dataset reads); without it the trunk is
-randomly initialised."""
+randomly initialised.  --track E and its companions belong to GAN training (main_bert.py): parsed here and ignored."""
 import os
 import sys
 

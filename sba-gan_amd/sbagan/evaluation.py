@@ -48,8 +48,10 @@ def _build_r_precision(suite, text_encoder):
     """sbagan.rprecision.RPrecision over the sentence embeddings of every caption of the sampled split"""
     from sbagan.rprecision import RPrecision, encode_pool
     v = suite.values
-    pool, pool_class = encode_pool(suite.data_loader.dataset, lambda c, n: suite.encode(text_encoder, c, n),
-                                   suite.batch_size, seed=v['r_precision_seed'], device=suite.device)
+    if 'pool' not in suite.cache:   # (a caller that evaluates more than once keeps the encoded pool: sbagan.track)
+        suite.cache['pool'] = encode_pool(suite.data_loader.dataset, lambda c, n: suite.encode(text_encoder, c, n),
+                                          suite.batch_size, seed=v['r_precision_seed'], device=suite.device)
+    pool, pool_class = suite.cache['pool']
     return RPrecision(suite.load_image_encoder(), pool, pool_class, R=v['r_precision'], seed=v['r_precision_seed'])
 
 
@@ -61,9 +63,12 @@ def _build_fid(suite, text_encoder):
     dtype, path = dtype_name(), suite.values['fid_stats']
     key = stats_key(cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder'), dtype, suite.split_dir, cli.image_size())
     evaluator = FID(suite.image_encoder.pooled_features, D=2048, key=key, dtype=dtype)
-    if path and os.path.exists(path):
+    if 'fid_real' in suite.cache:   # (read and checked against the key by an earlier Suite of the same caller)
+        evaluator.set_real(suite.cache['fid_real'])
+    elif path and os.path.exists(path):
         evaluator.load_real(path)
         print('Load real FID statistics from:', path)
+        suite.cache['fid_real'] = evaluator.real_stats()
     return evaluator
 
 
@@ -250,11 +255,14 @@ ATTRIBUTES = tuple((opt.name, opt.default) for opt in OPTIONS) + tuple(
 
 class Suite(object):
     """The evaluators of one sampling() run.  values: {option name: value}.  The rest is what builders need of the trainer:
-    its _encode and _load_image_encoder, its data loader, batch size and device."""
+    its _encode and _load_image_encoder, its data loader, batch size and device.  cache: a dict of the caller's in which
+    the builders keep what does not change from one Suite to the next -- 'pool', rprecision.encode_pool's result, and
+    'fid_real', the statistics read from fid_stats -- for a caller that evaluates many times in one run (sbagan.track)."""
 
-    def __init__(self, values, split_dir, encode, load_image_encoder, data_loader, batch_size, device):
+    def __init__(self, values, split_dir, encode, load_image_encoder, data_loader, batch_size, device, cache=None):
         self.values, self.split_dir, self.encode, self.load_image_encoder = values, split_dir, encode, load_image_encoder
         self.data_loader, self.batch_size, self.device = data_loader, batch_size, device
+        self.cache = {} if cache is None else cache
         self.image_encoder = self.train_crops = None
         self.records = [rec for rec in EVALUATORS if values[rec.stem]]
         for opt in (opt for rec in self.records for opt in rec.options if opt.lo is not None):
@@ -283,7 +291,8 @@ class Suite(object):
 
     def update(self, last, real_last, sent_emb, class_ids, keys):
         """one batch.  Each side goes through the trunk once for every consumer of rows: the generated side not at all
-        when R-precision has just run it through, the real side only when somebody takes real rows"""
+        when R-precision has just run it through, the real side only when somebody takes real rows.  real_last None: the
+        real rows come through feed_real_rows instead (evaluators of rows and rankings only)"""
         for ev in self._ranking:
             ev.update(last, sent_emb, class_ids)
         if self._fake_rows:
@@ -291,14 +300,23 @@ class Suite(object):
                 self.image_encoder.pooled_features(last)
             for ev, with_keys in self._fake_rows:
                 ev.update_features('fake', self.image_encoder.last_pooled, *((keys,) if with_keys else ()))
-            if self._real_rows:
+            if self._real_rows and real_last is not None:
                 real_feats = self.image_encoder.pooled_features(real_last)
                 for ev in self._real_rows:
                     ev.update_features('real', real_feats)
+        if real_last is None and self._images:
+            raise ValueError('the evaluators of pixels (%s) need the real images of every batch'
+                             % ', '.join(rec.stem for rec in self.records if rec.consumes == 'images'))
         for ev, with_classes in self._images:       # the pixels themselves: no trunk
             extra = (class_ids,) if with_classes else ()
             ev.update('fake', last, *extra)
             ev.update('real', real_last, *extra)
+
+    def feed_real_rows(self, rows):
+        """the real side as pooled trunk rows [n][2048] the caller has kept (f32, on the device), to every evaluator that
+        still takes real rows; goes with update(..., real_last=None)"""
+        for ev in self._real_rows:
+            ev.update_features('real', rows)
 
     def finish(self, out_dir):
         """the result of every evaluator, in table order: printed, written to <stem>.json, followed by its finish step.

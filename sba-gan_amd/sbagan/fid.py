@@ -148,5 +148,19 @@ class FID(Evaluator):
         self._stats['real'] = (n, mu, sigma, trace)
         self._loaded.add('real')
 
+    def real_stats(self):
+        """(n, mu, sigma, trace) of the real side, as load_real or the rows gave it"""
+        return self._full_stats('real')
+
+    def set_real(self, stats):
+        """the real side from real_stats() of an evaluator under the same key (a file read once, kept by the caller);
+        like load_real, the side then takes no rows"""
+        n, mu, sigma, trace = stats
+        if mu.shape != (self.D,) or sigma.shape != (self.D, self.D) or n < 2:
+            raise ValueError('FID: the statistics handed over are not [%d] / [%d][%d] of n >= 2 rows' % (self.D, self.D, self.D))
+        self._acc.pop('real', None)
+        self._stats['real'] = (int(n), mu, sigma, float(trace))
+        self._loaded.add('real')
+
     def result(self):
         return summarize(self._full_stats('real'), self._full_stats('fake'), self.dtype)

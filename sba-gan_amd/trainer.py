@@ -15,7 +15,9 @@ What differs, none of it in results:
   * checkpoints are the reference's files: Model/netG_epoch_N.pth (EMA weights, trainer.py:159-164) and
     Model/netD{i}.pth, loadable by either implementation.  With cfg.TRAIN.NET_E == '' the reference prints an
     error and fails; pass `allow_random_encoders=True` to train against randomly initialised frozen encoders
-    (synthetic-data runs and tests).
+    (synthetic-data runs and tests);
+  * with `track` (--track E) the EMA generator is evaluated on a held-out split at the end of every E-th epoch and after
+    the final checkpoint (sbagan.track): Model/track.jsonl, and with `track_best` Model/netG_best.pth / best.json.
 """
 import json
 import os
@@ -249,6 +251,16 @@ class condGANTrainer(object):
     log_interval = 100          # iterations between two loss lines
     average_interval = 1000     # iterations between the 'average' (EMA generator) image dumps
 
+    track = 0                   # --track E: evaluate the EMA generator on a held-out split every E epochs
+    track_split, track_n, track_captions, track_best = 'test', 0, 1, None
+
+    def _tracker(self):
+        """the held-out evaluation of --track (sbagan.track.Tracker), or None when the flag is off"""
+        if not self.track:
+            return None
+        from sbagan.track import Tracker
+        return Tracker(self, self.track, self.track_split, self.track_n, self.track_captions, self.track_best)
+
     def _replay_step(self, text_encoder, noise):
         """the static batch slot and the step over it (sbagan.static_batch); a device loader writes straight into it"""
         from miscc import cli
@@ -288,6 +300,7 @@ class condGANTrainer(object):
         if self.replay:
             slot, stepper = self._replay_step(text_encoder, noise)
         self.slot, self.slot_step = slot, stepper
+        self.tracker = tracker = self._tracker()
         for epoch in range(start_epoch, self.max_epoch):
             start_t = time.time()
             step = 0
@@ -340,10 +353,18 @@ class condGANTrainer(object):
                 self.save_model(netG, gan.flatG.ema_params(), netsD, epoch)
                 if stepper is not None:
                     stepper.resync()
+            if tracker is not None and tracker.due(epoch):
+                # --track: the EMA weights, as save_model would write them now, on the held-out set (sbagan.track)
+                snapshot = epoch % cfg.TRAIN.SNAPSHOT_INTERVAL == 0
+                tracker.evaluate(netG, text_encoder, epoch, gen_iterations, stepper,
+                                 'netG_epoch_%d.pth' % epoch if snapshot else None)
             if max_steps is not None and gen_iterations >= max_steps:
                 break
         gan.finish()
         self.save_model(netG, gan.flatG.ema_params(), netsD, self.max_epoch)
+        if tracker is not None:
+            tracker.evaluate(netG, text_encoder, self.max_epoch, gen_iterations, stepper,
+                             'netG_epoch_%d.pth' % self.max_epoch)
 
     # ------------------------------------------------------------------ inference (trainer.py:348-518)
     # Written from the OUTPUT-FILE contract of the reference's three inference entry points (what a user of its eval
