@@ -89,6 +89,26 @@ int sba_geoaug_fwd(const float* real, int nr, const float* fake, int nf, const f
                    void* stream);
 int sba_geoaug_bwd(const float* dout, int n, const float* mats, float* dx, int S, void* stream);
 
+/* The truncation trick in W (Karras et al., CVPR 2019; csrc/truncation.hip, sbagan/truncation.py): the
+ * mean style of a mapping network and the pull of a style towards it.  Neither entry point synchronises with the host
+ * or uses atomics; both are graph-capturable.
+ * sba_style_mean: the column means of w [n][D] f32, in float64, in an order that is part of the contract.  For column d:
+ *     P_c = the float64 sum of rows 256 c .. min(256 c + 256, n) - 1, added in ascending row order;
+ *     T   = the float64 sum of the P_c, in ascending c;        (every sum starts from +0.0)
+ *     mean64[d] = T / n, one IEEE division;   mean32[d] = (float) mean64[d], round to nearest.
+ *   The result does not depend on the grid; two calls give the same bits; a NaN or Inf in a column reaches that column
+ *   only.  One launch for the partials and one for the tail; a single launch when n <= 256.
+ *   workspace: at least ceil(n / 256) * D * 8 bytes, 8-byte aligned; may be NULL when n <= 256.
+ *   SBA_E_ARG unless 1 <= n <= 2^20, 1 <= D <= 4096, w and mean32 non-NULL and 4-byte aligned, mean64 non-NULL and 8-byte
+ *   aligned, and workspace as stated.
+ * sba_style_truncate: out[r][d] = w_avg[d] + psi * (w[r][d] - w_avg[d]) over w [n][D], w_avg [D], as three separately
+ *   rounded f32 operations -- subtract, multiply, add; never a fused multiply-add.  psi == 1.0f exactly: every row is
+ *   copied bit for bit (the formula does not give w back in floating point).  out == w (in place) is allowed.
+ *   SBA_E_ARG unless psi is finite, 1 <= n <= 2^20, 1 <= D <= 4096, and all pointers are non-NULL and 4-byte aligned.
+ * Both: SBA_E_ARG before any launch, nothing written. */
+int sba_style_mean(const float* w, int n, int D, double* mean64, float* mean32, void* workspace, void* stream);
+int sba_style_truncate(const float* w, const float* w_avg, float psi, float* out, int n, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

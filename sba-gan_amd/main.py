@@ -18,7 +18,7 @@ if _HERE not in sys.path:
 from datasets import TextDataset, tokenize  # noqa: E402
 from miscc import cli, transforms  # noqa: E402
 from miscc.config import cfg  # noqa: E402
-from sbagan import evaluation, track  # noqa: E402
+from sbagan import evaluation, track, truncation  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -111,6 +111,16 @@ def main(argv=None, args=None, dataset_cls=TextDataset, make_trainer=None):
             print(track.not_tracked_line(args))
     elif getattr(args, 'track', 0):
         print('--track is ignored outside training')
+    given = [f for f in ('truncation', 'truncation_sweep') if getattr(args, f, None) is not None]
+    if training:
+        if given:
+            print('%s %s ignored in training' % (' / '.join('--' + f for f in given), 'is' if len(given) == 1 else 'are'))
+    else:
+        algo.truncation, algo.truncation_n = getattr(args, 'truncation', None), getattr(args, 'truncation_n', 16384)
+        algo.truncation_sweep = getattr(args, 'truncation_sweep', None)
+        algo.truncation_sweep_n = getattr(args, 'truncation_sweep_n', 0)
+        if algo.truncation_sweep and cfg.B_VALIDATION and truncation.not_swept_line(args):
+            print(truncation.not_swept_line(args))
     start_t = time.time()
     if training:
         algo.train()

@@ -7,6 +7,7 @@
     [--diffaug_p P]  [--ada TARGET]  [--ada_kimg K]  [--ada_interval N]  [--ada_pmax P]
     [--geoaug POLICY: flip,rot90,scale,rotate in front of the discriminators]
     [--track E]  [--track_split NAME]  [--track_n N]  [--track_captions C]  [--track_best KEY: GAN training]
+    [--truncation PSI[,PSI]]  [--truncation_n N]  [--truncation_sweep LIST]  [--truncation_sweep_n N: sampling / gen_example]
     [--retrieval E]  [--retrieval_only: DAMSM pre-training]
     [--bert_dir DIR: the BERT entry points]
 
@@ -22,7 +23,7 @@ import re
 import numpy as np
 import torch
 
-from sbagan import evaluation, track
+from sbagan import evaluation, track, truncation
 
 from .config import cfg, cfg_from_file
 
@@ -199,6 +200,32 @@ def options(what, default_cfg, argv=None, bert=False, gan=False):
                     help='with --track: whenever an evaluation improves on the best KEY so far, write '
                          'Model/netG_best.pth (the bytes of that epoch\'s checkpoint) and Model/best.json; KEY one of '
                          + ', '.join(track.BEST_KEYS) + '.  On resume a best.json beside TRAIN.NET_G is honoured')
+    ap.add_argument('--truncation', dest='truncation', default=None, metavar='PSI[,PSI]', type=truncation.parse_psi,
+                    help='sampling / gen_example: the truncation trick in W (sbagan.truncation) -- every style the later '
+                         'stages read is pulled towards the mean style, w_avg + PSI (w - w_avg), PSI in [0, 1]: 1 is the '
+                         'generator as trained (bit for bit the run without the flag), 0 the mean style; a pair sets '
+                         'stage 2 and stage 3 apart (BRANCH_NUM 3).  w_avg is the mean of the checkpoint\'s own mapping '
+                         'network over --truncation_n codes from a generator of its own, summed in a fixed float64 order '
+                         '(HIP).  The PNGs, every evaluator that is on and the attention maps see the truncated images; '
+                         'sampling writes truncation.json.  model.G_NET also feeds z to its first stage: its 64 px '
+                         'image does not move.  Default: off.  Ignored in training and by the DAMSM entry points')
+    ap.add_argument('--truncation_n', dest='truncation_n', default=truncation.DEFAULT_N, metavar='N',
+                    type=_ranged_int('N', 1, truncation.MAX_N, 'a number of codes from 1 to %d' % truncation.MAX_N),
+                    help='with --truncation / --truncation_sweep: codes in the mean style (default %d)'
+                         % truncation.DEFAULT_N)
+    ap.add_argument('--truncation_sweep', dest='truncation_sweep', default=None, metavar='LIST',
+                    type=truncation.parse_sweep,
+                    help='sampling: after the normal run has written its files, evaluate the generator at every psi of '
+                         'the comma-separated LIST (each in [0, 1], none twice) over ONE frozen set of the sampled split '
+                         '-- the same captions, noise and eps for every psi, the real images through the trunk once -- '
+                         'with those of --fid, --kid, --prdc and --r_precision that are on (at least one must be): one '
+                         'line per psi, truncation_sweep.json, no image written.  With or without --truncation.  '
+                         'gen_example: also write <key>/0_s_<idx>_psi.png, the last stage at every psi of LIST over one '
+                         'noise draw.  On this project\'s own trunk and compute dtype: comparable between runs of this '
+                         'project only')
+    ap.add_argument('--truncation_sweep_n', dest='truncation_sweep_n', default=0, metavar='N',
+                    type=_ranged_int('N', 0, None, '0 (the whole split) or a number of images'),
+                    help='with --truncation_sweep: the first N images of the split, caption 0 of each; 0 = all of them')
     if bert:        # the BERT entry points (pretrain_DAMSM_bert.py, main_bert.py)
         ap.add_argument('--bert_dir', dest='bert_dir', type=str, default=None,
                         help='local HuggingFace BERT directory (config, weights, vocab.txt); default: random trunk')
@@ -208,6 +235,9 @@ def options(what, default_cfg, argv=None, bert=False, gan=False):
             ap.error('--%s needs a non-empty --diffaug POLICY' % flag)
     if args.ada is not None and args.diffaug_p is not None and args.diffaug_p > args.ada_pmax:
         ap.error('--diffaug_p %g is above --ada_pmax %g' % (args.diffaug_p, args.ada_pmax))
+    problem = truncation.check_flags(args) if gan else None
+    if problem:
+        ap.error(problem)
     if args.track and gan:
         problem = track.check_flags(args)
         if problem:

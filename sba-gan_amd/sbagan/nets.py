@@ -425,10 +425,28 @@ class _GBase(nn.Module):
     # serial chain of its backward pass.  Same kernels, same operands.  SBA_FORK_CTX=0: inside the stages, as before.
     fork_ctx = os.environ.get('SBA_FORK_CTX', '1') != '0'
 
+    # --truncation: the truncation trick in W (sbagan/truncation.py).  None = off: not one launch, allocation
+    # or stream operation differs.  A sbagan.truncation.Truncation: every w below is replaced, right behind the mapping
+    # network and on its stream, by w_avg + psi (w - w_avg) -- so the style and key pre-projections of the side stream read
+    # the truncated w, and it crosses to the main stream behind the same `_CrossStream` guard.  What that reaches:
+    #   model.G_NET       z itself also feeds the first stage: only the AdaIN styles of stages 2 and 3 are truncated, the
+    #                     64 px image does not move;
+    #   the BERT classes  z acts through w alone: psi = 0 makes the images independent of the noise;
+    #   G_NET_MIX         ws[0] (stage 2) takes the first psi of a pair, ws[1] (stage 3) the second.
+    # Inference only (no backward): raises in training mode or with grad enabled.
+    truncation = None
+
+    def _truncated(self, ws):
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError('a generator with a truncation set runs in eval mode under no_grad only: the truncation '
+                               'has no backward (set netG.truncation = None to train)')
+        return self.truncation.apply(ws)
+
     def _styles(self, *zs, word_embs=None):
         self._pre = None
         if not (self.fork_mapping and zs[0].is_cuda):
-            return [self.mapping_net(z) for z in zs], None
+            ws = [self.mapping_net(z) for z in zs]
+            return (ws if self.truncation is None else self._truncated(ws)), None
         main = torch.cuda.current_stream()
         side = _MAP_STREAMS.get(zs[0].device)
         if side is None:
@@ -436,6 +454,8 @@ class _GBase(nn.Module):
         side.wait_stream(main)
         with torch.cuda.stream(side):
             ws = [self.mapping_net(z) for z in zs]
+            if self.truncation is not None:
+                ws = self._truncated(ws)
             if self.fork_ctx and self._fork_guard and word_embs is not None and self.branch_num > 1:
                 stages = [(self.h_net2, ws[0])] + ([(self.h_net3, ws[-1])] if self.branch_num > 2 else [])
                 self._pre = [(st.style_of(w), st.keys_of(word_embs)) for st, w in stages]

@@ -2922,3 +2922,45 @@ def geoaug(real, fake, mats):
     """The geometrically augmented [real | fake] batch of one discriminator pass (real = None: the fake images alone).
     mats: f32 [(nr + nf)][4], one matrix per image, as sba_geoaug_prepare writes them (sbagan.geoaug.GeoAugment)."""
     return GeoAugFn.apply(fake.float().contiguous(), None if real is None else real.float().contiguous(), mats)
+
+
+# ----------------------------------------------------------------------------
+# The truncation trick in W (csrc/truncation.hip; sbagan/truncation.py; DESIGN.md 7s)
+# ----------------------------------------------------------------------------
+STYLE_MEAN_CHUNK = 256      # rows per float64 partial sum of sba_style_mean: part of its contract
+
+
+def style_mean(w):
+    """(mean64 [D] float64, mean32 [D] float32): the column means of the contiguous f32 matrix w [n][D] in the fixed order
+    of sba_style_mean -- float64 partial sums over chunks of 256 rows in row order, added in chunk order, one division,
+    mean32 its rounding.  One launch for n <= 256, two otherwise, on the current stream; no host sync."""
+    _need_gpu(w)
+    if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or w.numel() < 1:
+        raise ValueError('style_mean: w must be a non-empty contiguous float32 matrix [n][D], got %s %s'
+                         % (w.dtype, tuple(w.shape)))
+    n, D = w.shape
+    chunks = (n + STYLE_MEAN_CHUNK - 1) // STYLE_MEAN_CHUNK
+    mean64 = torch.empty((D,), dtype=torch.float64, device=w.device)
+    mean32 = torch.empty((D,), dtype=torch.float32, device=w.device)
+    workspace = torch.empty((chunks, D), dtype=torch.float64, device=w.device) if chunks > 1 else None
+    call('sba_style_mean', _p(w), n, D, _p(mean64), _p(mean32), _p(workspace), _stream())
+    return mean64, mean32
+
+
+def style_truncate(w, w_avg, psi, out=None):
+    """w_avg + psi (w - w_avg) over the rows of the contiguous f32 matrix w [n][D] (sba_style_truncate): three separately
+    rounded f32 operations, psi == 1 a bit-exact copy.  out: where to write (w itself: in place); default a new tensor.
+    One launch on the current stream, no host sync; no backward."""
+    _need_gpu(w)
+    if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or w.numel() < 1:
+        raise ValueError('style_truncate: w must be a non-empty contiguous float32 matrix [n][D], got %s %s'
+                         % (w.dtype, tuple(w.shape)))
+    n, D = w.shape
+    if w_avg.dtype != torch.float32 or tuple(w_avg.shape) != (D,) or not w_avg.is_contiguous() or w_avg.device != w.device:
+        raise ValueError('style_truncate: w_avg must be contiguous float32 [%d] on %s' % (D, w.device))
+    if out is None:
+        out = torch.empty_like(w)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, D) or not out.is_contiguous() or out.device != w.device:
+        raise ValueError('style_truncate: out must be contiguous float32 [%d][%d] on %s' % (n, D, w.device))
+    call('sba_style_truncate', _p(w), _p(w_avg), float(psi), _p(out), n, D, _stream())
+    return out

@@ -23,6 +23,9 @@ What makes it an instrument of training rather than a second sampling run:
 The figures live on this project's own trunk and compute dtype, as their sampling twins do: comparable between epochs and
 runs of this project only.
 
+The frozen set and the measurement over it are FrozenSet, which needs no trainer and no training step: Tracker derives
+from it, and sampling()'s --truncation_sweep measures every psi on one (sbagan.truncation.sweep).
+
 Host code; importing this module loads no device library (miscc.cli imports it for the flags)."""
 import collections
 import json
@@ -176,72 +179,57 @@ class _Loader(object):
         self.dataset, self.num_workers = dataset, num_workers
 
 
-class Tracker(object):
-    """trainer: the condGANTrainer (its device, batch size, data loader, model directory, text and noise hooks, evaluator
-    options and, by the time of the first evaluation, its GANStep); every / split / n / captions / best: --track,
-    --track_split, --track_n, --track_captions, --track_best."""
+class FrozenSet(object):
+    """The frozen evaluation set (see the module's text) and the measurement over it, without a trainer or a GANStep:
+    what --track evaluates every due epoch (Tracker) and what sampling()'s --truncation_sweep evaluates per psi
+    (sbagan.truncation.sweep).
 
-    def __init__(self, trainer, every, split='test', n=0, captions=1, best=None):
-        from miscc.config import cfg
-        self.trainer, self.every, self.split, self.n, self.captions = trainer, int(every), str(split), int(n), int(captions)
-        if self.every < 1:
-            raise ValueError('track must be an interval of at least 1 epoch (got %d)' % self.every)
+    encode: the trainer's _encode hook (text_encoder, captions, cap_lens) -> (words_embs, sent_emb); noise_shape: n ->
+    the shape of the noise of n rows; batch_size, device; values: {option name: value} of sbagan.evaluation's options
+    (those of the tracked evaluators count); split: the name the evaluators are told; n: the first n images of the data
+    set (0: all); captions: captions 0 .. captions - 1 of each; num_workers: of the real-image pass.  The image encoder
+    (InceptionHIP) and the data set arrive with prepare()."""
+
+    def __init__(self, encode, noise_shape, batch_size, device, values, split, n=0, captions=1, num_workers=0):
+        self.encode, self.noise_shape, self.batch_size, self.device = encode, noise_shape, int(batch_size), device
+        self.values, self.split, self.n, self.captions = tracked_values(values), str(split), int(n), int(captions)
+        self.num_workers = num_workers
         if self.n < 0:
-            raise ValueError('track_n must be 0 (the whole split) or a number of images (got %d)' % self.n)
-        if not 1 <= self.captions <= cfg.TEXT.CAPTIONS_PER_IMAGE:
-            raise ValueError('track_captions must be from 1 to TEXT.CAPTIONS_PER_IMAGE = %d (got %d)'
-                             % (cfg.TEXT.CAPTIONS_PER_IMAGE, self.captions))
-        self.values = tracked_values({opt.name: getattr(trainer, opt.name) for opt in evaluation.OPTIONS})
+            raise ValueError('n must be 0 (the whole split) or a number of images (got %d)' % self.n)
         if not any(self.values[stem] for stem in TRACKED):
-            raise ValueError('track needs at least one of fid, kid, prdc, r_precision: they are what it measures')
-        if best is not None and not self.values[best.split('.')[0]]:
-            raise ValueError('track_best %s needs %s' % (best, best.split('.')[0]))
-        resume = os.path.dirname(cfg.TRAIN.NET_G) if cfg.TRAIN.NET_G else None
-        self.best = Best(best, trainer.model_dir, resume) if best is not None else None
-        self.path = os.path.join(trainer.model_dir, 'track.jsonl')
+            raise ValueError('a frozen set needs at least one of fid, kid, prdc, r_precision: they are what it measures')
         self.prepared = False
-        self.records = []           # of this run, as appended
-        self.timing = {}            # seconds of the last evaluation's parts (tools/bench_track.py)
-
-    def due(self, epoch):
-        return due(epoch, self.every)
+        self.timing = {}            # seconds of the last measurement's parts (tools/bench_track.py)
 
     # ------------------------------------------------------------------ once per run
-    def _dataset(self):
-        from miscc.config import cfg
-        sampled = self.trainer.data_loader.dataset
-        extra = {'bert_dir': sampled.bert_dir} if hasattr(sampled, 'bert_dir') else {}
-        return type(sampled)(sampled.data_dir, self.split, base_size=cfg.TREE.BASE_SIZE, transform=None, **extra)
-
-    def prepare(self, text_encoder, dataset=None):
-        """the frozen evaluation set (see the module's text); dataset: the held-out data set when the caller has one"""
+    def prepare(self, text_encoder, image_encoder, dataset, what='--track'):
+        """the frozen evaluation set (see the module's text) over `dataset`; what: the flag named in messages"""
         import numpy as np
         import torch
         from miscc import cli
         from miscc.config import cfg
         from . import ops
         from .nearest import encode_train
-        from .rprecision import encode_pool
         from .trainer import build_mask
         t0 = time.time()
-        tr, dev, B = self.trainer, self.trainer.device, self.trainer.batch_size
-        self.image_encoder = enc = tr.gan.image_encoder
+        dev, B = self.device, self.batch_size
+        self.image_encoder = enc = image_encoder
         if enc is None or not hasattr(enc, 'pooled_features'):
-            raise RuntimeError('--track needs the HIP image encoder of the step (InceptionHIP.pooled_features)')
-        self.dataset = ds = dataset if dataset is not None else self._dataset()
+            raise RuntimeError('%s needs the HIP image encoder (InceptionHIP.pooled_features)' % what)
+        self.dataset = ds = dataset
         total = len(ds)
         n = total if self.n == 0 else self.n
         if n > total:
-            raise ValueError('track_n %d is more than the %d images of the %s split' % (n, total, self.split))
+            raise ValueError('%s: %d is more than the %d images of the %s split' % (what, n, total, self.split))
         C, W, per = self.captions, cfg.TEXT.WORDS_NUM, ds.embeddings_num
-        workers = getattr(tr.data_loader, 'num_workers', 0)
+        workers = self.num_workers
         loader = _Loader(ds, workers)
 
         # the evaluators are built once here for what is refused at construction (a value out of range, a --fid_stats
         # file under another key) and for what every later Suite is handed in self.cache: the R-precision pool and the
         # real statistics read from --fid_stats
         def encode(enc_, captions, cap_lens):
-            return tr._encode(enc_, captions, cap_lens)
+            return self.encode(enc_, captions, cap_lens)
         self._suite_args = (self.values, self.split, encode, lambda: self.image_encoder, loader, B, dev)
         self.cache = {}
         suite = evaluation.Suite(*self._suite_args, cache=self.cache)
@@ -272,8 +260,8 @@ class Tracker(object):
             order = np.argsort(-lens[lo:lo + B], kind='stable')
             inverse = np.empty_like(order)
             inverse[order] = np.arange(len(order))
-            w, s = tr._encode(text_encoder, torch.from_numpy(caps[lo:lo + B][order]).to(dev),
-                              torch.from_numpy(lens[lo:lo + B][order]).to(dev))
+            w, s = self.encode(text_encoder, torch.from_numpy(caps[lo:lo + B][order]).to(dev),
+                               torch.from_numpy(lens[lo:lo + B][order]).to(dev))
             full = torch.zeros((w.size(0), w.size(1), W), dtype=torch.float32, device=dev)
             full[:, :, :min(W, w.size(2))] = w.detach().float()[:, :, :W]   # (the columns past the longest caption: zeros)
             back = torch.from_numpy(inverse).to(dev)
@@ -286,18 +274,18 @@ class Tracker(object):
         self.keys = [str(k) for k in ds.filenames[:n] for _ in range(C)]
         gen = torch.Generator(device=dev)
         gen.manual_seed(SEED)
-        self.noise = torch.randn(tr._noise_shape(n * C), generator=gen, device=dev, dtype=torch.float32)
+        self.noise = torch.randn(self.noise_shape(n * C), generator=gen, device=dev, dtype=torch.float32)
         self.eps = torch.randn((n * C, cfg.GAN.CONDITION_DIM), generator=gen, device=dev, dtype=torch.float32)
         self.images, self.rows = n, n * C
         self.prepared = True
         torch.cuda.synchronize()
         self.timing['prepare'] = time.time() - t0
-        print('--track: %d images x %d captions of the %s split prepared in %.1f s'
-              % (n, C, self.split, self.timing['prepare']))
+        print('%s: %d images x %d captions of the %s split prepared in %.1f s'
+              % (what, n, C, self.split, self.timing['prepare']))
 
     # ------------------------------------------------------------------ per evaluation
     def slices(self):
-        return [(lo, min(lo + self.trainer.batch_size, self.rows)) for lo in range(0, self.rows, self.trainer.batch_size)]
+        return [(lo, min(lo + self.batch_size, self.rows)) for lo in range(0, self.rows, self.batch_size)]
 
     def measure(self, generator, ca_net):
         """{stem: result} of `generator` (netG in eval mode, or its fused wrapper) over the frozen set: fresh evaluators,
@@ -331,6 +319,52 @@ class Tracker(object):
             per[rec.stem] = time.time() - ts
         self.timing.update(generate=t1 - t0, results=time.time() - t1, result_of=per)
         return results
+
+
+class Tracker(FrozenSet):
+    """trainer: the condGANTrainer (its device, batch size, data loader, model directory, text and noise hooks, evaluator
+    options and, by the time of the first evaluation, its GANStep); every / split / n / captions / best: --track,
+    --track_split, --track_n, --track_captions, --track_best."""
+
+    def __init__(self, trainer, every, split='test', n=0, captions=1, best=None):
+        from miscc.config import cfg
+        self.trainer, self.every = trainer, int(every)
+        if self.every < 1:
+            raise ValueError('track must be an interval of at least 1 epoch (got %d)' % self.every)
+        if int(n) < 0:
+            raise ValueError('track_n must be 0 (the whole split) or a number of images (got %d)' % int(n))
+        if not 1 <= int(captions) <= cfg.TEXT.CAPTIONS_PER_IMAGE:
+            raise ValueError('track_captions must be from 1 to TEXT.CAPTIONS_PER_IMAGE = %d (got %d)'
+                             % (cfg.TEXT.CAPTIONS_PER_IMAGE, int(captions)))
+        values = tracked_values({opt.name: getattr(trainer, opt.name) for opt in evaluation.OPTIONS})
+        if not any(values[stem] for stem in TRACKED):
+            raise ValueError('track needs at least one of fid, kid, prdc, r_precision: they are what it measures')
+        if best is not None and not values[best.split('.')[0]]:
+            raise ValueError('track_best %s needs %s' % (best, best.split('.')[0]))
+        # (the hooks are read off the trainer when they are called: a test or a tool may have replaced them since)
+        super(Tracker, self).__init__(lambda *a: trainer._encode(*a), lambda rows: trainer._noise_shape(rows),
+                                      trainer.batch_size, trainer.device, values, split, n, captions,
+                                      getattr(trainer.data_loader, 'num_workers', 0))
+        resume = os.path.dirname(cfg.TRAIN.NET_G) if cfg.TRAIN.NET_G else None
+        self.best = Best(best, trainer.model_dir, resume) if best is not None else None
+        self.path = os.path.join(trainer.model_dir, 'track.jsonl')
+        self.records = []           # of this run, as appended
+
+    def due(self, epoch):
+        return due(epoch, self.every)
+
+    # ------------------------------------------------------------------ once per run
+    def _dataset(self):
+        from miscc.config import cfg
+        sampled = self.trainer.data_loader.dataset
+        extra = {'bert_dir': sampled.bert_dir} if hasattr(sampled, 'bert_dir') else {}
+        return type(sampled)(sampled.data_dir, self.split, base_size=cfg.TREE.BASE_SIZE, transform=None, **extra)
+
+    def prepare(self, text_encoder, dataset=None):
+        """the frozen evaluation set; dataset: the held-out data set when the caller has one"""
+        self.batch_size = self.trainer.batch_size
+        super(Tracker, self).prepare(text_encoder, self.trainer.gan.image_encoder,
+                                     dataset if dataset is not None else self._dataset())
 
     def evaluate(self, netG, text_encoder, epoch, iteration, stepper=None, checkpoint=None):
         """One evaluation of the EMA weights at the end of `epoch`.  checkpoint: the name of the netG_epoch_N.pth save_model

@@ -31,7 +31,7 @@ from datasets import as_batch, prepare_data
 from miscc.config import cfg
 from miscc.utils import copy_G_params, load_params, mkdir_p, weights_init
 from model import CNN_ENCODER, D_NET64, D_NET128, D_NET256, G_NET, RNN_ENCODER
-from sbagan import evaluation
+from sbagan import evaluation, truncation
 from sbagan.trainer import GANStep, build_mask, prepare_labels
 
 
@@ -422,16 +422,71 @@ class condGANTrainer(object):
         cut = ckpt.rfind('.pth')
         return ckpt[:cut] if cut >= 0 else ckpt
 
-    def _generate(self, netG, text_encoder, captions, cap_lens, noise, with_sent=False, with_att=False):
+    def _generate(self, netG, text_encoder, captions, cap_lens, noise, with_sent=False, with_att=False, keep=None):
         """fake images of every stage for one caption batch (noise is refilled in place); with_sent: and the sentence
-        embeddings they were generated from; with_att: and the attention maps of every later stage"""
+        embeddings they were generated from; with_att: and the attention maps of every later stage; keep: a dict that
+        receives the call's inputs (sent_emb, words_embs, mask, eps) for a caller that runs the generator on them again
+        (_forward_kept)"""
         words_embs, sent_emb = self._encode(text_encoder, captions, cap_lens)
         noise.normal_(0, 1)
-        with torch.no_grad():
-            fake_imgs, att_maps, _, _ = netG(noise, sent_emb, words_embs, build_mask(captions, words_embs.size(2)))
+        mask = build_mask(captions, words_embs.size(2))
+        if keep is not None:
+            keep.update(sent_emb=sent_emb, words_embs=words_embs, mask=mask)
+            fake_imgs, att_maps = self._forward_kept(netG, noise, keep)
+        else:
+            with torch.no_grad():
+                fake_imgs, att_maps, _, _ = netG(noise, sent_emb, words_embs, mask)
         if with_att:
             return fake_imgs, att_maps
         return (fake_imgs, sent_emb) if with_sent else fake_imgs
+
+    @staticmethod
+    def _forward_kept(netG, noise, kept):
+        """(fake images, attention maps) of netG on `noise` and the inputs of `kept` (_generate's keep).  The conditioning
+        eps is part of them: the first call draws it -- by the very call CA_NET would make at this point of the global
+        generator's sequence, so the run's draws are those of a run that keeps nothing -- and every later call reads
+        it back and draws nothing."""
+        ca_net = truncation.unwrap(netG).ca_net
+        held = ca_net.eps
+        if 'eps' not in kept:
+            kept['eps'] = held if held is not None else torch.randn(
+                (kept['sent_emb'].size(0), ca_net.c_dim), dtype=torch.float32, device=kept['sent_emb'].device)
+        ca_net.eps = kept['eps']
+        try:
+            with torch.no_grad():
+                return netG(noise, kept['sent_emb'], kept['words_embs'], kept['mask'])[:2]
+        finally:
+            ca_net.eps = held
+
+    truncation_n = truncation.DEFAULT_N     # --truncation_n: codes in the mean style (the module, read before the line below)
+    truncation = None           # --truncation PSI[,PSI]: the truncation trick in W for sampling / gen_example (DESIGN.md 7s)
+    truncation_sweep = None     # --truncation_sweep LIST: sampling's psi sweep over a frozen set; gen_example's psi strips
+    truncation_sweep_n = 0      # --truncation_sweep_n: images of the frozen set (0: the whole split)
+
+    def _set_truncation(self, *generators):
+        """--truncation: set on every loaded generator (each takes the mean of its own mapping network); returns the
+        first one's Truncation, or None when the flag is off"""
+        if self.truncation is None:
+            return None
+        return [truncation.set_truncation(g, self.truncation, self.truncation_n) for g in generators][0]
+
+    def _write_psi_strips(self, netG, noise, kept, order, out_dir):
+        """--truncation_sweep in gen_example: <out_dir>/0_s_<original index>_psi.png per caption -- the last stage's image
+        of netG at every psi of the list, left to right, over the noise and the inputs of the run's own call (`kept`);
+        no text is drawn, nothing is drawn from a generator.  The generator's truncation is put back."""
+        net = truncation.unwrap(netG)
+        held, base, tiles = net.truncation, net.truncation, []
+        try:
+            for psi in self.truncation_sweep:
+                if base is None:
+                    base = truncation.Truncation(net, psi, self.truncation_n)
+                net.truncation = base.with_psi(psi)
+                tiles.append(self._forward_kept(netG, noise, kept)[0][-1])
+        finally:
+            net.truncation = held
+        for j, src in enumerate(order):
+            strip = np.concatenate([_to_uint8(batch[j]) for batch in tiles], axis=1)
+            Image.fromarray(strip).save(os.path.join(out_dir, '0_s_%d_psi.png' % int(src)))
 
     attention_maps = False      # --attention_maps: the attention overlays of save_img_results / gen_example
 
@@ -465,7 +520,9 @@ class condGANTrainer(object):
 
     def sampling(self, split_dir):
         """trainer.py:363-433: one image (the last stage's) per caption of the split; beside them what the evaluators
-        that are on report (sbagan.evaluation: its table names their attributes here, set below the class)."""
+        that are on report (sbagan.evaluation: its table names their attributes here, set below the class).  With
+        `truncation` the generator is truncated in W (every file and figure sees it; truncation.json); with
+        `truncation_sweep` the psi sweep follows the run (sbagan.truncation.sweep; truncation_sweep.json)."""
         root = self._output_root()
         if root is None:
             return None
@@ -474,6 +531,8 @@ class condGANTrainer(object):
         out_dir = os.path.join(root, 'valid' if split_dir == 'test' else split_dir)
         mkdir_p(out_dir)
         netG, text_encoder = self._load_inference_models()
+        truncated = self._set_truncation(netG)
+        w_rms = truncation.WDistance(truncated) if truncated is not None else None
         suite.attach(text_encoder)
         noise = torch.empty(self._noise_shape(self.batch_size), device=self.device)
         made = set()
@@ -483,22 +542,33 @@ class condGANTrainer(object):
             real_imgs, captions, cap_lens, class_ids, keys = prepare_data(data)
             fake_imgs, sent_emb = self._generate(netG, text_encoder, captions, cap_lens, noise, with_sent=True)
             last = fake_imgs[-1]
+            if w_rms is not None:
+                w_rms.update(noise)
             suite.update(last, real_imgs[-1], sent_emb, class_ids, keys)
             for img, key in zip(last, keys):
                 self._write_image(img, os.path.join(out_dir, 'single', key) + '_s-1.png', made)
         for stem, (evaluator, result) in suite.finish(out_dir).items():
             setattr(self, stem + '_evaluator', evaluator)
             setattr(self, stem + '_result', result)
+        if truncated is not None:
+            self.truncation_result = truncation.write_json(out_dir, truncated, w_rms)
+        if self.truncation_sweep:
+            # behind the normal run and its files: the sweep measures on a frozen set of its own and draws nothing
+            ranking = suite.on.get('r_precision')
+            trunk = suite.image_encoder if suite.image_encoder is not None else getattr(ranking, 'image_encoder', None)
+            self.truncation_sweep_result = truncation.sweep(self, netG, text_encoder, self.truncation_sweep, split_dir,
+                                                            out_dir, n=self.truncation_sweep_n, image_encoder=trunk)
         return out_dir
 
     def gen_example(self, data_dic):
         """trainer.py:435-518: data_dic[key] = [captions (n x Lmax int64, sorted by length), cap_lens, sorted_indices];
         every stage's image per caption, named by the caption's ORIGINAL position; with attention_maps also the
-        top-5 word strips 0_s_<index>_a<k>.png."""
+        top-5 word strips 0_s_<index>_a<k>.png; with truncation_sweep also the psi strips 0_s_<index>_psi.png."""
         root = self._output_root()
         if root is None:
             return None
         netG, text_encoder = self._load_inference_models()
+        self._set_truncation(netG)
         for key, (captions, cap_lens, order) in data_dic.items():
             out_dir = os.path.join(root, key)
             print(out_dir)
@@ -506,12 +576,15 @@ class condGANTrainer(object):
             captions = torch.from_numpy(np.ascontiguousarray(captions)).to(self.device)
             cap_lens = torch.from_numpy(np.ascontiguousarray(cap_lens)).to(self.device)
             noise = torch.empty(self._noise_shape(captions.shape[0]), device=self.device)
-            stages, att_maps = self._generate(netG, text_encoder, captions, cap_lens, noise, with_att=True)
+            kept = {} if self.truncation_sweep else None
+            stages, att_maps = self._generate(netG, text_encoder, captions, cap_lens, noise, with_att=True, keep=kept)
             for stage, batch in enumerate(stages):
                 for img, src in zip(batch, order):
                     self._write_image(img, os.path.join(out_dir, '0_s_%d_g%d.png' % (int(src), stage)))
             if self.attention_maps:
                 self._write_top_words(stages, att_maps, captions, cap_lens, order, out_dir)
+            if self.truncation_sweep:
+                self._write_psi_strips(netG, noise, kept, order, out_dir)
         return root
 
 

@@ -50,7 +50,8 @@ class condGANTrainer(trainer.condGANTrainer):
         return words_embs.detach(), sent_emb.detach()
 
     def gen_example(self, data_dic):
-        """trainer_bert.py:440-566; with attention_maps also the top-5 word strips 0_s_<idx>_a<k>_<set>.png."""
+        """trainer_bert.py:440-566; with attention_maps also the top-5 word strips 0_s_<idx>_a<k>_<set>.png; with
+        truncation_sweep also the psi strips 0_s_<idx>_psi.png of G_NET on z1 (the 'A' set)."""
         root = self._output_root()
         if root is None:
             return None
@@ -70,6 +71,7 @@ class condGANTrainer(trainer.condGANTrainer):
             nets.append(self._inference_generator(net.to(dev).eval()))
         netG, netG_mix = nets
         print('Load G from: ', cfg.TRAIN.NET_G)
+        self._set_truncation(netG, netG_mix)
         for key, (captions, cap_lens, order) in data_dic.items():
             out_dir = os.path.join(root, key)
             print(out_dir)
@@ -81,11 +83,14 @@ class condGANTrainer(trainer.condGANTrainer):
             noise = torch.empty((2, captions.shape[0], cfg.GAN.Z_DIM), device=dev)
             noise.normal_(0, 1)
             swapped = torch.cat([noise[1:], noise[:1]], 0)
+            # (with truncation_sweep the 'A' call keeps its inputs, its eps among them, for the psi strips: the same draws)
+            kept = {'sent_emb': sent_emb, 'words_embs': words_embs, 'mask': mask} if self.truncation_sweep else None
             with torch.no_grad():
                 outs = {'AB': netG_mix(noise, sent_emb, words_embs, mask)[:2],
-                        'BA': netG_mix(swapped, sent_emb, words_embs, mask)[:2],
-                        'A': netG(noise[0], sent_emb, words_embs, mask)[:2],
-                        'B': netG(noise[1], sent_emb, words_embs, mask)[:2]}
+                        'BA': netG_mix(swapped, sent_emb, words_embs, mask)[:2]}
+                outs['A'] = (netG(noise[0], sent_emb, words_embs, mask)[:2] if kept is None
+                             else self._forward_kept(netG, noise[0], kept))
+                outs['B'] = netG(noise[1], sent_emb, words_embs, mask)[:2]
             for tag in ('AB', 'BA', 'A', 'B'):
                 stages, att_maps = outs[tag]
                 for stage, batch in enumerate(stages):
@@ -93,4 +98,6 @@ class condGANTrainer(trainer.condGANTrainer):
                         self._write_image(img, os.path.join(out_dir, '0_s_%d_g%d_%s.png' % (int(src), stage, tag)))
                 if self.attention_maps:
                     self._write_top_words(stages, att_maps, captions, cap_lens, order, out_dir, suffix='_' + tag)
+            if self.truncation_sweep:       # from the plain G_NET on noise[0]: the 'A' set's inputs
+                self._write_psi_strips(netG, noise[0], kept, order, out_dir)
         return root
